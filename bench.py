@@ -18,13 +18,25 @@ Protocol: actions U(-1, 1) from Philox4x32-10 keyed by 0
 distinct batch per step; an untimed pre-roll (--preroll, 200 steps) ages the episodes past
 their first steps so the timed window sees steady-state contact counts and auto-resets, then
 W warm-up steps, then EXACTLY K timed steps (one HIP graph of the K launches) bracketed by a
-barrier + device sync on both sides, max over ranks.  The timed windows (--windows, default 5;
-value = the median window) replay the same captured graphs, i.e. the same K action batches;
-the env state moves on between windows, so every window steps different states.
+barrier + device sync on both sides, max over ranks.
 
-  python bench.py [--gpus N --steps K --warmup W]
+A plain run does only what the headline needs: set-up, pre-roll, warm-up, one timed window of the
+K steps, the --dump-outputs files if asked for, and the result line (static roofline figures
+included: they are arithmetic on the measured time and the shipped PMC summaries).  --full adds
+everything that takes runs of its own: five timed windows instead of one (--windows; value = the
+median window; the windows replay the same captured graphs, i.e. the same K action batches, and
+the env state moves on between them, so every window steps different states), the float32 leg and
+the other BASELINE configs (--legs), the CPU-oracle baseline, and at N > 1 the RCCL all-gather
+timing.
+
+--dump-outputs DIR writes what the last timed step returned to its caller -- StepResult's obs,
+reward, done, truncated and terminal_obs of this rank's envs -- as DIR/<name>.npy (float32; rank
+r > 0 writes <name>.rank<r>.npy).  Actions, reset noise and env count are functions of the
+arguments alone, so two builds run with the same arguments step the same inputs.
+
+  python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
-  python -m torch.distributed.run --nproc-per-node 2 ... bench.py --gpus 2 --dry-run-cpu
+  python -m torch.distributed.run --nproc-per-node 2 ... bench.py --gpus 2 --dry-run-cpu --full
       (CI: the N > 1 control flow -- gloo process group, barriers, max over ranks, the flat
        gather, the JSON line -- on CPU with a no-physics stand-in env; value meaningless)
 """
@@ -41,6 +53,7 @@ METRIC = "env steps/sec (whole node) at N parallel envs, Ant + Humanoid, 1/2/4/8
 ENV_ID = "AntPyBulletEnv-v0"
 ENVS_PER_GPU = 16384
 ACTION_SEED = 0x5EED
+DUMP_MAX_BYTES = 60_000_000  # --dump-outputs: all arrays together (64 MB less room for the .npy headers)
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 FP32_PEAK_TFLOPS = 157.3  # MI355X_MICROARCH.md: FP32 vector (non-matrix) peak
 FP64_PEAK_TFLOPS = 78.6  # MI355X spec sheet: FP64 vector peak (the guide lists no FP64 figure)
@@ -304,6 +317,24 @@ def timed_rollout(make_env, env_id, n, steps, warmup, preroll, dev, rank, world,
     return env, elapsed, kernel_ms, G, [r[0] / steps * 1e3 for r in runs]
 
 
+def dump_outputs(env, out_dir, rank):
+    """--dump-outputs: the arrays the last timed step handed its caller (StepResult: obs, reward,
+    done, truncated, terminal_obs; Ant at 16,384 envs: 3.9 MB in all) as float32 .npy.  At most
+    DUMP_MAX_BYTES in all: beyond that env count, the same fixed (seed 0) sorted sample of envs
+    in every array."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = f".rank{rank}" if rank else ""
+    arrays = {name: getattr(env, name).detach().cpu().numpy().astype(np.float32)
+              for name in ("obs", "reward", "done", "truncated", "terminal_obs") if getattr(env, name, None) is not None}
+    n = env.num_envs
+    row_bytes = sum(a.nbytes for a in arrays.values()) // max(n, 1)
+    keep = DUMP_MAX_BYTES // max(row_bytes, 1)
+    rows = np.sort(np.random.default_rng(0).choice(n, keep, replace=False)) if keep < n else None
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), a if rows is None else a[rows])
+
+
 def leg_summary(env, world, n, steps, elapsed, kernel_ms, flops):
     """value / roofline block of one workload (HBM line from the algorithmic bytes; FP32 line
     from the counted flops when profiles/flops_per_env_step.json has the robot; float64 handles:
@@ -343,18 +374,25 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=1000)
-    ap.add_argument("--windows", type=int, default=5,
-                    help="timed windows of --steps steps each; value and ms_per_step are the median window")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: five timed windows (the median reported), "
+                         "the extra legs, the CPU baseline and (N > 1) the all-gather timing")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's obs / reward / done / truncated / terminal_obs as DIR/<name>.npy")
+    ap.add_argument("--windows", type=int, default=None,
+                    help="timed windows of --steps steps each; value and ms_per_step are the median window "
+                         "(default: 1, or 5 with --full)")
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--preroll", type=int, default=200, help="untimed steps before the warm-up (episode aging)")
     ap.add_argument("--envs-per-gpu", type=int, default=ENVS_PER_GPU)
     ap.add_argument("--env", default=ENV_ID)
     ap.add_argument("--no-gather", action="store_true",
-                    help="N > 1: skip timing the RCCL obs|reward|done all-gather (timed separately, outside `value`)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="--full, N > 1: skip timing the RCCL obs|reward|done all-gather (timed separately, "
+                         "outside `value`)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU-oracle baseline")
     ap.add_argument("--no-graph", action="store_true", help="launch every step from the host (no HIP graph)")
     ap.add_argument("--legs", default=EXTRA_LEGS,
-                    help="extra workloads env:envs_per_gpu,... timed beside `value` ('none' = off)")
+                    help="--full: extra workloads env:envs_per_gpu,... timed beside `value` ('none' = off)")
     ap.add_argument("--second-env", default=None, help="(compat) 'none' disables the extra legs")
     ap.add_argument("--leg-steps", type=int, default=200)
     ap.add_argument("--dry-run-cpu", action="store_true", help="CI: N > 1 control flow on CPU/gloo, no physics")
@@ -364,8 +402,10 @@ def main():
                     help="the headline handle's physics precision (64, the default: float64, the reference's "
                          "btScalar; 32: the float32 fast mode)")
     args = ap.parse_args()
-    if args.second_env == "none":
+    if args.second_env == "none" or not args.full:
         args.legs = "none"
+    if args.windows is None:
+        args.windows = 5 if args.full else 1
 
     import torch
     import torch.distributed as dist
@@ -401,9 +441,11 @@ def main():
                                                            args.preroll, dev, rank, world, args.no_graph,
                                                            windows=args.windows)
     head = leg_summary(env, world, n, args.steps, elapsed, kernel_ms, flops)
+    if args.dump_outputs:
+        dump_outputs(env, args.dump_outputs, rank)
 
     gather_ms = None
-    if not args.no_gather and world > 1:
+    if args.full and not args.no_gather and world > 1:
         for _ in range(3):
             gather_step(env.obs, env.reward, env.done)
         _sync(dev)
@@ -468,7 +510,7 @@ def main():
             out["allgather_payload"] = "obs | reward | done, float32 [global_envs, obs_dim + 2]"
         if args.dry_run_cpu:
             out["dry_run"] = "cpu/gloo stand-in env: control-flow check only, value is not a measurement"
-        if world == 1 and not args.no_cpu_baseline and not args.dry_run_cpu:
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.dry_run_cpu:
             out["cpu_baseline"] = cpu_baseline()
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -18,7 +18,7 @@
     GATHER_EVERY steps.  The gathered flat batch must be bitwise equal to (a)'s whole-batch
     trajectory at every gathered step (auto-resets happen inside the window: asserted).  RCCL
     cannot put two ranks on one device, so the collective is gloo here; the RCCL branch of
-    gather_flat runs in the driver's multi-GPU bench (bench.py --gpus N).
+    gather_flat runs in the multi-GPU bench (bench.py --gpus N --full).
 
 Reference: /root/reference/pybulletgym/envs/__init__.py:59-64,80-84 (the env ids),
 scene_bases.py:47-51 (one scene per env: envs are independent, so sharding is exact).

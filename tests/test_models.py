@@ -8,12 +8,15 @@ import pytest
 import pybulletgym_amd  # noqa: F401
 from pybulletgym_amd import codegen, mjcf, robots
 
-REF_ASSETS = robots.reference_asset_dir()
+# the reference's robot descriptions (the MJCF files robots.SPECS names and the Atlas URDF), stored
+# unchanged under tests/golden/assets/ in the reference's envs/assets/ layout
+ASSETS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "assets")
+REF_ASSETS = os.path.join(ASSETS, "mjcf")
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_ASSETS), reason="reference assets only in the build container")
-def test_committed_tables_are_current():
-    tables = codegen.compile_all()
+def test_committed_tables_are_current(monkeypatch):
+    monkeypatch.setattr(robots, "reference_robot_dir", lambda: os.path.join(ASSETS, "robots"))
+    tables = codegen.compile_all(REF_ASSETS)
     with open(codegen.HEADER) as f:
         assert f.read() == codegen.emit_header(tables), "run python -m pybulletgym_amd.codegen"
     for key, t in tables.items():
@@ -104,7 +107,6 @@ def test_walker2d_topology_and_gains():
     assert [t["link_name"][l] for l in t["foot_link"]] == ["foot", "foot_left"]
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_ASSETS), reason="reference assets only in the build container")
 def test_importer_overrides_change_the_generated_tables():
     """A getDynamicsInfo / getJointInfo-shaped override (models/importer_overrides.json format)
     replaces the mjcf.py rules: mass, inertia diagonal, lateral friction, joint damping and

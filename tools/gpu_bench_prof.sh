@@ -10,9 +10,9 @@ OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 cd $R
 export TMPDIR=/tmp
-timeout -k 10 300 python bench.py "$@" > $OUT/bench.json 2> $OUT/bench.err
-# the bench command itself (same steps / warmup), without the CPU leg
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o run -- python bench.py --no-cpu-baseline "$@" > $OUT/trace.log 2>&1
+timeout -k 10 300 python bench.py --full "$@" > $OUT/bench.json 2> $OUT/bench.err
+# the bench command itself (same steps / warmup, every leg), without the CPU leg
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o run -- python bench.py --full --no-cpu-baseline "$@" > $OUT/trace.log 2>&1
 for W in ${PROF_ROBOTS:-ant humanoid hopper halfcheetah ant_f64 humanoid_f64 hopper_f64 halfcheetah_f64}; do
   case $W in
     ant) A="--env AntPyBulletEnv-v0 --envs-per-gpu 16384 --precision 32";;

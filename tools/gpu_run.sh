@@ -4,7 +4,7 @@
 #     tests[:PYTEST_K]  pytest -m gpu (optionally -k PYTEST_K) with the parity report
 #     full              the whole -m gpu suite (+ parity report, dumps)
 #     smoke             __graft_entry__.smoke()
-#     bench[:ARGS]      python bench.py ARGS (ARGS: comma-separated)
+#     bench[:ARGS]      python bench.py --full ARGS (ARGS: comma-separated; every leg and the CPU baseline)
 #     prof              tools/gpu_bench_prof.sh TAG_prof (bench + rocprof stats + PMC passes)
 #     stalls            tools/gpu_stalls.sh TAG_stalls
 # A step that faults, aborts or times out ends the call (no later GPU step runs).
@@ -33,7 +33,7 @@ for S in "$@"; do
       timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.txt 2>&1; rc=$?; tail -2 $OUT/smoke.txt;;
     bench)
       nb=$((nb + 1)); BF=$OUT/bench_${nb}_$(echo "$arg" | tr -c 'a-zA-Z0-9' '_' | cut -c1-40).json
-      timeout -k 10 400 python bench.py ${arg//,/ } > $BF 2>> $OUT/bench.err; rc=$?; tail -c 400 $BF;;
+      timeout -k 10 400 python bench.py --full ${arg//,/ } > $BF 2>> $OUT/bench.err; rc=$?; tail -c 400 $BF;;
     prof)
       bash tools/gpu_bench_prof.sh ${TAG}_prof --steps 1000 --warmup 50; rc=$?;;
     stalls)

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Reproduces the round-5 float64 quad miscompile's faulting ISA from git history:
+# Reproduces the round-5 float64 quad miscompile's faulting ISA from the stored round-5 source:
 # compiles the round-5 source (commit 4428492) of team_step_kernel<F64<Ant>,16> under the default machine
 # schedule and under the register-pressure trackers, then runs the partial-EXEC copy check on both.
 # Expected: the default build has the VGPR->AGPR split copies of a54/a55/a180/a181 in a divergent
@@ -9,7 +9,8 @@ set -euo pipefail
 REPO=$(cd "$(dirname "$0")/.." && pwd)
 W=${1:-/tmp/pbg_r05_repro}
 rm -rf "$W" && mkdir -p "$W"
-git -C "$REPO" archive 44284927f8c7b1aa8bfb3a2ce5060a444b8317e4 pybullet-gym_amd/csrc include | tar -x -C "$W"
+# tests/golden/r05_quad_source.tar.gz = git archive 44284927f8c7b1aa8bfb3a2ce5060a444b8317e4 pybullet-gym_amd/csrc include
+tar -xzf "$REPO/tests/golden/r05_quad_source.tar.gz" -C "$W"
 F="--offload-arch=gfx950 -O3 -std=c++17 -fno-slp-vectorize -DPBG_TEAM64_TU -DPBG_ROBOT=Ant --cuda-device-only -S"
 cd "$W/pybullet-gym_amd"
 /opt/rocm/bin/hipcc $F -o "$W/default.s" csrc/pbg_robot.hip 2> /dev/null &
