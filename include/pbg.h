@@ -243,6 +243,78 @@ int pbg_sample_actions(int action_dim, int n_envs, int n_steps, uint64_t seed, u
 
 const char* pbg_last_error(void);
 
+/* ---- The pretrained-policy closed loop (appended; nothing above changes) ----
+ * The reference's enjoy scripts (examples/roboschool-weights/enjoy_TF_*.py) load a three-layer ReLU
+ * MLP, SmallReactivePolicy (:21-31: relu(x w1 + b1) -> relu(. w2 + b2) -> . w3 + b3), and run
+ * env.step(pi.act(obs)) until the episode ends.  A pbg_policy is that MLP; one kernel launch
+ * evaluates all three layers for a batch of observations.
+ *
+ * Numeric contract (host and device give the same floats for every input): every output of a layer
+ * is a k-ascending fused-multiply-add chain started from the bias,
+ *   acc = b[j]; for k = 0..K-1: acc = fmaf(x[k], W[k][j], acc);
+ * the hidden layers then apply  acc < 0 ? 0 : acc  (a NaN passes through, as np.maximum does). */
+typedef struct pbg_policy pbg_policy;
+
+#define PBG_POLICY_MAX_DIM 256 /* obs_dim, h1, h2 */
+#define PBG_POLICY_MAX_ACT 64  /* act_dim */
+
+/* weights: HOST float32, the reference's layout (enjoy_TF_*.py:21-31): w1[obs_dim,h1] b1[h1]
+ * w2[h1,h2] b2[h2] w3[h2,act_dim] b3[act_dim], row-major; copied, the caller keeps its own.
+ * 1 <= obs_dim, h1, h2 <= 256 and 1 <= act_dim <= 64, nothing need be a multiple of anything.
+ * device >= 0: uploaded there.  device == -1: host-only policy (no HIP call at all).
+ * PBG_E_ARG (before any HIP call) for dims out of range, a NULL array or device < -1; PBG_E_HIP
+ * for a device that does not exist.  *out is NULL after every failure. */
+int pbg_policy_create(int device, int obs_dim, int h1, int h2, int act_dim, const float* w1, const float* b1,
+                      const float* w2, const float* b2, const float* w3, const float* b3, pbg_policy** out);
+void pbg_policy_destroy(pbg_policy* p);
+/* act[n, act_dim] = pi(obs[n, obs_dim]), device pointers on the policy's device, one launch, async
+ * on `stream`; rows past n are neither read nor written.  PBG_E_ARG on a host-only policy. */
+int pbg_policy_act(const pbg_policy* p, int n, const float* obs, float* act, void* stream);
+/* The same floats on the CPU (host pointers; any policy, host-only or not). */
+int pbg_policy_act_host(const pbg_policy* p, int n, const float* obs, float* act);
+
+/* Buffers of a closed-loop rollout, all caller-owned DEVICE memory of the handle's GPU, n = the
+ * handle's n_envs, T = n_steps.  Versioned by struct_size like pbg_create_opts_t: set it to
+ * sizeof(pbg_rollout_io_t) of the header the caller was built with; the library reads only the
+ * fields that size covers (fields appended after done_traj, the end of the first version, take zero),
+ * so a caller built with an older header keeps working.  PBG_E_ARG for a size below the first
+ * version's, above the library's, or not a multiple of 4. */
+typedef struct {
+  uint32_t struct_size;
+  int n_steps;            /* T >= 1 */
+  int autoreset;          /* as pbg_step_io_t.autoreset.  0: an env that has finished an episode
+                             (done_episodes > 0) keeps stepping but stops accumulating: the
+                             first-episode score of the enjoy scripts */
+  int reserved;           /* 0 */
+  float* obs;             /* [n, obs_dim] in: the current observation (of reset or of the last step);
+                             out: the observation after the last step */
+  float* act;             /* [n, act_dim] work: the last action */
+  float* rew;             /* [n] work: the last float32 reward (unused when rew_traj is given) */
+  double* rew64;          /* [n] work: the last float64 reward */
+  uint8_t* done;          /* [n] work: the last done flags (unused when done_traj is given) */
+  /* per-env episode accumulators: zeroed by the caller before the first call, continued by later ones.
+   * Per env-step: cur_return += reward64, cur_length += 1; if done: done_return += cur_return,
+   * done_length += cur_length, done_episodes += 1, cur_return = cur_length = 0 */
+  double* cur_return;     /* [n] return of the running episode */
+  int32_t* cur_length;    /* [n] its length */
+  double* done_return;    /* [n] summed returns of the finished episodes */
+  int32_t* done_length;   /* [n] their summed lengths */
+  int32_t* done_episodes; /* [n] how many finished */
+  /* nullable trajectories */
+  float* obs_traj;        /* [T, n, obs_dim] the observation each action was computed from */
+  float* act_traj;        /* [T, n, act_dim] */
+  float* rew_traj;        /* [T, n] float32 reward */
+  uint8_t* done_traj;     /* [T, n] */
+} pbg_rollout_io_t;
+
+/* T closed-loop steps: per step act = pi(obs), then the handle's step (pbg_step_ex) with `autoreset`,
+ * then the bookkeeping above.  Enqueues 2 T + 1 kernels on `stream` only (per step the actor, which
+ * also does the previous step's bookkeeping, and the step; one bookkeeping launch closes the call);
+ * never synchronises, allocates or touches the host, so it captures into a HIP graph as a plain
+ * chain.  PBG_E_ARG for a host-only policy, one on another device, or one whose obs_dim / act_dim
+ * differ from the handle's. */
+int pbg_rollout(pbg_handle* h, const pbg_policy* p, const pbg_rollout_io_t* io, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

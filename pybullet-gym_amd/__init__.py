@@ -20,6 +20,9 @@ def __getattr__(name):
     if name == "VecEnv":
         from .vec_env import VecEnv
         return VecEnv
+    if name == "MLPPolicy":
+        from .policy import MLPPolicy
+        return MLPPolicy
     if name in ("make", "register_with_gym"):
         from . import envs
         return getattr(envs, name)

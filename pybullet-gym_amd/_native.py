@@ -63,6 +63,22 @@ class SimParams(ctypes.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class RolloutIO(ctypes.Structure):
+    """pbg_rollout_io_t (pbg_rollout): versioned by struct_size; device pointers of caller-owned buffers."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("n_steps", ctypes.c_int), ("autoreset", ctypes.c_int),
+                ("reserved", ctypes.c_int), ("obs", ctypes.c_void_p), ("act", ctypes.c_void_p),
+                ("rew", ctypes.c_void_p), ("rew64", ctypes.c_void_p), ("done", ctypes.c_void_p),
+                ("cur_return", ctypes.c_void_p), ("cur_length", ctypes.c_void_p), ("done_return", ctypes.c_void_p),
+                ("done_length", ctypes.c_void_p), ("done_episodes", ctypes.c_void_p), ("obs_traj", ctypes.c_void_p),
+                ("act_traj", ctypes.c_void_p), ("rew_traj", ctypes.c_void_p), ("done_traj", ctypes.c_void_p)]
+
+    def __init__(self, **kw):
+        super().__init__(struct_size=ctypes.sizeof(RolloutIO), **kw)
+
+
+POLICY_MAX_DIM = 256  # PBG_POLICY_MAX_DIM: obs_dim, h1, h2
+POLICY_MAX_ACT = 64   # PBG_POLICY_MAX_ACT
+
 _lib = None
 
 
@@ -102,6 +118,16 @@ def lib():
         L.pbg_debug_poison.argtypes = [H, ctypes.c_uint32, P]
         L.pbg_debug_poison.restype = I
     L.pbg_last_error.restype = ctypes.c_char_p
+    if hasattr(L, "pbg_policy_create"):  # the tools also load diagnostic and older builds without the policy
+        FP = ctypes.POINTER(ctypes.c_float)
+        L.pbg_policy_create.argtypes = [I, I, I, I, I, FP, FP, FP, FP, FP, FP, ctypes.POINTER(H)]
+        L.pbg_policy_destroy.argtypes = [H]
+        L.pbg_policy_destroy.restype = None
+        L.pbg_policy_act.argtypes = [H, I, P, P, P]
+        L.pbg_policy_act_host.argtypes = [H, I, P, P]
+        L.pbg_rollout.argtypes = [H, H, ctypes.POINTER(RolloutIO), P]
+        for f in ("pbg_policy_create", "pbg_policy_act", "pbg_policy_act_host", "pbg_rollout"):
+            getattr(L, f).restype = I
     for f in ("pbg_info", "pbg_reset", "pbg_step", "pbg_step_ex", "pbg_get_state", "pbg_set_state",
               "pbg_pack_record_sizes", "pbg_pack", "pbg_create_debug", "pbg_sample_actions", "pbg_create_ex",
               "pbg_default_sim_params", "pbg_get_sim_params", "pbg_create_v2", "pbg_precision"):
@@ -114,7 +140,8 @@ EXPORTED = ("pbg_create", "pbg_create_debug", "pbg_create_ex", "pbg_create_v2", 
             "pbg_default_sim_params", "pbg_get_sim_params",
             "pbg_destroy", "pbg_info", "pbg_reset", "pbg_step", "pbg_step_ex",
             "pbg_get_state", "pbg_set_state", "pbg_pack_record_sizes", "pbg_pack", "pbg_sample_actions",
-            "pbg_debug_poison", "pbg_last_error")
+            "pbg_debug_poison", "pbg_last_error",
+            "pbg_policy_create", "pbg_policy_destroy", "pbg_policy_act", "pbg_policy_act_host", "pbg_rollout")
 
 
 def check(rc: int, what: str):

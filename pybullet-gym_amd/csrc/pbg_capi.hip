@@ -10,6 +10,7 @@
 
 #include "../../include/pbg.h"
 #include "models_gen.h"
+#include "pbg_internal.h"
 #include "pbg_launch.h"
 #include "pbg_records.h"
 #include "pbg_math.h"
@@ -121,17 +122,7 @@ const Ops* ops(int rid) {
   return (rid >= 0 && rid < 17) ? &table[rid] : nullptr;
 }
 
-struct DeviceGuard {
-  int prev = -1;
-  explicit DeviceGuard(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != dev) (void)hipSetDevice(dev);
-  }
-  ~DeviceGuard() {
-    int cur = -1;
-    if (hipGetDevice(&cur) == hipSuccess && prev >= 0 && cur != prev) (void)hipSetDevice(prev);
-  }
-};
+using pbg::DeviceGuard;  // pbg_internal.h
 
 int hip_check(int e, const char* what) {
   if (e == (int)hipSuccess) return PBG_OK;
@@ -162,6 +153,12 @@ struct pbg_handle {
   pbg_info_t info;
   pbg_sim_params_t params;
 };
+
+// pbg_internal.h: the policy translation unit's access to the error message and the handle
+namespace pbg {
+int capi_fail(int code, const char* msg) { return fail(code, "%s", msg); }
+int handle_device(const pbg_handle* h) { return h->device; }
+}  // namespace pbg
 
 extern "C" {
 

@@ -36,6 +36,23 @@ class StepResult:
     terminal_obs: torch.Tensor
 
 
+@dataclass
+class RolloutResult:
+    """What ``VecEnv.rollout`` leaves, per env (views of the env's own buffers): the running
+    episode's return and length, the summed returns / lengths of the episodes that finished, and
+    how many did; the trajectories when asked for."""
+    obs: torch.Tensor
+    cur_return: torch.Tensor     # [n] float64
+    cur_length: torch.Tensor     # [n] int32
+    done_return: torch.Tensor    # [n] float64
+    done_length: torch.Tensor    # [n] int32
+    done_episodes: torch.Tensor  # [n] int32
+    obs_traj: torch.Tensor = None   # [steps, n, obs_dim]
+    act_traj: torch.Tensor = None   # [steps, n, action_dim]
+    rew_traj: torch.Tensor = None   # [steps, n] float32
+    done_traj: torch.Tensor = None  # [steps, n] uint8
+
+
 class VecEnv:
     """``num_envs`` copies of ``env_id`` on one GPU.
 
@@ -98,6 +115,9 @@ class VecEnv:
         self.reward_terms = None
         self.contact_sig = None
         self._io = _native.StepIO()
+        self._ro_acc = None   # rollout(): accumulators, work buffers and per-(steps, trajectory) io, all lazy
+        self._ro_work = None
+        self._ro_io = {}
 
     @staticmethod
     def default_sim_params(env_id: str) -> dict:
@@ -176,6 +196,68 @@ class VecEnv:
                 self.step(a)
         torch.cuda.current_stream(dev).wait_stream(s)
         return g
+
+    # ---------------------------------------------------------------- closed loop
+    def rollout(self, policy, steps: int, trajectory: bool = False, fresh: bool = False) -> RolloutResult:
+        """``steps`` closed-loop env steps of every env, ``env.step(policy.act(obs))`` (the loop of the
+        reference's enjoy_TF_*.py scripts), entirely on the device: pbg_rollout, two kernel launches
+        per step plus one per call, no host work in between.  ``policy``: an ``MLPPolicy`` on this
+        env's device.  It starts from ``self.obs`` (the last ``reset`` / ``step`` / ``rollout``) and
+        leaves the last observation there.  The other step outputs are NOT refreshed: ``truncated``,
+        ``terminal_obs`` and ``reward64`` keep what the last ``step`` left, and with
+        ``trajectory=True`` so do ``reward`` and ``done`` (the step then writes them straight into
+        ``rew_traj`` / ``done_traj``, whose last row is the last step's); without trajectories
+        ``reward`` and ``done`` hold the last step's.
+
+        The per-env accumulators (``RolloutResult``) live on the env and continue from call to call
+        (two 8-step calls leave what one 16-step call leaves); ``fresh=True`` or
+        ``reset_rollout()`` zeroes them.  With ``autoreset=False`` an env that has finished an
+        episode stops accumulating, so ``done_return`` / ``done_length`` hold its first episode.
+        ``trajectory=True`` also records ``obs_traj`` (the observation each action was computed
+        from), ``act_traj``, ``rew_traj`` and ``done_traj``, ``[steps, n, ...]``.
+
+        All buffers are allocated once per ``(steps, trajectory)`` and reused, and the returned
+        tensors are views of them (``clone()`` what must survive the next call), so after one
+        eager call a rollout captures into a HIP graph like ``step``."""
+        steps = int(steps)
+        if steps < 1:
+            raise _native.PbgError(f"rollout: steps must be >= 1 (got {steps})")
+        n, info, kw = self.num_envs, self.info, dict(device=self.device)
+        if getattr(policy, "_p", None) is None or not hasattr(_native.lib(), "pbg_rollout"):
+            raise _native.PbgError("rollout: policy must be an open MLPPolicy (and the library built with pbg_rollout)")
+        if self._ro_acc is None:
+            self._ro_acc = dict(cur_return=torch.zeros(n, dtype=torch.float64, **kw),
+                                cur_length=torch.zeros(n, dtype=torch.int32, **kw),
+                                done_return=torch.zeros(n, dtype=torch.float64, **kw),
+                                done_length=torch.zeros(n, dtype=torch.int32, **kw),
+                                done_episodes=torch.zeros(n, dtype=torch.int32, **kw))
+            self._ro_work = dict(act=torch.zeros((n, info.action_dim), dtype=torch.float32, **kw),
+                                 rew64=torch.zeros(n, dtype=torch.float64, **kw))
+        if fresh:
+            self.reset_rollout()
+        key = (steps, bool(trajectory))
+        if key not in self._ro_io:
+            traj = {}
+            if trajectory:
+                traj = dict(obs_traj=torch.zeros((steps, n, info.obs_dim), dtype=torch.float32, **kw),
+                            act_traj=torch.zeros((steps, n, info.action_dim), dtype=torch.float32, **kw),
+                            rew_traj=torch.zeros((steps, n), dtype=torch.float32, **kw),
+                            done_traj=torch.zeros((steps, n), dtype=torch.uint8, **kw))
+            bufs = dict(obs=self.obs, rew=self.reward, done=self.done, **self._ro_work, **self._ro_acc, **traj)
+            io = _native.RolloutIO(n_steps=steps, **{k: v.data_ptr() for k, v in bufs.items()})
+            self._ro_io[key] = (io, traj)
+        io, traj = self._ro_io[key]
+        io.autoreset = 1 if self.autoreset else 0
+        _native.check(_native.lib().pbg_rollout(self._h, policy._p, ctypes.byref(io),
+                                                _stream(self.device)), "pbg_rollout")
+        return RolloutResult(obs=self.obs, **self._ro_acc, obs_traj=traj.get("obs_traj"),
+                             act_traj=traj.get("act_traj"), rew_traj=traj.get("rew_traj"),
+                             done_traj=traj.get("done_traj"))
+
+    def reset_rollout(self):
+        """Zero the rollout accumulators (stream-ordered, no allocation)."""
+        for t in (self._ro_acc or {}).values():
+            t.zero_()
 
     # ---------------------------------------------------------------- state records
     def get_state(self):

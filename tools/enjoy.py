@@ -1,0 +1,47 @@
+#!/usr/bin/env python3
+"""The reference's enjoy scripts (examples/roboschool-weights/enjoy_TF_*.py) on the device: load a
+SmallReactivePolicy's weights, run one episode per env through VecEnv.rollout and print the score.
+
+  python tools/enjoy.py AntPyBulletEnv-v0 --weights tests/golden/policy_ant.npz [--envs 64] [--precision 64]
+
+The reference prints "score=%0.2f in %i frames" per episode; this prints the batch's summary."""
+from __future__ import annotations
+
+import argparse
+import os
+import sys
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("env_id")
+    ap.add_argument("--weights", required=True, help="npz with weights_dense1_w ... weights_final_b")
+    ap.add_argument("--envs", type=int, default=64)
+    ap.add_argument("--precision", type=int, choices=(32, 64), default=64)
+    ap.add_argument("--seed", type=int, default=0)
+    args = ap.parse_args()
+
+    import torch
+    import pybulletgym_amd  # noqa: F401
+    from pybulletgym_amd.policy import MLPPolicy
+    from pybulletgym_amd.vec_env import VecEnv
+
+    env = VecEnv(args.env_id, args.envs, device="cuda:0", seed=args.seed, autoreset=False, precision=args.precision)
+    pi = MLPPolicy.from_npz(args.weights, device=env.device)
+    env.reset()
+    # one episode per env: the TimeLimit ends every episode by max_episode_steps
+    res = env.rollout(pi, env.info.max_episode_steps)
+    torch.cuda.synchronize()
+    assert int(res.done_episodes.min()) == 1 and int(res.done_episodes.max()) == 1
+    ret, length = res.done_return.cpu(), res.done_length.cpu().double()
+    print(f"{args.env_id} x{args.envs} (float{args.precision}): score mean {ret.mean():.2f} min {ret.min():.2f} "
+          f"max {ret.max():.2f} in {length.mean():.1f} frames (mean)")
+    pi.close()
+    env.close()
+
+
+if __name__ == "__main__":
+    main()
