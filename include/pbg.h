@@ -315,6 +315,75 @@ typedef struct {
  * differ from the handle's. */
 int pbg_rollout(pbg_handle* h, const pbg_policy* p, const pbg_rollout_io_t* io, void* stream);
 
+/* ---- Policy populations and evolution strategies (appended; nothing above changes) ----
+ * Evolution strategies with mirrored sampling (Salimans et al. 2017): a generation perturbs a centre
+ * theta into n_pairs mirrored pairs theta +- sigma eps_i, scores every member by closed-loop episodes,
+ * and moves theta along sum_i w_i eps_i.  The noise is counter-based (below), so it is regenerated where
+ * it is needed and never stored, and a shard that holds pairs pair0 .. pair0 + n_pairs of a larger
+ * population draws exactly the noise the whole population would: only one scalar per member (its
+ * fitness) has to cross between shards.
+ *
+ * Flat parameter layout.  theta is [D] float32, D = obs*h1 + h1 + h1*h2 + h2 + h2*act + act: the
+ * unpadded concatenation w1, b1, w2, b2, w3, b3, each row-major in pbg_policy_create's layout; the
+ * dimension limits are pbg_policy_create's.
+ *
+ * A pbg_population is P = 2 n_pairs members (one theta each) of one MLP shape in the memory of one
+ * device; members 2 i and 2 i + 1 are the mirrored pair i, whose global index is pair0 + i.
+ *
+ * Noise contract.  eps_i[4 b .. 4 b + 3] come from one Philox4x32-10 block, key = seed (low word k0,
+ * high word k1), counter = (b, pair0 + i, generation, 0xE5); its words x0..x3 give four normals by two
+ * Box-Muller pairs, (x0, x1) the first two and (x2, x3) the last two:
+ *   u1 = fmaf((float)(x0 >> 9), 2^-23, 2^-24)   exact, in (0, 1)
+ *   u2 = (float)(x1 >> 8) * 2^-24               exact, in [0, 1)
+ *   r  = sqrtf(-2 logf(u1));  normals (r cospif(2 u2), r sinpif(2 u2))
+ * The last block of a D that is no multiple of 4 drops its surplus normals.  The device computes this
+ * in float32 with the device library's logf / cospif / sinpif, in ONE function that noise, perturb and
+ * grad share: all three see the same bits.  The host counterpart computes in float64 and rounds once;
+ * host and device agree within 1e-5 absolute (|r| <= sqrt(48 ln 2) = 5.77; log <= 3 ulp, sinpi / cospi
+ * <= 4 ulp, correctly rounded sqrt and multiply: 5.77 (1.5 + 0.5 + 4 + 0.5) 2^-23 = 4.5e-6), not bitwise. */
+typedef struct pbg_population pbg_population;
+
+/* n_pairs >= 1 mirrored pairs on `device` (>= 0), members zeroed; pair0 >= 0: the global index of the
+ * first pair.  PBG_E_ARG (before any HIP call) for dims out of pbg_policy_create's ranges, n_pairs < 1,
+ * pair0 < 0 or device < 0; PBG_E_HIP for a device that does not exist.  *out is NULL after every failure. */
+int pbg_population_create(int device, int obs_dim, int h1, int h2, int act_dim, int n_pairs, int pair0,
+                          pbg_population** out);
+void pbg_population_destroy(pbg_population* p);
+/* eps_out: DEVICE [n_pairs, D] float32 = the noise of `generation`. */
+int pbg_population_noise(const pbg_population* p, uint64_t seed, uint32_t generation, float* eps_out, void* stream);
+/* The host counterpart (float64, rounded once; HOST eps_out [n_pairs, D]); needs no GPU. */
+int pbg_population_noise_host(int obs_dim, int h1, int h2, int act_dim, uint64_t seed, uint32_t generation, int pair0,
+                              int n_pairs, float* eps_out);
+/* member[2 i][d]     = (float)((double)theta[d] + (double)sigma * (double)eps_i[d])
+ * member[2 i + 1][d] = (float)((double)theta[d] - (double)sigma * (double)eps_i[d])
+ * with the device's eps (pbg_population_noise's bits); theta: DEVICE [D].  The product of two float32
+ * values is exact in float64, so each member is the correctly rounded theta +- sigma eps. */
+int pbg_population_perturb(pbg_population* p, const float* theta, float sigma, uint64_t seed, uint32_t generation,
+                           void* stream);
+/* member m = theta (DEVICE [D]); m = -1 sets every member (the centre's evaluation).  get: DEVICE [D] out. */
+int pbg_population_set_member(pbg_population* p, int m, const float* theta, void* stream);
+int pbg_population_get_member(const pbg_population* p, int m, float* theta_out, void* stream);
+/* act[n, act_dim] = pi_m(obs[n, obs_dim]): n must be a multiple of P (PBG_E_ARG otherwise); with
+ * G = n / P env e uses member e / G.  The numeric contract is pbg_policy_act's, per member: row e equals
+ * pbg_policy_act_host of a policy built from member e / G's weights, bit for bit.  One launch; rows past
+ * n are neither read nor written.  Any G is correct; a G that is no multiple of 16 leaves lanes of each
+ * member's last 16-env tile idle. */
+int pbg_population_act(const pbg_population* p, int n, const float* obs, float* act, void* stream);
+/* pbg_rollout with the population's actor: the same pbg_rollout_io_t, bookkeeping and 2 T + 1 launches,
+ * nothing touches the host (capturable as a plain chain).  PBG_E_ARG when the handle's n_envs is no
+ * multiple of P, for a population on another device, or for mismatched obs_dim / act_dim. */
+int pbg_rollout_population(pbg_handle* h, const pbg_population* p, const pbg_rollout_io_t* io, void* stream);
+/* fitness_out[m] (DEVICE [P] float64) = (sum over member m's G = n / P envs, env-ascending sequential
+ * float64 adds, of (done_return[e] + cur_return[e])) / G: the mean return per env over everything the
+ * rollout accumulators (pbg_rollout_io_t) hold.  n: a positive multiple of P. */
+int pbg_population_fitness(const pbg_population* p, int n, const double* cur_return, const double* done_return,
+                           double* fitness_out, void* stream);
+/* g_out[d] (DEVICE [D] float32) = (float)(sum over i = 0 .. n_pairs - 1 ascending, in float64, of
+ * (double)w[i] * (double)eps_i[d]): exact products, one float64 rounding per add, eps regenerated
+ * (pbg_population_noise's bits).  w: DEVICE [n_pairs] float32. */
+int pbg_population_grad(const pbg_population* p, const float* w, uint64_t seed, uint32_t generation, float* g_out,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,6 +23,12 @@ def __getattr__(name):
     if name == "MLPPolicy":
         from .policy import MLPPolicy
         return MLPPolicy
+    if name == "MLPPopulation":
+        from .policy import MLPPopulation
+        return MLPPopulation
+    if name == "EvolutionStrategy":
+        from .es import EvolutionStrategy
+        return EvolutionStrategy
     if name in ("make", "register_with_gym"):
         from . import envs
         return getattr(envs, name)

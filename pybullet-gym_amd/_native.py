@@ -128,6 +128,23 @@ def lib():
         L.pbg_rollout.argtypes = [H, H, ctypes.POINTER(RolloutIO), P]
         for f in ("pbg_policy_create", "pbg_policy_act", "pbg_policy_act_host", "pbg_rollout"):
             getattr(L, f).restype = I
+    if hasattr(L, "pbg_population_create"):  # policy populations / evolution strategies
+        U64, U32, F = ctypes.c_uint64, ctypes.c_uint32, ctypes.c_float
+        L.pbg_population_create.argtypes = [I, I, I, I, I, I, I, ctypes.POINTER(H)]
+        L.pbg_population_destroy.argtypes = [H]
+        L.pbg_population_destroy.restype = None
+        L.pbg_population_noise.argtypes = [H, U64, U32, P, P]
+        L.pbg_population_noise_host.argtypes = [I, I, I, I, U64, U32, I, I, P]
+        L.pbg_population_perturb.argtypes = [H, P, F, U64, U32, P]
+        L.pbg_population_set_member.argtypes = [H, I, P, P]
+        L.pbg_population_get_member.argtypes = [H, I, P, P]
+        L.pbg_population_act.argtypes = [H, I, P, P, P]
+        L.pbg_rollout_population.argtypes = [H, H, ctypes.POINTER(RolloutIO), P]
+        L.pbg_population_fitness.argtypes = [H, I, P, P, P, P]
+        L.pbg_population_grad.argtypes = [H, P, U64, U32, P, P]
+        for f in POPULATION_EXPORTED:
+            if f != "pbg_population_destroy":
+                getattr(L, f).restype = I
     for f in ("pbg_info", "pbg_reset", "pbg_step", "pbg_step_ex", "pbg_get_state", "pbg_set_state",
               "pbg_pack_record_sizes", "pbg_pack", "pbg_create_debug", "pbg_sample_actions", "pbg_create_ex",
               "pbg_default_sim_params", "pbg_get_sim_params", "pbg_create_v2", "pbg_precision"):
@@ -141,7 +158,17 @@ EXPORTED = ("pbg_create", "pbg_create_debug", "pbg_create_ex", "pbg_create_v2", 
             "pbg_destroy", "pbg_info", "pbg_reset", "pbg_step", "pbg_step_ex",
             "pbg_get_state", "pbg_set_state", "pbg_pack_record_sizes", "pbg_pack", "pbg_sample_actions",
             "pbg_debug_poison", "pbg_last_error",
-            "pbg_policy_create", "pbg_policy_destroy", "pbg_policy_act", "pbg_policy_act_host", "pbg_rollout")
+            "pbg_policy_create", "pbg_policy_destroy", "pbg_policy_act", "pbg_policy_act_host", "pbg_rollout",
+            "pbg_population_create", "pbg_population_destroy", "pbg_population_noise",
+            "pbg_population_noise_host", "pbg_population_perturb", "pbg_population_set_member",
+            "pbg_population_get_member", "pbg_population_act", "pbg_rollout_population",
+            "pbg_population_fitness", "pbg_population_grad")
+
+
+POPULATION_EXPORTED = ("pbg_population_create", "pbg_population_destroy", "pbg_population_noise",
+                       "pbg_population_noise_host", "pbg_population_perturb", "pbg_population_set_member",
+                       "pbg_population_get_member", "pbg_population_act", "pbg_rollout_population",
+                       "pbg_population_fitness", "pbg_population_grad")
 
 
 def check(rc: int, what: str):

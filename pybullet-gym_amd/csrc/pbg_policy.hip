@@ -3,16 +3,8 @@
 // (examples/roboschool-weights/enjoy_TF_*.py:25-31) once per env per step on the host; here one
 // launch evaluates all three layers for every env, the hidden activations never leave LDS.
 //
-// Numeric contract (pbg.h): out[j] = fmaf-chain over k ascending, started from b[j]; ReLU as
-// `v < 0 ? 0 : v`.  Host and device spell the same chain with __builtin_fmaf, one fma per (k, j, env),
-// so they agree bit for bit; nothing is split over k and nothing is left for the compiler to contract.
-//
-// Geometry (DESIGN.md "Policy kernel"): a workgroup of 256 lanes owns a tile of 16 envs.  Inside a
-// layer a lane owns one output column j and EL of the tile's envs: its weight reads W[k][j] are
-// coalesced over the lanes (the reference's row-major [K, H] layout as is, read through L2) and the
-// activations x[k][e0 .. e0 + EL) are wave-uniform float4 LDS broadcasts.  A layer of H <= 64 columns
-// splits the 16 envs over the four waves (EL = 4), H <= 128 over two wave pairs (EL = 8), wider
-// layers give every lane all 16: no wave idles through a narrow layer.
+// The MLP tile, its numeric contract and geometry, the bookkeeping and the loop's declaration are in
+// pbg_policy_dev.h, shared with the population actor (pbg_population.hip).
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdio.h>
@@ -21,103 +13,15 @@
 
 #include <new>
 
-#include "pbg_internal.h"
+#include "pbg_policy_dev.h"
 
 namespace {
 
-constexpr int PT = 16;                   // envs per workgroup (tile)
-constexpr int PB = 256;                  // lanes per workgroup
-constexpr int PD = PBG_POLICY_MAX_DIM;   // widest layer
-
-static_assert(PB == PD, "a lane per column of the widest layer");
-
-// bookkeeping of one finished env step (pbg.h pbg_rollout_io_t); rew64 NULL = nothing to do
-struct Book {
-  const double* rew64;
-  const uint8_t* done;
-  double* cur_return;
-  int32_t* cur_length;
-  double* done_return;
-  int32_t* done_length;
-  int32_t* done_episodes;
-  int autoreset;
-};
-
-__device__ __forceinline__ void book_env(const Book& b, int e) {
-  const int ep = b.done_episodes[e];
-  if (!b.autoreset && ep > 0) return;  // first-episode semantics: a finished env stops accumulating
-  double cr = b.cur_return[e] + b.rew64[e];
-  int cl = b.cur_length[e] + 1;
-  if (b.done[e]) {
-    b.done_return[e] += cr;
-    b.done_length[e] += cl;
-    b.done_episodes[e] = ep + 1;
-    cr = 0.0;
-    cl = 0;
-  }
-  b.cur_return[e] = cr;
-  b.cur_length[e] = cl;
-}
+using namespace pbg::policy;
 
 __global__ __launch_bounds__(256) void book_kernel(Book b, int n) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e < n) book_env(b, e);
-}
-
-struct Weights {
-  const float *w1, *b1, *w2, *b2, *w3, *b3;
-  int obs_dim, h1, h2, act_dim;
-};
-
-// One layer for this lane's column j and envs e0 .. e0 + EL of the tile: xT [K][PT] -> yT [H][PT], both LDS.
-template <int EL>
-__device__ __forceinline__ void layer_cols(const float* __restrict__ W, const float* __restrict__ bias, int K, int H,
-                                           int j, int e0, bool relu, const float* xT, float* yT) {
-  float acc[EL];
-  const float bj = bias[j];
-#pragma unroll
-  for (int e = 0; e < EL; e++) acc[e] = bj;
-  const float* wp = W + j;
-  const float* xp = xT + e0;
-  // (an explicit register double-buffer of the weight rows measured the same as this loop: the kernel
-  // is bound by the LDS broadcasts and the fma issue, not by the weights' L2 latency)
-#pragma unroll 4
-  for (int k = 0; k < K; k++) {
-    const float w = wp[(size_t)k * H];
-#pragma unroll
-    for (int q = 0; q < EL / 4; q++) {
-      const float4 x = *reinterpret_cast<const float4*>(xp + k * PT + 4 * q);
-      acc[4 * q + 0] = __builtin_fmaf(x.x, w, acc[4 * q + 0]);
-      acc[4 * q + 1] = __builtin_fmaf(x.y, w, acc[4 * q + 1]);
-      acc[4 * q + 2] = __builtin_fmaf(x.z, w, acc[4 * q + 2]);
-      acc[4 * q + 3] = __builtin_fmaf(x.w, w, acc[4 * q + 3]);
-    }
-  }
-#pragma unroll
-  for (int q = 0; q < EL / 4; q++) {
-    float4 y;
-    y.x = acc[4 * q + 0]; y.y = acc[4 * q + 1]; y.z = acc[4 * q + 2]; y.w = acc[4 * q + 3];
-    if (relu) {
-      y.x = y.x < 0.f ? 0.f : y.x; y.y = y.y < 0.f ? 0.f : y.y;
-      y.z = y.z < 0.f ? 0.f : y.z; y.w = y.w < 0.f ? 0.f : y.w;
-    }
-    *reinterpret_cast<float4*>(yT + j * PT + e0 + 4 * q) = y;
-  }
-}
-
-// A layer over the whole workgroup: H <= 64 columns -> 4 env groups of 4, <= 128 -> 2 of 8, else 1 of 16.
-__device__ __forceinline__ void layer(const float* __restrict__ W, const float* __restrict__ bias, int K, int H, bool relu,
-                                      const float* xT, float* yT) {
-  const int tid = threadIdx.x;
-  if (H <= 64) {
-    const int j = tid & 63, g = tid >> 6;
-    if (j < H) layer_cols<4>(W, bias, K, H, j, 4 * g, relu, xT, yT);
-  } else if (H <= 128) {
-    const int j = tid & 127, g = tid >> 7;
-    if (j < H) layer_cols<8>(W, bias, K, H, j, 8 * g, relu, xT, yT);
-  } else {
-    if (tid < H) layer_cols<16>(W, bias, K, H, tid, 0, relu, xT, yT);
-  }
 }
 
 // act[n, act_dim] = pi(obs[n, obs_dim]); optional copies of both into the rollout's trajectories; the
@@ -127,39 +31,8 @@ __global__ __launch_bounds__(PB) void policy_act_kernel(Weights P, int n, const 
                                                         float* __restrict__ act_traj, Book bk) {
   __shared__ __attribute__((aligned(16))) float bufA[PD * PT];
   __shared__ __attribute__((aligned(16))) float bufB[PD * PT];
-  const int tid = threadIdx.x;
   const int env0 = blockIdx.x * PT;
-  const int rows = min(PT, n - env0);  // >= 1: the grid is ceil(n / PT)
-
-  if (bk.rew64 && tid < rows) book_env(bk, env0 + tid);
-
-  // the tile's observations (rows * obs_dim contiguous floats) -> bufA [obs_dim][PT], zero past n
-  const int K0 = P.obs_dim;
-  for (int i = tid; i < PT * K0; i += PB) {
-    const int e = i / K0, k = i - e * K0;
-    float v = 0.f;
-    if (e < rows) {
-      const size_t at = (size_t)env0 * K0 + i;
-      v = obs[at];
-      if (obs_traj) obs_traj[at] = v;
-    }
-    bufA[k * PT + e] = v;
-  }
-  __syncthreads();
-  layer(P.w1, P.b1, K0, P.h1, true, bufA, bufB);
-  __syncthreads();
-  layer(P.w2, P.b2, P.h1, P.h2, true, bufB, bufA);
-  __syncthreads();
-  layer(P.w3, P.b3, P.h2, P.act_dim, false, bufA, bufB);
-  __syncthreads();
-  const int NA = P.act_dim;
-  for (int i = tid; i < rows * NA; i += PB) {
-    const int e = i / NA, j = i - e * NA;
-    const float v = bufB[j * PT + e];
-    const size_t at = (size_t)env0 * NA + i;
-    act[at] = v;
-    if (act_traj) act_traj[at] = v;
-  }
+  act_tile(P, env0, min(PT, n - env0), obs, act, obs_traj, act_traj, bk, bufA, bufB);  // rows >= 1: the grid is ceil(n / PT)
 }
 
 }  // namespace
@@ -185,6 +58,11 @@ int launch_act(const pbg_policy* p, int n, const float* obs, float* act, float* 
   hipLaunchKernelGGL(policy_act_kernel, dim3(grid), dim3(PB), 0, stream, weights_at(p, p->dev), n, obs, act, obs_traj,
                      act_traj, bk);
   return (int)hipGetLastError();
+}
+
+int act_of_policy(const void* actor, int n, const float* obs, float* act, float* obs_traj, float* act_traj,
+                  const Book& bk, hipStream_t stream) {
+  return launch_act(static_cast<const pbg_policy*>(actor), n, obs, act, obs_traj, act_traj, bk, stream);
 }
 
 int hip_fail(int e, const char* what) {
@@ -302,33 +180,52 @@ int pbg_policy_act(const pbg_policy* p, int n, const float* obs, float* act, voi
 
 int pbg_rollout(pbg_handle* h, const pbg_policy* p, const pbg_rollout_io_t* uio, void* stream) {
   if (!h || !p || !uio) return pbg::capi_fail(PBG_E_ARG, "pbg_rollout: NULL handle, policy or io");
+  if (p->device < 0 || !p->dev) return pbg::capi_fail(PBG_E_ARG, "pbg_rollout: host-only policy");
+  return rollout_loop("pbg_rollout", h, uio, stream, p->device, p->obs_dim, p->act_dim, 1, act_of_policy, p);
+}
+
+}  // extern "C"
+
+int pbg::policy::rollout_loop(const char* who, pbg_handle* h, const pbg_rollout_io_t* uio, void* stream, int actor_device,
+                              int obs_dim, int act_dim, int group, ActLaunch launch, const void* actor) {
+  char msg[200];
   // versioned like pbg_create_opts_t: the first version ends with done_traj; read only what the caller's
   // struct holds, fields appended later take zero (their default) for an older caller
   constexpr uint32_t v1_size = (uint32_t)(offsetof(pbg_rollout_io_t, done_traj) + sizeof(uint8_t*));
   if (uio->struct_size < v1_size || uio->struct_size > (uint32_t)sizeof(pbg_rollout_io_t) || uio->struct_size % 4u != 0u) {
-    char msg[96];
-    snprintf(msg, sizeof(msg), "pbg_rollout: io->struct_size %u is not a pbg_rollout_io_t size", uio->struct_size);
+    snprintf(msg, sizeof(msg), "%s: io->struct_size %u is not a pbg_rollout_io_t size", who, uio->struct_size);
     return pbg::capi_fail(PBG_E_ARG, msg);
   }
   pbg_rollout_io_t io_copy;
   memset(&io_copy, 0, sizeof(io_copy));
   memcpy(&io_copy, uio, uio->struct_size);
   const pbg_rollout_io_t* io = &io_copy;
-  if (p->device < 0 || !p->dev) return pbg::capi_fail(PBG_E_ARG, "pbg_rollout: host-only policy");
   const int dev = pbg::handle_device(h);
-  if (p->device != dev) return pbg::capi_fail(PBG_E_ARG, "pbg_rollout: the policy lives on another device than the handle");
-  pbg_info_t info;
-  if (pbg_info(h, &info)) return PBG_E_ARG;
-  if (p->obs_dim != info.obs_dim || p->act_dim != info.action_dim) {
-    char msg[160];
-    snprintf(msg, sizeof(msg), "pbg_rollout: policy maps %d -> %d, the env's obs_dim / action_dim are %d / %d", p->obs_dim,
-             p->act_dim, info.obs_dim, info.action_dim);
+  if (actor_device != dev) {
+    snprintf(msg, sizeof(msg), "%s: the policy lives on another device than the handle", who);
     return pbg::capi_fail(PBG_E_ARG, msg);
   }
-  if (io->n_steps < 1) return pbg::capi_fail(PBG_E_ARG, "pbg_rollout: n_steps must be >= 1");
+  pbg_info_t info;
+  if (pbg_info(h, &info)) return PBG_E_ARG;
+  if (obs_dim != info.obs_dim || act_dim != info.action_dim) {
+    snprintf(msg, sizeof(msg), "%s: policy maps %d -> %d, the env's obs_dim / action_dim are %d / %d", who, obs_dim,
+             act_dim, info.obs_dim, info.action_dim);
+    return pbg::capi_fail(PBG_E_ARG, msg);
+  }
+  if (group > 1 && info.n_envs % group != 0) {
+    snprintf(msg, sizeof(msg), "%s: the handle's %d envs are not a multiple of the population's %d members", who,
+             info.n_envs, group);
+    return pbg::capi_fail(PBG_E_ARG, msg);
+  }
+  if (io->n_steps < 1) {
+    snprintf(msg, sizeof(msg), "%s: n_steps must be >= 1", who);
+    return pbg::capi_fail(PBG_E_ARG, msg);
+  }
   if (!io->obs || !io->act || !io->rew64 || (!io->rew && !io->rew_traj) || (!io->done && !io->done_traj) ||
-      !io->cur_return || !io->cur_length || !io->done_return || !io->done_length || !io->done_episodes)
-    return pbg::capi_fail(PBG_E_ARG, "pbg_rollout: NULL required buffer");
+      !io->cur_return || !io->cur_length || !io->done_return || !io->done_length || !io->done_episodes) {
+    snprintf(msg, sizeof(msg), "%s: NULL required buffer", who);
+    return pbg::capi_fail(PBG_E_ARG, msg);
+  }
   DeviceGuard dg(dev);
   hipStream_t s = (hipStream_t)stream;
   const int n = info.n_envs;
@@ -343,9 +240,9 @@ int pbg_rollout(pbg_handle* h, const pbg_policy* p, const pbg_rollout_io_t* uio,
   st.autoreset = io->autoreset ? 1 : 0;
   for (int t = 0; t < io->n_steps; t++) {
     // actor: the bookkeeping of step t - 1, then act = pi(obs)
-    int e = launch_act(p, n, io->obs, io->act, io->obs_traj ? io->obs_traj + (size_t)t * no : nullptr,
-                       io->act_traj ? io->act_traj + (size_t)t * na : nullptr, bk, s);
-    if (e) return hip_fail(e, "policy_act_kernel launch");
+    int e = launch(actor, n, io->obs, io->act, io->obs_traj ? io->obs_traj + (size_t)t * no : nullptr,
+                   io->act_traj ? io->act_traj + (size_t)t * na : nullptr, bk, s);
+    if (e) return hip_fail(e, "actor kernel launch");
     // the step writes reward and done straight into the trajectory rows when there are any
     st.rew = io->rew_traj ? io->rew_traj + (size_t)t * n : io->rew;
     st.done = io->done_traj ? io->done_traj + (size_t)t * n : io->done;
@@ -358,5 +255,3 @@ int pbg_rollout(pbg_handle* h, const pbg_policy* p, const pbg_rollout_io_t* uio,
   const int e = (int)hipGetLastError();
   return e ? hip_fail(e, "rollout bookkeeping launch") : PBG_OK;
 }
-
-}  // extern "C"

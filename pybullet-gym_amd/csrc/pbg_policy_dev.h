@@ -1,0 +1,169 @@
+// pbg_policy_dev.h -- what the two actor translation units share: the MLP tile (pbg_policy.hip's
+// policy_act_kernel evaluates it with one weight set for every workgroup, pbg_population.hip's
+// population_act_kernel with the workgroup's own member's), the rollout bookkeeping and the rollout
+// loop itself (pbg_rollout and pbg_rollout_population enqueue the same 2 T + 1 launches and differ in
+// the actor launch only).
+//
+// Numeric contract (pbg.h): out[j] = fmaf-chain over k ascending, started from b[j]; ReLU as
+// `v < 0 ? 0 : v`.  One fma per (k, j, env), nothing split over k, nothing left for the compiler to
+// contract.
+//
+// Geometry (DESIGN.md "Policy kernel"): a workgroup of 256 lanes owns a tile of 16 envs.  Inside a
+// layer a lane owns one output column j and EL of the tile's envs: its weight reads W[k][j] are
+// coalesced over the lanes (the reference's row-major [K, H] layout as is) and the activations
+// x[k][e0 .. e0 + EL) are wave-uniform float4 LDS broadcasts.  A layer of H <= 64 columns splits the
+// 16 envs over the four waves (EL = 4), H <= 128 over two wave pairs (EL = 8), wider layers give
+// every lane all 16: no wave idles through a narrow layer.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+#include "pbg_internal.h"
+
+namespace pbg {
+namespace policy {
+
+constexpr int PT = 16;                   // envs per workgroup (tile)
+constexpr int PB = 256;                  // lanes per workgroup
+constexpr int PD = PBG_POLICY_MAX_DIM;   // widest layer
+
+static_assert(PB == PD, "a lane per column of the widest layer");
+
+// bookkeeping of one finished env step (pbg.h pbg_rollout_io_t); rew64 NULL = nothing to do
+struct Book {
+  const double* rew64;
+  const uint8_t* done;
+  double* cur_return;
+  int32_t* cur_length;
+  double* done_return;
+  int32_t* done_length;
+  int32_t* done_episodes;
+  int autoreset;
+};
+
+__device__ __forceinline__ void book_env(const Book& b, int e) {
+  const int ep = b.done_episodes[e];
+  if (!b.autoreset && ep > 0) return;  // first-episode semantics: a finished env stops accumulating
+  double cr = b.cur_return[e] + b.rew64[e];
+  int cl = b.cur_length[e] + 1;
+  if (b.done[e]) {
+    b.done_return[e] += cr;
+    b.done_length[e] += cl;
+    b.done_episodes[e] = ep + 1;
+    cr = 0.0;
+    cl = 0;
+  }
+  b.cur_return[e] = cr;
+  b.cur_length[e] = cl;
+}
+
+struct Weights {
+  const float *w1, *b1, *w2, *b2, *w3, *b3;
+  int obs_dim, h1, h2, act_dim;
+};
+
+// One layer for this lane's column j and envs e0 .. e0 + EL of the tile: xT [K][PT] -> yT [H][PT], both LDS.
+template <int EL>
+__device__ __forceinline__ void layer_cols(const float* __restrict__ W, const float* __restrict__ bias, int K, int H,
+                                           int j, int e0, bool relu, const float* xT, float* yT) {
+  float acc[EL];
+  const float bj = bias[j];
+#pragma unroll
+  for (int e = 0; e < EL; e++) acc[e] = bj;
+  const float* wp = W + j;
+  const float* xp = xT + e0;
+  // (an explicit register double-buffer of the weight rows measured the same as this loop: the kernel
+  // is bound by the LDS broadcasts and the fma issue, not by the weights' L2 latency)
+#pragma unroll 4
+  for (int k = 0; k < K; k++) {
+    const float w = wp[(size_t)k * H];
+#pragma unroll
+    for (int q = 0; q < EL / 4; q++) {
+      const float4 x = *reinterpret_cast<const float4*>(xp + k * PT + 4 * q);
+      acc[4 * q + 0] = __builtin_fmaf(x.x, w, acc[4 * q + 0]);
+      acc[4 * q + 1] = __builtin_fmaf(x.y, w, acc[4 * q + 1]);
+      acc[4 * q + 2] = __builtin_fmaf(x.z, w, acc[4 * q + 2]);
+      acc[4 * q + 3] = __builtin_fmaf(x.w, w, acc[4 * q + 3]);
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < EL / 4; q++) {
+    float4 y;
+    y.x = acc[4 * q + 0]; y.y = acc[4 * q + 1]; y.z = acc[4 * q + 2]; y.w = acc[4 * q + 3];
+    if (relu) {
+      y.x = y.x < 0.f ? 0.f : y.x; y.y = y.y < 0.f ? 0.f : y.y;
+      y.z = y.z < 0.f ? 0.f : y.z; y.w = y.w < 0.f ? 0.f : y.w;
+    }
+    *reinterpret_cast<float4*>(yT + j * PT + e0 + 4 * q) = y;
+  }
+}
+
+// A layer over the whole workgroup: H <= 64 columns -> 4 env groups of 4, <= 128 -> 2 of 8, else 1 of 16.
+__device__ __forceinline__ void layer(const float* __restrict__ W, const float* __restrict__ bias, int K, int H, bool relu,
+                                      const float* xT, float* yT) {
+  const int tid = threadIdx.x;
+  if (H <= 64) {
+    const int j = tid & 63, g = tid >> 6;
+    if (j < H) layer_cols<4>(W, bias, K, H, j, 4 * g, relu, xT, yT);
+  } else if (H <= 128) {
+    const int j = tid & 127, g = tid >> 7;
+    if (j < H) layer_cols<8>(W, bias, K, H, j, 8 * g, relu, xT, yT);
+  } else {
+    if (tid < H) layer_cols<16>(W, bias, K, H, tid, 0, relu, xT, yT);
+  }
+}
+
+// One workgroup's tile: envs env0 .. env0 + rows (1 <= rows <= PT) with the weights P.
+// act[e] = pi(obs[e]); optional copies of both into the rollout's trajectories; the bookkeeping of the
+// previous env step (bk.rew64 != NULL) for the tile's envs comes first.  Rows past `rows` are zero-filled
+// in LDS and neither read from nor written to memory.  bufA / bufB: the workgroup's two [PD][PT] LDS planes.
+__device__ __forceinline__ void act_tile(const Weights P, int env0, int rows, const float* __restrict__ obs,
+                                         float* __restrict__ act, float* __restrict__ obs_traj,
+                                         float* __restrict__ act_traj, const Book bk, float* bufA, float* bufB) {
+  const int tid = threadIdx.x;
+  if (bk.rew64 && tid < rows) book_env(bk, env0 + tid);
+
+  // the tile's observations (rows * obs_dim contiguous floats) -> bufA [obs_dim][PT], zero past `rows`
+  const int K0 = P.obs_dim;
+  for (int i = tid; i < PT * K0; i += PB) {
+    const int e = i / K0, k = i - e * K0;
+    float v = 0.f;
+    if (e < rows) {
+      const size_t at = (size_t)env0 * K0 + i;
+      v = obs[at];
+      if (obs_traj) obs_traj[at] = v;
+    }
+    bufA[k * PT + e] = v;
+  }
+  __syncthreads();
+  layer(P.w1, P.b1, K0, P.h1, true, bufA, bufB);
+  __syncthreads();
+  layer(P.w2, P.b2, P.h1, P.h2, true, bufB, bufA);
+  __syncthreads();
+  layer(P.w3, P.b3, P.h2, P.act_dim, false, bufA, bufB);
+  __syncthreads();
+  const int NA = P.act_dim;
+  for (int i = tid; i < rows * NA; i += PB) {
+    const int e = i / NA, j = i - e * NA;
+    const float v = bufB[j * PT + e];
+    const size_t at = (size_t)env0 * NA + i;
+    act[at] = v;
+    if (act_traj) act_traj[at] = v;
+  }
+}
+
+// The actor launch of a rollout: act = pi(obs) for the handle's n envs after the bookkeeping `bk`,
+// enqueued on `stream`; returns the hipError_t of the launch.
+typedef int (*ActLaunch)(const void* actor, int n, const float* obs, float* act, float* obs_traj, float* act_traj,
+                         const Book& bk, hipStream_t stream);
+
+// The closed loop of pbg_rollout / pbg_rollout_population (pbg_policy.hip): validates `io` against the
+// handle and the actor's device and dims, then enqueues per step the actor and the handle's step, and
+// one closing bookkeeping launch.  `who` names the entry point in error messages; `group` > 1: the
+// handle's n_envs must be a multiple of it (the population's member count).
+int rollout_loop(const char* who, pbg_handle* h, const pbg_rollout_io_t* io, void* stream, int actor_device,
+                 int obs_dim, int act_dim, int group, ActLaunch launch, const void* actor);
+
+}  // namespace policy
+}  // namespace pbg

@@ -1,0 +1,405 @@
+// pbg_population.hip -- policy populations and the evolution-strategy kernels (include/pbg.h
+// pbg_population_*, pbg_rollout_population).  A population is P = 2 n_pairs weight sets of one MLP shape
+// in device memory, member m's flat parameter vector at members + m D (pbg.h "Flat parameter layout").
+//
+// The actor (population_act_kernel) is pbg_policy.hip's tile (pbg_policy_dev.h act_tile: 256 lanes, 16
+// envs, the same k-ascending fma chain) with the grid over (member, tile of that member's G envs): a tile
+// never straddles two members and the workgroup's weight pointers start at its member.  The once-per-
+// generation kernels (noise, perturb, grad, fitness, member copies) are written for the stated summation
+// order, not for speed.
+//
+// Same-bits rule: es_normals4 is the only place the device computes the noise; noise, perturb and grad
+// call it with the same counter and so see the same floats.  Every multiply-add in this file is either a
+// spelled-out fma or cannot be contracted (a product that feeds no add).
+#include <hip/hip_runtime.h>
+#include <limits.h>
+#include <math.h>
+#include <stddef.h>
+#include <stdio.h>
+#include <string.h>
+
+#include <new>
+
+#include "pbg_math.h"
+#include "pbg_policy_dev.h"
+
+struct pbg_population {
+  int device;
+  int obs_dim, h1, h2, act_dim;
+  int n_pairs, pair0;
+  int D;           // parameters per member
+  float* members;  // device [2 n_pairs, D]
+};
+
+namespace {
+
+using namespace pbg::policy;
+using pbg::DeviceGuard;
+
+constexpr uint32_t ES_TAG = 0xE5u;  // fourth counter word of the noise stream
+
+struct Dims {
+  int obs_dim, h1, h2, act_dim;
+};
+
+__host__ __device__ inline int param_count(const Dims& d) {
+  return d.obs_dim * d.h1 + d.h1 + d.h1 * d.h2 + d.h2 + d.h2 * d.act_dim + d.act_dim;
+}
+
+// ---------------------------------------------------------------- noise
+// Two normals from two Philox words (pbg.h "Noise contract").  u1 = (a >> 9 + 1/2) 2^-23 lies in (0, 1)
+// and is exact; -2 logf, 2 u2 and the two r * trig products feed no add.
+__device__ __forceinline__ void es_box_muller(uint32_t a, uint32_t b, float& n0, float& n1) {
+  const float u1 = __builtin_fmaf((float)(a >> 9), 0x1p-23f, 0x1p-24f);
+  const float u2 = (float)(b >> 8) * 0x1p-24f;
+  const float r = sqrtf(-2.0f * logf(u1));
+  const float t = 2.0f * u2;
+  n0 = r * cospif(t);
+  n1 = r * sinpif(t);
+}
+
+// The four normals of parameters 4 b .. 4 b + 3 of the global pair `pair` in `generation`.
+__device__ __forceinline__ void es_normals4(uint32_t k0, uint32_t k1, uint32_t b, uint32_t pair, uint32_t generation,
+                                            float e[4]) {
+  u4 c;
+  c.x = b;
+  c.y = pair;
+  c.z = generation;
+  c.w = ES_TAG;
+  const u4 x = philox4x32_10(c, k0, k1);
+  es_box_muller(x.x, x.y, e[0], e[1]);
+  es_box_muller(x.z, x.w, e[2], e[3]);
+}
+
+// grid (n_pairs, ceil(nb / 256)): a lane per (pair, block of 4 parameters)
+__global__ __launch_bounds__(256) void noise_kernel(int D, uint32_t k0, uint32_t k1, uint32_t pair0, uint32_t generation,
+                                                    float* __restrict__ eps) {
+  const int i = blockIdx.x;
+  const int b = blockIdx.y * 256 + threadIdx.x;
+  if (4 * b >= D) return;
+  float e[4];
+  es_normals4(k0, k1, (uint32_t)b, pair0 + (uint32_t)i, generation, e);
+  float* out = eps + (size_t)i * D;
+#pragma unroll
+  for (int t = 0; t < 4; t++)
+    if (4 * b + t < D) out[4 * b + t] = e[t];
+}
+
+// members 2 i and 2 i + 1 = theta +- sigma eps_i, in float64 (the product of two floats is exact there),
+// rounded once
+__global__ __launch_bounds__(256) void perturb_kernel(int D, const float* __restrict__ theta, float sigma, uint32_t k0,
+                                                      uint32_t k1, uint32_t pair0, uint32_t generation,
+                                                      float* __restrict__ members) {
+  const int i = blockIdx.x;
+  const int b = blockIdx.y * 256 + threadIdx.x;
+  if (4 * b >= D) return;
+  float e[4];
+  es_normals4(k0, k1, (uint32_t)b, pair0 + (uint32_t)i, generation, e);
+  float* plus = members + (size_t)(2 * i) * D;
+  float* minus = plus + D;
+  const double s = (double)sigma;
+#pragma unroll
+  for (int t = 0; t < 4; t++) {
+    const int d = 4 * b + t;
+    if (d < D) {
+      const double th = (double)theta[d];
+      plus[d] = (float)__builtin_fma(s, (double)e[t], th);
+      minus[d] = (float)__builtin_fma(-s, (double)e[t], th);
+    }
+  }
+}
+
+// g[d] = sum over the pairs, ascending, of w[i] eps_i[d] in float64 (exact products, one rounding per
+// add); a lane per block of 4 parameters regenerates the noise pair by pair
+__global__ __launch_bounds__(256) void grad_kernel(int D, int n_pairs, const float* __restrict__ w, uint32_t k0, uint32_t k1,
+                                                   uint32_t pair0, uint32_t generation, float* __restrict__ g) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (4 * b >= D) return;
+  double acc[4] = {0.0, 0.0, 0.0, 0.0};
+  for (int i = 0; i < n_pairs; i++) {
+    float e[4];
+    es_normals4(k0, k1, (uint32_t)b, pair0 + (uint32_t)i, generation, e);
+    const double wi = (double)w[i];
+#pragma unroll
+    for (int t = 0; t < 4; t++) acc[t] = __builtin_fma(wi, (double)e[t], acc[t]);
+  }
+#pragma unroll
+  for (int t = 0; t < 4; t++)
+    if (4 * b + t < D) g[4 * b + t] = (float)acc[t];
+}
+
+// fitness[m] = (sum over member m's G envs, ascending, of done_return + cur_return) / G; a lane per member
+__global__ __launch_bounds__(256) void fitness_kernel(int P, int G, const double* __restrict__ cur_return,
+                                                      const double* __restrict__ done_return, double* __restrict__ fitness) {
+  const int m = blockIdx.x * 256 + threadIdx.x;
+  if (m >= P) return;
+  double s = 0.0;
+  for (int k = 0; k < G; k++) {
+    const size_t e = (size_t)m * G + k;
+    s += done_return[e] + cur_return[e];
+  }
+  fitness[m] = s / (double)G;
+}
+
+// dst[r, :] = src[r * src_stride + :] for r < rows (src_stride 0: every row takes the same vector)
+__global__ __launch_bounds__(256) void copy_rows_kernel(int D, size_t src_stride, const float* __restrict__ src,
+                                                        float* __restrict__ dst) {
+  const int d = blockIdx.y * 256 + threadIdx.x;
+  if (d < D) dst[(size_t)blockIdx.x * D + d] = src[(size_t)blockIdx.x * src_stride + d];
+}
+
+// ---------------------------------------------------------------- actor
+// grid = P * tpm workgroups, tpm = ceil(G / PT) tiles per member: workgroup (m, t) owns envs
+// m G + t PT .. + rows of member m; the last tile of a member whose G is no multiple of PT has fewer rows
+// (zero-filled in LDS, nothing read or written past them).
+__global__ __launch_bounds__(PB) void population_act_kernel(const float* __restrict__ members, Dims dm, int D, int G, int tpm,
+                                                            const float* __restrict__ obs, float* __restrict__ act,
+                                                            float* __restrict__ obs_traj, float* __restrict__ act_traj,
+                                                            Book bk) {
+  __shared__ __attribute__((aligned(16))) float bufA[PD * PT];
+  __shared__ __attribute__((aligned(16))) float bufB[PD * PT];
+  const int m = blockIdx.x / tpm;
+  const int t = blockIdx.x - m * tpm;
+  const float* base = members + (size_t)m * D;
+  Weights W;
+  W.obs_dim = dm.obs_dim; W.h1 = dm.h1; W.h2 = dm.h2; W.act_dim = dm.act_dim;
+  W.w1 = base;
+  W.b1 = W.w1 + dm.obs_dim * dm.h1;
+  W.w2 = W.b1 + dm.h1;
+  W.b2 = W.w2 + dm.h1 * dm.h2;
+  W.w3 = W.b2 + dm.h2;
+  W.b3 = W.w3 + dm.h2 * dm.act_dim;
+  act_tile(W, m * G + t * PT, min(PT, G - t * PT), obs, act, obs_traj, act_traj, bk, bufA, bufB);
+}
+
+int launch_population_act(const void* actor, int n, const float* obs, float* act, float* obs_traj, float* act_traj,
+                          const Book& bk, hipStream_t stream) {
+  const pbg_population* p = static_cast<const pbg_population*>(actor);
+  const int P = 2 * p->n_pairs;
+  const int G = n / P;  // the callers have checked n % P == 0 and n > 0
+  const int tpm = (G + PT - 1) / PT;
+  const Dims dm{p->obs_dim, p->h1, p->h2, p->act_dim};
+  hipLaunchKernelGGL(population_act_kernel, dim3((unsigned)P * (unsigned)tpm), dim3(PB), 0, stream, p->members, dm, p->D, G,
+                     tpm, obs, act, obs_traj, act_traj, bk);
+  return (int)hipGetLastError();
+}
+
+// ---------------------------------------------------------------- host side
+int hip_fail(int e, const char* what) {
+  char msg[160];
+  snprintf(msg, sizeof(msg), "%s: HIP error %d", what, e);
+  return pbg::capi_fail(PBG_E_HIP, msg);
+}
+
+int launched(const char* what) {
+  const int e = (int)hipGetLastError();
+  return e ? hip_fail(e, what) : PBG_OK;
+}
+
+bool dims_ok(int obs_dim, int h1, int h2, int act_dim) {
+  return obs_dim >= 1 && obs_dim <= PBG_POLICY_MAX_DIM && h1 >= 1 && h1 <= PBG_POLICY_MAX_DIM && h2 >= 1 &&
+         h2 <= PBG_POLICY_MAX_DIM && act_dim >= 1 && act_dim <= PBG_POLICY_MAX_ACT;
+}
+
+int bad_dims(const char* who, int obs_dim, int h1, int h2, int act_dim) {
+  char msg[200];
+  snprintf(msg, sizeof(msg), "%s: dims (%d, %d, %d, %d) outside 1..%d (obs_dim, h1, h2), 1..%d (act_dim)", who, obs_dim, h1,
+           h2, act_dim, PBG_POLICY_MAX_DIM, PBG_POLICY_MAX_ACT);
+  return pbg::capi_fail(PBG_E_ARG, msg);
+}
+
+// the largest population whose member count and whose global pair indices stay inside an int
+bool pairs_ok(int n_pairs, int pair0) { return n_pairs >= 1 && n_pairs <= INT_MAX / 2 && pair0 >= 0 && pair0 <= INT_MAX - n_pairs; }
+
+void host_philox(uint32_t c[4], uint32_t k0, uint32_t k1) {
+  for (int r = 0; r < 10; r++) {
+    const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
+    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n1 = (uint32_t)p1;
+    const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1, n3 = (uint32_t)p0;
+    c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+}
+
+// the noise contract in float64, rounded once
+void host_box_muller(uint32_t a, uint32_t b, float* n0, float* n1) {
+  const double u1 = (double)(a >> 9) * 0x1p-23 + 0x1p-24;
+  const double u2 = (double)(b >> 8) * 0x1p-24;
+  const double r = sqrt(-2.0 * log(u1));
+  const double ang = 2.0 * M_PI * u2;
+  *n0 = (float)(r * cos(ang));
+  *n1 = (float)(r * sin(ang));
+}
+
+dim3 pair_grid(const pbg_population* p) { return dim3((unsigned)p->n_pairs, (unsigned)(((p->D + 3) / 4 + 255) / 256)); }
+
+}  // namespace
+
+extern "C" {
+
+int pbg_population_create(int device, int obs_dim, int h1, int h2, int act_dim, int n_pairs, int pair0,
+                          pbg_population** out) {
+  if (!out) return pbg::capi_fail(PBG_E_ARG, "pbg_population_create: out is NULL");
+  *out = nullptr;
+  if (!dims_ok(obs_dim, h1, h2, act_dim)) return bad_dims("pbg_population_create", obs_dim, h1, h2, act_dim);
+  if (!pairs_ok(n_pairs, pair0)) {
+    char msg[160];
+    snprintf(msg, sizeof(msg), "pbg_population_create: n_pairs %d must be >= 1 and pair0 %d >= 0 (and their sum an int)",
+             n_pairs, pair0);
+    return pbg::capi_fail(PBG_E_ARG, msg);
+  }
+  if (device < 0) return pbg::capi_fail(PBG_E_ARG, "pbg_population_create: device must be >= 0 (the members live on a GPU)");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device >= ndev) {
+    (void)hipGetLastError();
+    char msg[64];
+    snprintf(msg, sizeof(msg), "pbg_population_create: no HIP device %d", device);
+    return pbg::capi_fail(PBG_E_HIP, msg);
+  }
+  pbg_population* p = new (std::nothrow) pbg_population();
+  if (!p) return pbg::capi_fail(PBG_E_NOMEM, "pbg_population_create: out of host memory");
+  p->device = device;
+  p->obs_dim = obs_dim; p->h1 = h1; p->h2 = h2; p->act_dim = act_dim;
+  p->n_pairs = n_pairs;
+  p->pair0 = pair0;
+  p->D = param_count(Dims{obs_dim, h1, h2, act_dim});
+  p->members = nullptr;
+  DeviceGuard dg(device);
+  const size_t bytes = (size_t)2 * n_pairs * p->D * sizeof(float);
+  int e = (int)hipMalloc(&p->members, bytes);
+  if (!e) e = (int)hipMemset(p->members, 0, bytes);
+  if (e) {
+    pbg_population_destroy(p);
+    return hip_fail(e, "pbg_population_create: member storage");
+  }
+  *out = p;
+  return PBG_OK;
+}
+
+void pbg_population_destroy(pbg_population* p) {
+  if (!p) return;
+  if (p->members) {
+    DeviceGuard dg(p->device);
+    (void)hipFree(p->members);
+  }
+  delete p;
+}
+
+int pbg_population_noise_host(int obs_dim, int h1, int h2, int act_dim, uint64_t seed, uint32_t generation, int pair0,
+                              int n_pairs, float* eps_out) {
+  if (!dims_ok(obs_dim, h1, h2, act_dim)) return bad_dims("pbg_population_noise_host", obs_dim, h1, h2, act_dim);
+  if (!pairs_ok(n_pairs, pair0) || !eps_out)
+    return pbg::capi_fail(PBG_E_ARG, "pbg_population_noise_host: n_pairs must be >= 1, pair0 >= 0 and eps_out not NULL");
+  const int D = param_count(Dims{obs_dim, h1, h2, act_dim});
+  const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+  for (int i = 0; i < n_pairs; i++) {
+    float* row = eps_out + (size_t)i * D;
+    for (int b = 0; 4 * b < D; b++) {
+      uint32_t c[4] = {(uint32_t)b, (uint32_t)pair0 + (uint32_t)i, generation, ES_TAG};
+      host_philox(c, k0, k1);
+      float e[4];
+      host_box_muller(c[0], c[1], &e[0], &e[1]);
+      host_box_muller(c[2], c[3], &e[2], &e[3]);
+      for (int t = 0; t < 4 && 4 * b + t < D; t++) row[4 * b + t] = e[t];
+    }
+  }
+  return PBG_OK;
+}
+
+int pbg_population_noise(const pbg_population* p, uint64_t seed, uint32_t generation, float* eps_out, void* stream) {
+  if (!p || !eps_out) return pbg::capi_fail(PBG_E_ARG, "pbg_population_noise: NULL population or eps_out");
+  DeviceGuard dg(p->device);
+  hipLaunchKernelGGL(noise_kernel, pair_grid(p), dim3(256), 0, (hipStream_t)stream, p->D, (uint32_t)seed,
+                     (uint32_t)(seed >> 32), (uint32_t)p->pair0, generation, eps_out);
+  return launched("noise_kernel launch");
+}
+
+int pbg_population_perturb(pbg_population* p, const float* theta, float sigma, uint64_t seed, uint32_t generation,
+                           void* stream) {
+  if (!p || !theta) return pbg::capi_fail(PBG_E_ARG, "pbg_population_perturb: NULL population or theta");
+  DeviceGuard dg(p->device);
+  hipLaunchKernelGGL(perturb_kernel, pair_grid(p), dim3(256), 0, (hipStream_t)stream, p->D, theta, sigma, (uint32_t)seed,
+                     (uint32_t)(seed >> 32), (uint32_t)p->pair0, generation, p->members);
+  return launched("perturb_kernel launch");
+}
+
+int pbg_population_set_member(pbg_population* p, int m, const float* theta, void* stream) {
+  if (!p || !theta) return pbg::capi_fail(PBG_E_ARG, "pbg_population_set_member: NULL population or theta");
+  const int P = 2 * p->n_pairs;
+  if (m < -1 || m >= P) {
+    char msg[96];
+    snprintf(msg, sizeof(msg), "pbg_population_set_member: member %d outside 0..%d (or -1 for every member)", m, P - 1);
+    return pbg::capi_fail(PBG_E_ARG, msg);
+  }
+  DeviceGuard dg(p->device);
+  const unsigned rows = m < 0 ? (unsigned)P : 1u;
+  float* dst = p->members + (m < 0 ? (size_t)0 : (size_t)m * p->D);
+  hipLaunchKernelGGL(copy_rows_kernel, dim3(rows, (unsigned)((p->D + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p->D,
+                     (size_t)0, theta, dst);
+  return launched("set_member launch");
+}
+
+int pbg_population_get_member(const pbg_population* p, int m, float* theta_out, void* stream) {
+  if (!p || !theta_out) return pbg::capi_fail(PBG_E_ARG, "pbg_population_get_member: NULL population or theta_out");
+  const int P = 2 * p->n_pairs;
+  if (m < 0 || m >= P) {
+    char msg[96];
+    snprintf(msg, sizeof(msg), "pbg_population_get_member: member %d outside 0..%d", m, P - 1);
+    return pbg::capi_fail(PBG_E_ARG, msg);
+  }
+  DeviceGuard dg(p->device);
+  hipLaunchKernelGGL(copy_rows_kernel, dim3(1u, (unsigned)((p->D + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p->D,
+                     (size_t)0, p->members + (size_t)m * p->D, theta_out);
+  return launched("get_member launch");
+}
+
+int pbg_population_act(const pbg_population* p, int n, const float* obs, float* act, void* stream) {
+  if (!p) return pbg::capi_fail(PBG_E_ARG, "pbg_population_act: population is NULL");
+  const int P = 2 * p->n_pairs;
+  if (n < 0 || n % P != 0 || (n > 0 && (!obs || !act))) {
+    char msg[128];
+    snprintf(msg, sizeof(msg), "pbg_population_act: n = %d must be a multiple of the %d members, obs and act not NULL", n, P);
+    return pbg::capi_fail(PBG_E_ARG, msg);
+  }
+  if (n == 0) return PBG_OK;
+  DeviceGuard dg(p->device);
+  Book none;
+  memset(&none, 0, sizeof(none));
+  const int e = launch_population_act(p, n, obs, act, nullptr, nullptr, none, (hipStream_t)stream);
+  return e ? hip_fail(e, "population_act_kernel launch") : PBG_OK;
+}
+
+int pbg_rollout_population(pbg_handle* h, const pbg_population* p, const pbg_rollout_io_t* io, void* stream) {
+  if (!h || !p || !io) return pbg::capi_fail(PBG_E_ARG, "pbg_rollout_population: NULL handle, population or io");
+  return rollout_loop("pbg_rollout_population", h, io, stream, p->device, p->obs_dim, p->act_dim, 2 * p->n_pairs,
+                      launch_population_act, p);
+}
+
+int pbg_population_fitness(const pbg_population* p, int n, const double* cur_return, const double* done_return,
+                           double* fitness_out, void* stream) {
+  if (!p || !cur_return || !done_return || !fitness_out)
+    return pbg::capi_fail(PBG_E_ARG, "pbg_population_fitness: NULL population or buffer");
+  const int P = 2 * p->n_pairs;
+  if (n < P || n % P != 0) {
+    char msg[128];
+    snprintf(msg, sizeof(msg), "pbg_population_fitness: n = %d must be a positive multiple of the %d members", n, P);
+    return pbg::capi_fail(PBG_E_ARG, msg);
+  }
+  DeviceGuard dg(p->device);
+  hipLaunchKernelGGL(fitness_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, (hipStream_t)stream, P, n / P, cur_return,
+                     done_return, fitness_out);
+  return launched("fitness_kernel launch");
+}
+
+int pbg_population_grad(const pbg_population* p, const float* w, uint64_t seed, uint32_t generation, float* g_out,
+                        void* stream) {
+  if (!p || !w || !g_out) return pbg::capi_fail(PBG_E_ARG, "pbg_population_grad: NULL population, w or g_out");
+  DeviceGuard dg(p->device);
+  const int nb = (p->D + 3) / 4;
+  hipLaunchKernelGGL(grad_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p->D, p->n_pairs, w,
+                     (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)p->pair0, generation, g_out);
+  return launched("grad_kernel launch");
+}
+
+}  // extern "C"

@@ -104,3 +104,212 @@ class MLPPolicy:
                                                    torch.cuda.current_stream(self.device).cuda_stream),
                       "pbg_policy_act")
         return y
+
+
+def param_count(dims) -> int:
+    """D of the flat parameter vector of dims = (obs_dim, h1, h2, act_dim) (include/pbg.h)."""
+    o, h1, h2, a = [int(d) for d in dims]
+    return o * h1 + h1 + h1 * h2 + h2 + h2 * a + a
+
+
+def pack_theta(ws) -> np.ndarray:
+    """The six arrays w1, b1, w2, b2, w3, b3 -> the flat float32 ``[D]`` vector (their unpadded row-major
+    concatenation, include/pbg.h "Flat parameter layout")."""
+    return np.concatenate([np.ascontiguousarray(np.asarray(a), dtype=np.float32).ravel() for a in ws])
+
+
+def unpack_theta(dims, theta):
+    """The flat ``[D]`` vector -> the six arrays (copies) in ``MLPPolicy``'s order and shapes."""
+    o, h1, h2, a = [int(d) for d in dims]
+    t = np.ascontiguousarray(np.asarray(theta), dtype=np.float32)
+    if t.shape != (param_count(dims),):
+        raise _native.PbgError(f"unpack_theta: theta shape {t.shape}, expected ({param_count(dims)},)")
+    out, at = [], 0
+    for shape in ((o, h1), (h1,), (h1, h2), (h2,), (h2, a), (a,)):
+        cnt = int(np.prod(shape))
+        out.append(t[at:at + cnt].reshape(shape).copy())
+        at += cnt
+    return out
+
+
+class MLPPopulation:
+    """``2 * n_pairs`` weight sets ("members") of one MLP shape on one GPU (include/pbg.h pbg_population_*):
+    the population of an evolution strategy with mirrored sampling.  Members ``2 i`` and ``2 i + 1`` are the
+    pair ``theta +- sigma eps_i``; ``pair0`` is the global index of the first pair when this object holds a
+    slice of a larger population (the noise depends on the global index only).
+
+    ``dims = (obs_dim, h1, h2, act_dim)``.  A parameter vector ("theta") is a contiguous float32 tensor of
+    ``n_params`` elements on ``device``: w1, b1, w2, b2, w3, b3 concatenated (``pack_theta``).  ``act``
+    and ``VecEnv.rollout`` split a batch of ``n = n_members * G`` envs into ``n_members`` consecutive
+    groups of ``G``; group m runs member m.  Every method is asynchronous on the current stream and
+    allocates only the results it is not handed (``out=``), so a generation captures into a HIP graph."""
+
+    def __init__(self, dims, n_pairs: int, device, pair0: int = 0):
+        import torch
+        self.dims = tuple(int(d) for d in dims)
+        if len(self.dims) != 4:
+            raise _native.PbgError(f"MLPPopulation: dims must be (obs_dim, h1, h2, act_dim), got {dims!r}")
+        self.obs_dim, self.h1, self.h2, self.act_dim = self.dims
+        self.n_pairs, self.pair0 = int(n_pairs), int(pair0)
+        self.n_members = 2 * self.n_pairs
+        self.n_params = param_count(self.dims)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise _native.PbgError(f"MLPPopulation: device must be a GPU, got {device!r}")
+        idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
+        self.device = torch.device("cuda", idx)
+        if not hasattr(_native.lib(), "pbg_population_create"):
+            raise _native.PbgError(f"{_native.LIB_PATH} has no pbg_population_create: a build without populations")
+        h = ctypes.c_void_p()
+        _native.check(_native.lib().pbg_population_create(idx, *self.dims, self.n_pairs, self.pair0, ctypes.byref(h)),
+                      "pbg_population_create")
+        self._pop = h
+
+    def close(self):
+        if getattr(self, "_pop", None):
+            _native.lib().pbg_population_destroy(self._pop)
+            self._pop = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    # ------------------------------------------------------------------ helpers
+    def _open(self, what):
+        if not getattr(self, "_pop", None):
+            raise _native.PbgError(f"MLPPopulation.{what}: the population is closed")
+        return self._pop
+
+    def _stream(self):
+        import torch
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    def _vec(self, t, what, name, shape, dtype=None):
+        """``t`` must already be a contiguous tensor of ``shape`` and ``dtype`` on the device: the native
+        call takes its pointer as is, so nothing is converted (or written past) silently."""
+        import torch
+        dtype = torch.float32 if dtype is None else dtype
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.device != self.device or \
+                not t.is_contiguous() or tuple(t.shape) != tuple(shape):
+            raise _native.PbgError(f"MLPPopulation.{what}: {name} must be a contiguous {dtype} tensor of shape "
+                                   f"{tuple(shape)} on {self.device}")
+        return t
+
+    # ------------------------------------------------------------------ parameters
+    def init_theta(self, seed: int = 0):
+        """A fresh centre: weights N(0, 1 / fan-in), biases zero (numpy ``default_rng(seed)``), as a device
+        float32 tensor ``[n_params]``."""
+        import torch
+        rng = np.random.default_rng(seed)
+        ws = []
+        for k, h in ((self.obs_dim, self.h1), (self.h1, self.h2), (self.h2, self.act_dim)):
+            ws.append((rng.standard_normal((k, h)) / np.sqrt(k)).astype(np.float32))
+            ws.append(np.zeros(h, np.float32))
+        return torch.from_numpy(pack_theta(ws)).to(self.device)
+
+    def perturb(self, theta, sigma: float, seed: int, generation: int):
+        """members ``2 i``, ``2 i + 1`` = ``theta +- sigma * eps_i`` (float64 arithmetic, rounded once)."""
+        p = self._open("perturb")
+        theta = self._vec(theta, "perturb", "theta", (self.n_params,))
+        _native.check(_native.lib().pbg_population_perturb(p, theta.data_ptr(), float(sigma), int(seed), int(generation),
+                                                           self._stream()), "pbg_population_perturb")
+
+    def noise(self, seed: int, generation: int, out=None):
+        """``[n_pairs, n_params]`` float32: the eps of ``generation``, the bits ``perturb`` and ``grad`` use."""
+        import torch
+        p = self._open("noise")
+        shape = (self.n_pairs, self.n_params)
+        out = torch.empty(shape, dtype=torch.float32, device=self.device) if out is None else out
+        out = self._vec(out, "noise", "out", shape)
+        _native.check(_native.lib().pbg_population_noise(p, int(seed), int(generation), out.data_ptr(), self._stream()),
+                      "pbg_population_noise")
+        return out
+
+    def grad(self, w, seed: int, generation: int, out=None):
+        """``g[d] = sum_i w[i] * eps_i[d]`` (pair-ascending float64 sum, cast to float32); ``w``: float32
+        ``[n_pairs]`` on the device."""
+        import torch
+        p = self._open("grad")
+        w = self._vec(w, "grad", "w", (self.n_pairs,))
+        out = torch.empty(self.n_params, dtype=torch.float32, device=self.device) if out is None else out
+        out = self._vec(out, "grad", "out", (self.n_params,))
+        _native.check(_native.lib().pbg_population_grad(p, w.data_ptr(), int(seed), int(generation), out.data_ptr(),
+                                                        self._stream()), "pbg_population_grad")
+        return out
+
+    def fitness(self, rollout_result, out=None):
+        """Per-member mean return per env, float64 ``[n_members]``: the mean over the member's envs of
+        ``done_return + cur_return`` of a ``RolloutResult`` (env-ascending float64 sum / G)."""
+        import torch
+        p = self._open("fitness")
+        cur, done = rollout_result.cur_return, rollout_result.done_return
+        n = cur.shape[0] if isinstance(cur, torch.Tensor) and cur.dim() == 1 else -1
+        if n < self.n_members or n % self.n_members != 0:
+            raise _native.PbgError(f"MLPPopulation.fitness: {n} envs are not a positive multiple of the "
+                                   f"{self.n_members} members")
+        cur = self._vec(cur, "fitness", "cur_return", (n,), torch.float64)
+        done = self._vec(done, "fitness", "done_return", (n,), torch.float64)
+        out = torch.empty(self.n_members, dtype=torch.float64, device=self.device) if out is None else out
+        out = self._vec(out, "fitness", "out", (self.n_members,), torch.float64)
+        _native.check(_native.lib().pbg_population_fitness(p, n, cur.data_ptr(), done.data_ptr(), out.data_ptr(),
+                                                           self._stream()), "pbg_population_fitness")
+        return out
+
+    def set_all(self, theta):
+        """Every member = ``theta`` (the centre's evaluation)."""
+        self.set_member(-1, theta)
+
+    def set_member(self, m: int, theta):
+        p = self._open("set_member")
+        theta = self._vec(theta, "set_member", "theta", (self.n_params,))
+        _native.check(_native.lib().pbg_population_set_member(p, int(m), theta.data_ptr(), self._stream()),
+                      "pbg_population_set_member")
+
+    def get_member(self, m: int, out=None):
+        """Member ``m``'s parameter vector as a device tensor."""
+        import torch
+        p = self._open("get_member")
+        out = torch.empty(self.n_params, dtype=torch.float32, device=self.device) if out is None else out
+        out = self._vec(out, "get_member", "out", (self.n_params,))
+        _native.check(_native.lib().pbg_population_get_member(p, int(m), out.data_ptr(), self._stream()),
+                      "pbg_population_get_member")
+        return out
+
+    def member_weights(self, m: int):
+        """Member ``m`` as the six numpy arrays ``MLPPolicy`` takes (synchronises)."""
+        return unpack_theta(self.dims, self.get_member(m).cpu().numpy())
+
+    def save_npz(self, path, theta_or_member):
+        """Write a parameter vector (a tensor or array ``[n_params]``) or member (an int) as an npz with the
+        reference's key names: ``MLPPolicy.from_npz`` and tools/enjoy.py load it."""
+        if isinstance(theta_or_member, (int, np.integer)):
+            ws = self.member_weights(int(theta_or_member))
+        else:
+            t = theta_or_member
+            ws = unpack_theta(self.dims, t.detach().cpu().numpy() if hasattr(t, "detach") else t)
+        np.savez(path, **dict(zip(NPZ_KEYS, ws)))
+
+    # ------------------------------------------------------------------ actor
+    def act(self, obs, out=None):
+        """``[n, obs_dim]`` float32 observations -> ``[n, act_dim]`` actions, ``n`` a multiple of
+        ``n_members``: rows ``m G .. (m + 1) G`` (``G = n / n_members``) through member m, each row
+        bit for bit what a host ``MLPPolicy`` of that member's weights computes."""
+        import torch
+        p = self._open("act")
+        x = obs
+        if not isinstance(x, torch.Tensor):
+            raise _native.PbgError("MLPPopulation.act: obs must be a torch tensor")
+        if x.dtype != torch.float32 or x.device != self.device or not x.is_contiguous():
+            x = x.to(device=self.device, dtype=torch.float32).contiguous()
+        if x.dim() != 2 or x.shape[1] != self.obs_dim:
+            raise _native.PbgError(f"MLPPopulation.act: obs shape {tuple(x.shape)}, expected [n, {self.obs_dim}]")
+        n = x.shape[0]
+        if n % self.n_members != 0:
+            raise _native.PbgError(f"MLPPopulation.act: {n} rows are not a multiple of the {self.n_members} members")
+        y = torch.empty((n, self.act_dim), dtype=torch.float32, device=self.device) if out is None else out
+        y = self._vec(y, "act", "out", (n, self.act_dim))
+        _native.check(_native.lib().pbg_population_act(p, n, x.data_ptr(), y.data_ptr(), self._stream()),
+                      "pbg_population_act")
+        return y

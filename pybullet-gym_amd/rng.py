@@ -66,3 +66,30 @@ def sample_actions(action_dim: int, global_ids, steps, seed: int = 0x5EED) -> np
             if j < action_dim:
                 out[..., j] = v[..., t]
     return out
+
+
+def es_param_count(dims) -> int:
+    """D of the flat parameter vector of an MLP dims = (obs_dim, h1, h2, act_dim) (include/pbg.h)."""
+    o, h1, h2, a = [int(d) for d in dims]
+    return o * h1 + h1 + h1 * h2 + h2 + h2 * a + a
+
+
+def es_noise(dims, seed: int, generation: int, pair0: int, n_pairs: int) -> np.ndarray:
+    """float32 [n_pairs, D]: the evolution-strategy noise of pbg_population_noise (include/pbg.h "Noise
+    contract": Philox4x32-10, key = seed, counter = (block of 4 params, pair0 + i, generation, 0xE5), two
+    Box-Muller pairs per block), computed in float64 and rounded once like pbg_population_noise_host.
+    The device computes the same formula in float32: it agrees within 1e-5 absolute, not bitwise."""
+    D = es_param_count(dims)
+    nb = (D + 3) // 4
+    key = (seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF)
+    B, I = np.meshgrid(np.arange(nb, dtype=np.uint32), np.arange(pair0, pair0 + n_pairs, dtype=np.uint32))
+    ctr = np.stack([B, I, np.full_like(B, generation & 0xFFFFFFFF), np.full_like(B, 0xE5)], axis=-1)
+    x = philox4x32_10(ctr, key)
+    out = np.empty((n_pairs, nb, 4), dtype=np.float32)
+    for h in (0, 1):
+        u1 = (x[..., 2 * h] >> np.uint32(9)).astype(np.float64) * 2.0 ** -23 + 2.0 ** -24
+        u2 = (x[..., 2 * h + 1] >> np.uint32(8)).astype(np.float64) * 2.0 ** -24
+        r = np.sqrt(-2.0 * np.log(u1))
+        out[..., 2 * h] = r * np.cos(2.0 * np.pi * u2)
+        out[..., 2 * h + 1] = r * np.sin(2.0 * np.pi * u2)
+    return np.ascontiguousarray(out.reshape(n_pairs, 4 * nb)[:, :D])

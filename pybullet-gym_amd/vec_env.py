@@ -202,7 +202,9 @@ class VecEnv:
         """``steps`` closed-loop env steps of every env, ``env.step(policy.act(obs))`` (the loop of the
         reference's enjoy_TF_*.py scripts), entirely on the device: pbg_rollout, two kernel launches
         per step plus one per call, no host work in between.  ``policy``: an ``MLPPolicy`` on this
-        env's device.  It starts from ``self.obs`` (the last ``reset`` / ``step`` / ``rollout``) and
+        env's device, or an ``MLPPopulation`` (pbg_rollout_population: ``num_envs`` must be a multiple of
+        its ``n_members``; env e runs member ``e // (num_envs // n_members)``).  It starts from
+        ``self.obs`` (the last ``reset`` / ``step`` / ``rollout``) and
         leaves the last observation there.  The other step outputs are NOT refreshed: ``truncated``,
         ``terminal_obs`` and ``reward64`` keep what the last ``step`` left, and with
         ``trajectory=True`` so do ``reward`` and ``done`` (the step then writes them straight into
@@ -223,8 +225,14 @@ class VecEnv:
         if steps < 1:
             raise _native.PbgError(f"rollout: steps must be >= 1 (got {steps})")
         n, info, kw = self.num_envs, self.info, dict(device=self.device)
-        if getattr(policy, "_p", None) is None or not hasattr(_native.lib(), "pbg_rollout"):
-            raise _native.PbgError("rollout: policy must be an open MLPPolicy (and the library built with pbg_rollout)")
+        pop = getattr(policy, "_pop", None)  # an MLPPopulation: env e runs member e // (n // n_members)
+        if pop is not None:
+            if n % policy.n_members != 0:
+                raise _native.PbgError(f"rollout: {n} envs are not a multiple of the population's "
+                                       f"{policy.n_members} members")
+        elif getattr(policy, "_p", None) is None or not hasattr(_native.lib(), "pbg_rollout"):
+            raise _native.PbgError("rollout: policy must be an open MLPPolicy or MLPPopulation (and the library "
+                                   "built with pbg_rollout)")
         if self._ro_acc is None:
             self._ro_acc = dict(cur_return=torch.zeros(n, dtype=torch.float64, **kw),
                                 cur_length=torch.zeros(n, dtype=torch.int32, **kw),
@@ -248,8 +256,12 @@ class VecEnv:
             self._ro_io[key] = (io, traj)
         io, traj = self._ro_io[key]
         io.autoreset = 1 if self.autoreset else 0
-        _native.check(_native.lib().pbg_rollout(self._h, policy._p, ctypes.byref(io),
-                                                _stream(self.device)), "pbg_rollout")
+        if pop is not None:
+            _native.check(_native.lib().pbg_rollout_population(self._h, pop, ctypes.byref(io),
+                                                               _stream(self.device)), "pbg_rollout_population")
+        else:
+            _native.check(_native.lib().pbg_rollout(self._h, policy._p, ctypes.byref(io),
+                                                    _stream(self.device)), "pbg_rollout")
         return RolloutResult(obs=self.obs, **self._ro_acc, obs_traj=traj.get("obs_traj"),
                              act_traj=traj.get("act_traj"), rew_traj=traj.get("rew_traj"),
                              done_traj=traj.get("done_traj"))

@@ -1,0 +1,215 @@
+#!/usr/bin/env python3
+"""Population rollout benchmark: what per-member weights cost beside the shared-weight actor.
+
+Float64 Ant at 16,384 envs; each leg a HIP graph of K = 20 closed-loop steps on an env of its own, timed
+in one process with tools/bench_rollout.py's protocol (pre-roll, warm replay, five windows bracketed by
+device events, the legs alternated per window):
+
+  A  VecEnv.rollout(MLPPolicy): one weight set for every env (pbg_rollout, the baseline)
+  B  VecEnv.rollout(MLPPopulation) at 1,024 members x 16 envs (pbg_rollout_population)
+  C  the same at 4,096 members x 4 envs: a quarter-filled 16-env tile per member
+
+Every member holds the pretrained Ant weights the baseline runs, so the three legs compute the same
+actions from the same states (asserted on the final observations) and differ only in where the actor
+reads its weights from: one 49 KB set through L2, or one set per member from HBM.
+
+Also measured: a device-to-device copy's bandwidth on the same box (the yardstick for the actor's weight
+stream) and the once-per-generation work outside the rollout (perturb + fitness + ranks + grad + update,
+one HIP graph) at 512 pairs.
+
+  python tools/bench_population.py [--out profiles/population_rollout.json]
+  python tools/bench_population.py --actor-only [--members 1024]   # actor launches alone, for a kernel trace
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import statistics
+import sys
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+sys.path.insert(0, os.path.join(REPO, "tests"))
+
+ENV_ID, N = "AntPyBulletEnv-v0", 16384
+K = 20  # steps per graph
+LEGS = {"A": None, "B": 1024, "C": 4096}  # members (None: the shared-weight policy)
+
+
+def capture(fn, dev):
+    import torch
+    s = torch.cuda.Stream(dev)
+    s.wait_stream(torch.cuda.current_stream(dev))
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g, stream=s):
+        fn()
+    torch.cuda.current_stream(dev).wait_stream(s)
+    return g
+
+
+def actors(dev, members):
+    """The pretrained Ant policy as an MLPPolicy and as populations whose members all hold its weights."""
+    import torch
+    import policies
+    from pybulletgym_amd.policy import MLPPolicy, MLPPopulation, pack_theta
+    ws = policies.Policy(ENV_ID).w
+    dims = (ws[0].shape[0], ws[0].shape[1], ws[2].shape[1], ws[4].shape[1])
+    theta = torch.from_numpy(pack_theta(ws)).to(dev)
+    out = {}
+    for leg, m in members.items():
+        if m is None:
+            out[leg] = MLPPolicy(*ws, device=dev)
+        else:
+            out[leg] = MLPPopulation(dims, m // 2, dev)
+            out[leg].set_all(theta)
+    return out, dims, theta
+
+
+def timed(windows, replays, legs, run, dev, per):
+    """`windows` rounds over the legs, each window `replays` calls of run(leg) between two device events;
+    returns {leg: [microseconds per `per`]}."""
+    import torch
+    stream = torch.cuda.current_stream(dev)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    res = {leg: [] for leg in legs}
+    for _ in range(windows):
+        for leg in legs:
+            torch.cuda.synchronize(dev)
+            e0.record(stream)
+            for _ in range(replays):
+                run(leg)
+            e1.record(stream)
+            torch.cuda.synchronize(dev)
+            res[leg].append(e0.elapsed_time(e1) * 1e3 / (replays * per))
+    return res
+
+
+def summary(w):
+    return {"windows": w, "median": {k: statistics.median(v) for k, v in w.items()},
+            "min": {k: min(v) for k, v in w.items()}, "max": {k: max(v) for k, v in w.items()}}
+
+
+def bench_rollout(args, dev):
+    import torch
+    from pybulletgym_amd.vec_env import VecEnv
+    pis, dims, _ = actors(dev, LEGS)
+    envs = {leg: VecEnv(ENV_ID, N, device=dev, seed=0, autoreset=True, precision=64) for leg in LEGS}
+    for e in envs.values():
+        e.reset()
+    pre = (args.preroll + args.warmup + K - 1) // K
+    for _ in range(pre):
+        for leg in LEGS:
+            envs[leg].rollout(pis[leg], K)
+    torch.cuda.synchronize(dev)
+    graphs = {leg: capture(lambda leg=leg: envs[leg].rollout(pis[leg], K), dev) for leg in LEGS}
+    for leg in LEGS:
+        graphs[leg].replay()
+    w = timed(args.windows, args.replays, list(LEGS), lambda leg: graphs[leg].replay(), dev, K)
+    out = summary(w)
+    med = out["median"]
+    D = pis["B"].n_params
+    out.update({"env_id": ENV_ID, "n_envs": N, "precision": 64, "steps_per_graph": K, "replays_per_window": args.replays,
+                "unit": "us per env-batch step", "members": LEGS, "mlp_dims": dims, "params_per_member": D,
+                "B_minus_A_us": med["B"] - med["A"], "C_minus_A_us": med["C"] - med["A"],
+                # every member holds A's weights: the three envs must be in the same state, bit for bit
+                "final_obs_equal": bool(torch.equal(envs["A"].obs, envs["B"].obs) and
+                                        torch.equal(envs["A"].obs, envs["C"].obs)),
+                "actor_weight_bytes_per_step": {leg: (1 if m is None else m * ((N // m + 15) // 16)) * D * 4
+                                                for leg, m in LEGS.items()}})
+    for e in envs.values():
+        e.close()
+    for p in pis.values():
+        p.close()
+    return out
+
+
+def bench_copy(args, dev):
+    """Device-to-device copy of 1 GiB: bytes read plus bytes written over the time."""
+    import torch
+    n = 1 << 28
+    a = torch.empty(n, dtype=torch.float32, device=dev).normal_()
+    b = torch.empty_like(a)
+    for _ in range(3):
+        b.copy_(a)
+    w = timed(args.windows, 10, ["copy"], lambda leg: b.copy_(a), dev, 1)["copy"]
+    gbs = [2 * 4 * n / (us * 1e-6) / 1e9 for us in w]
+    return {"bytes_each_way": 4 * n, "us": w, "GB_per_s_read_plus_write": {"median": statistics.median(gbs),
+                                                                           "min": min(gbs), "max": max(gbs)}}
+
+
+def bench_generation(args, dev):
+    """perturb + fitness + centred ranks + grad + the centre's update at 512 pairs x 16 envs, one graph."""
+    import torch
+    from pybulletgym_amd.es import EvolutionStrategy
+    from pybulletgym_amd.vec_env import VecEnv
+    pis, dims, theta = actors(dev, {"B": 1024})
+    pop = pis["B"]
+    env = VecEnv(ENV_ID, N, device=dev, seed=0, autoreset=True, precision=64)
+    env.reset()
+    es = EvolutionStrategy(env, pop, sigma=0.02, lr=0.01, steps=K, seed=0)
+    es.theta.copy_(theta)
+    res = env.rollout(pop, K, fresh=True)
+
+    def generation():
+        pop.perturb(es.theta, es.sigma, es.seed, 0)
+        es.update(res, 0)
+
+    generation()
+    torch.cuda.synchronize(dev)
+    g = capture(generation, dev)
+    g.replay()
+    w = timed(args.windows, 20, ["generation"], lambda leg: g.replay(), dev, 1)["generation"]
+    out = {"n_pairs": pop.n_pairs, "params": pop.n_params, "unit": "us per generation (without the rollout)", "us": w,
+           "median": statistics.median(w), "min": min(w), "max": max(w)}
+    env.close()
+    pop.close()
+    return out
+
+
+def actor_only(args, dev):
+    """Launches of the actors alone at n = 16,384 (run under a kernel trace): the shared-weight kernel and
+    the population kernel at --members."""
+    import torch
+    pis, dims, _ = actors(dev, {"A": None, "P": args.members})
+    obs = torch.randn((N, dims[0]), device=dev)
+    out = torch.empty((N, dims[3]), device=dev)
+    for _ in range(50):
+        pis["A"].act(obs, out=out)
+        pis["P"].act(obs, out=out)
+    torch.cuda.synchronize(dev)
+    print(f"actor-only done: policy_act_kernel and population_act_kernel at {args.members} members x {N // args.members}")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "population_rollout.json"))
+    ap.add_argument("--preroll", type=int, default=200)
+    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--windows", type=int, default=5)
+    ap.add_argument("--replays", type=int, default=10, help="graph replays (of 20 steps) per timed window")
+    ap.add_argument("--actor-only", action="store_true")
+    ap.add_argument("--members", type=int, default=1024)
+    args = ap.parse_args()
+    import torch
+    import pybulletgym_amd  # noqa: F401
+    dev = torch.device("cuda:0")
+    if args.actor_only:
+        return actor_only(args, dev)
+    res = {"rollout": bench_rollout(args, dev), "copy": bench_copy(args, dev), "generation": bench_generation(args, dev)}
+    bw = res["copy"]["GB_per_s_read_plus_write"]["median"]
+    res["actor_weight_stream_at_copy_bandwidth_us"] = {
+        leg: b / (bw * 1e9) * 1e6 for leg, b in res["rollout"]["actor_weight_bytes_per_step"].items()}
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(res, f, indent=1)
+    r = res["rollout"]
+    print("rollout us/step median [min, max]: " + "  ".join(
+        f"{leg} {r['median'][leg]:.1f} [{r['min'][leg]:.1f}, {r['max'][leg]:.1f}]" for leg in LEGS) +
+        f"  B-A {r['B_minus_A_us']:.1f}  C-A {r['C_minus_A_us']:.1f}  same states: {r['final_obs_equal']}")
+    print(f"copy {bw:.0f} GB/s (read + write)  generation {res['generation']['median']:.1f} us")
+    print(json.dumps({"done": bool(r["final_obs_equal"]), "out": args.out}))
+
+
+if __name__ == "__main__":
+    main()
