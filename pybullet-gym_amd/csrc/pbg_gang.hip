@@ -54,59 +54,7 @@ namespace pbg {
 template <class R, int T = 16>
 constexpr int gang_block();  // (after the layout: the float64 regions decide it)
 
-// bound_ctrl set: every permutation used here reads a valid lane, and with it the
-// compiler folds `x + mov_dpp(x)` into one v_add_f32_dpp (no mov, no DPP hazard nop).
-template <int CTRL>
-PBG_DEV float dpp_f(float x) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, x), CTRL, 0xF, 0xF, true));
-}
-// float64: the two dwords moved by the same permutation
-template <int CTRL>
-PBG_DEV double dpp_f(double x) {
-  const uint64_t u = __builtin_bit_cast(uint64_t, x);
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_mov_dpp((int)(uint32_t)u, CTRL, 0xF, 0xF, true);
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_mov_dpp((int)(uint32_t)(u >> 32), CTRL, 0xF, 0xF, true);
-  return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
-}
-// gfx950 v_permlane16_swap_b32 a, b: the odd rows of a trade places with the even rows of b.
-// With a = b = x (x uniform within each row) a ends up holding the even row's value and b the odd
-// row's, in both rows of each pair.  Inline asm because this ROCm's builtin
-// (__builtin_amdgcn_permlane16_swap) returns the first register for both of its results.  The
-// compiler's hazard recognizer cannot see inside the asm, so the s_nop 3 (4 wait states) covers
-// both hazards a preceding VALU instruction can leave for a permlane: a VALU write of an operand
-// register, and a VALU write of EXEC (v_cmpx) -- the latter needs 4 wait states on gfx950.
-// gang_sum<32> is only called from the 32-lane kernel's row reductions, all reached with the
-// gang's full EXEC mask (wave-uniform control flow).
-PBG_DEV void row_pair_swap(float& a, float& b) {
-  asm volatile("s_nop 3\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b));
-}
-PBG_DEV void row_pair_swap_u(uint32_t& a, uint32_t& b) {
-  asm volatile("s_nop 3\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b));
-}
-PBG_DEV void row_pair_swap(double& a, double& b) {  // the two dwords of each
-  uint64_t ua = __builtin_bit_cast(uint64_t, a), ub = __builtin_bit_cast(uint64_t, b);
-  uint32_t al = (uint32_t)ua, ah = (uint32_t)(ua >> 32), bl = (uint32_t)ub, bh = (uint32_t)(ub >> 32);
-  row_pair_swap_u(al, bl);
-  row_pair_swap_u(ah, bh);
-  a = __builtin_bit_cast(double, ((uint64_t)ah << 32) | al);
-  b = __builtin_bit_cast(double, ((uint64_t)bh << 32) | bl);
-}
-// all-reduce over the T (4, 8, 16 or 32) lanes of a DPP row segment (T = 32: a row pair);
-// identical bits in every lane (each step adds a value and its mirror image: a + b == b + a;
-// the row-pair step adds the even row's sum to the odd row's in that order in both rows)
-template <int T, class V>
-PBG_DEV V gang_sum(V x) {
-  x = x + dpp_f<0xB1>(x);  // quad_perm [1,0,3,2]
-  x = x + dpp_f<0x4E>(x);  // quad_perm [2,3,0,1]
-  if constexpr (T >= 8) x = x + dpp_f<0x141>(x);   // row_half_mirror
-  if constexpr (T >= 16) x = x + dpp_f<0x140>(x);  // row_mirror
-  if constexpr (T >= 32) {
-    V a = x, b = x;
-    row_pair_swap(a, b);  // a: the even row's value, b: the odd row's, in both rows of the pair
-    x = a + b;
-  }
-  return x;
-}
+// the row helpers -- dpp_f, dpp_u, row_pair_swap, gang_sum, gang_sum_u32 -- live in pbg_lanes.h
 PBG_DEV bool wave_any(bool p) { return __ballot(p) != 0ull; }
 // a 32-bit chain mask stored in a word of the contact descriptor (its bits, not a number)
 template <class S>
@@ -116,24 +64,6 @@ PBG_DEV S mask_word(uint32_t m) {
 }
 PBG_DEV uint32_t word_mask(float w) { return __builtin_bit_cast(uint32_t, w); }
 PBG_DEV uint32_t word_mask(double w) { return (uint32_t)__builtin_bit_cast(uint64_t, w); }
-template <int CTRL>
-PBG_DEV uint32_t dpp_u(uint32_t x) {
-  return (uint32_t)__builtin_amdgcn_mov_dpp((int)x, CTRL, 0xF, 0xF, true);
-}
-// integer sum over the T lanes of a DPP row segment (mod 2^32), same in every lane
-template <int T>
-PBG_DEV uint32_t gang_sum_u32(uint32_t x) {
-  x += dpp_u<0xB1>(x);
-  x += dpp_u<0x4E>(x);
-  if constexpr (T >= 8) x += dpp_u<0x141>(x);
-  if constexpr (T >= 16) x += dpp_u<0x140>(x);
-  if constexpr (T >= 32) {
-    uint32_t a = x, b = x;
-    row_pair_swap_u(a, b);
-    x = a + b;
-  }
-  return x;
-}
 // 32-lane gangs (two envs per wave): for the robots whose factorisation is front-parallel and
 // whose per-lane registers then fit two waves per SIMD (Humanoid family).  The 16-lane kernel
 // stays for the others, and for these under pbg_create_debug(gang_lanes = 16).

@@ -69,8 +69,16 @@ PBG_DEV V3<S> cross3(V3<S> a, V3<S> b) {
 // (correctly rounded) sqrt, fast_rsq an IEEE division of it, and fast_rcp is NOT correctly rounded
 // -- it is within 1 ulp of the IEEE quotient for finite, non-zero, non-overflowing-reciprocal
 // arguments only (x = 0 gives NaN, not inf).  Every call site guards its argument; the checks build
-// (-DPBG_DEV_CHECKS) asserts it.
-PBG_DEV float fast_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
+// (-DPBG_DEV_CHECKS) asserts it.  Measured on the device (tests/test_devmath_gpu.py, every exponent):
+// float rcp 0.88, sqrt 0.91, rsq 0.86 ulp over normal arguments; fast_rcp(double) gave the IEEE quotient's
+// bits, denormal reciprocals included.
+// v_rcp_f32 returns a zero where the reciprocal is a denormal float (|x| > 2^126): there, and only there,
+// the reciprocal of x / 4 (a normal float) is scaled back, which rounds once into the denormals (<= 0.94
+// ulp); every other argument keeps the single instruction's bits (+-inf still give +-0)
+PBG_DEV float fast_rcp(float x) {
+  const float r = __builtin_amdgcn_rcpf(x);
+  return r == 0.0f ? 0.25f * __builtin_amdgcn_rcpf(0.25f * x) : r;
+}
 PBG_DEV float fast_sqrt(float x) { return __builtin_amdgcn_sqrtf(x); }
 PBG_DEV float fast_rsq(float x) { return __builtin_amdgcn_rsqf(x); }
 // float64 reciprocal: v_rcp_f64 refined by two Newton steps (within 1 ulp of the IEEE quotient for
@@ -91,7 +99,9 @@ PBG_DEV double fast_rsq(double x) { return 1.0 / __builtin_sqrt(x); }
 template <class S>
 PBG_DEV S norm3(V3<S> a) { return fast_sqrt(dot3(a, a)); }
 // clamp(x, lo, hi) for lo <= hi in one v_med3_f32 (fminf(fmaxf()) costs two instructions
-// plus the IEEE canonicalisations of its operands); same result for non-NaN x
+// plus the IEEE canonicalisations of its operands); same result for non-NaN x.  Measured on the device
+// (tests/test_devmath_gpu.py): denormals pass through unflushed, clamp(-0, +0, +0) is +0, and a NaN x
+// never comes back as NaN -- float gives lo or hi, double gives lo
 template <class S>
 PBG_DEV S clampf(S x, nd<S> lo, nd<S> hi) {
   if constexpr (std::is_same<S, float>::value) return __builtin_amdgcn_fmed3f(x, lo, hi);
@@ -100,10 +110,18 @@ PBG_DEV S clampf(S x, nd<S> lo, nd<S> hi) {
 
 
 // sin/cos for the moderate arguments of the physics (joint angles, exp-map half angles):
-// 3-part Cody-Waite reduction by pi/2 + minimax polynomials on [-pi/4, pi/4], a few ulp
-// for |x| < 1e5.  Branch-free and short: the library sincosf carries a Payne-Hanek
-// large-argument path that, executed as selects, costs ~50 instructions per call.
-PBG_DEV void sincos_fast(float x, float* sp, float* cp) {
+// 3-part Cody-Waite reduction by pi/2 + minimax polynomials on [-pi/4, pi/4].  Branch-free and
+// short: the library sincosf carries a Payne-Hanek large-argument path that, executed as selects,
+// costs ~50 instructions per call.
+// Accuracy against float64 sin / cos, swept over every float in [0, 1e5] on the host: 1.24 ulp up to
+// pi/4, 1.55 ulp up to 3.2, 5.8 ulp up to 10; past that the RELATIVE error is unbounded in ulp near the
+// zeros of sin / cos (32,280 ulp up to 1e5: the three constants carry pi/2 to ~48 bits, times n), and the
+// contract the physics relies on is the ABSOLUTE error, 9.31e-8 over the whole range.
+// tests/test_devmath_host.py holds 1.7 ulp up to 3.2 and 1.03e-7 absolute up to 1e5 (10 % headroom for
+// the arguments its stride skips).  sin is odd and cos even bit for bit, except that sin(-0) = +0 (k = -0
+// makes r = +0); NaN and +-inf give NaN.  Every multiply-add is a spelled-out fma, so the host build
+// (pbg_devtest.hip) and the device agree bit for bit (tests/test_devmath_gpu.py).
+PBG_SC64_FN void sincos_fast(float x, float* sp, float* cp) {
   const float k = __builtin_rintf(x * 0.636619772367581343f);
   float r = __builtin_fmaf(-k, 1.5703125f, x);
   r = __builtin_fmaf(-k, 4.837512969970703125e-4f, r);
@@ -117,10 +135,14 @@ PBG_DEV void sincos_fast(float x, float* sp, float* cp) {
   *sp = (q & 2) ? -s0 : s0;
   *cp = ((q + 1) & 2) ? -c0 : c0;
 }
-// float64: Cody-Waite reduction + the msun minimax kernels (pbg_sincos64.h): within 0.8 ulp for
-// |x| <= 1e5, 1e-15 absolute to 1e6 (tests/test_sincos64.py), ~45 instructions and no branch, where the
-// device library's sincos takes ~150 with its Payne-Hanek path behind a branch (the physics' joint
-// angles and half-angle increments never need it; NaN and inf give NaN, as the library does)
+// float64: Cody-Waite reduction + the msun minimax kernels (pbg_sincos64.h): |err| <= 1 ulp +
+// (|n| + 1) 2^-87 with n = rint(x 2/pi) for |x| <= 1e5 (the second term is the reduction's: it dominates
+// next to a multiple of pi/2, where the result is tiny), 1e-15 absolute to 1e6 (tests/test_sincos64.py,
+// tests/test_devmath_host.py; the device build: tests/test_devmath_gpu.py), ~45 instructions and no
+// branch, where the device library's sincos takes ~150 with its Payne-Hanek path behind a branch (the
+// physics' joint angles and half-angle increments never need it).  NaN and inf give NaN, as the library
+// does; unlike the library, sin(-0) is +0, and huge finite arguments are not reduced: garbage from ~1e16,
+// NaN from 1e171 at the latest (pbg_sincos64.h).
 PBG_DEV void sincos_fast(double x, double* sp, double* cp) {
 #ifdef PBG_SC64_LIB  // diagnostic builds: the device library's sincos
   sincos(x, sp, cp);

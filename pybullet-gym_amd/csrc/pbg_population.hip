@@ -8,7 +8,7 @@
 // generation kernels (noise, perturb, grad, fitness, member copies) are written for the stated summation
 // order, not for speed.
 //
-// Same-bits rule: es_normals4 is the only place the device computes the noise; noise, perturb and grad
+// Same-bits rule: es_normals4 (pbg_es_noise.h) is the only place the device computes the noise; noise, perturb and grad
 // call it with the same counter and so see the same floats.  Every multiply-add in this file is either a
 // spelled-out fma or cannot be contracted (a product that feeds no add).
 #include <hip/hip_runtime.h>
@@ -21,6 +21,7 @@
 #include <new>
 
 #include "pbg_math.h"
+#include "pbg_es_noise.h"
 #include "pbg_policy_dev.h"
 
 struct pbg_population {
@@ -34,9 +35,8 @@ struct pbg_population {
 namespace {
 
 using namespace pbg::policy;
+using namespace pbg::es;  // es_box_muller, es_normals4, ES_TAG (pbg_es_noise.h)
 using pbg::DeviceGuard;
-
-constexpr uint32_t ES_TAG = 0xE5u;  // fourth counter word of the noise stream
 
 struct Dims {
   int obs_dim, h1, h2, act_dim;
@@ -44,31 +44,6 @@ struct Dims {
 
 __host__ __device__ inline int param_count(const Dims& d) {
   return d.obs_dim * d.h1 + d.h1 + d.h1 * d.h2 + d.h2 + d.h2 * d.act_dim + d.act_dim;
-}
-
-// ---------------------------------------------------------------- noise
-// Two normals from two Philox words (pbg.h "Noise contract").  u1 = (a >> 9 + 1/2) 2^-23 lies in (0, 1)
-// and is exact; -2 logf, 2 u2 and the two r * trig products feed no add.
-__device__ __forceinline__ void es_box_muller(uint32_t a, uint32_t b, float& n0, float& n1) {
-  const float u1 = __builtin_fmaf((float)(a >> 9), 0x1p-23f, 0x1p-24f);
-  const float u2 = (float)(b >> 8) * 0x1p-24f;
-  const float r = sqrtf(-2.0f * logf(u1));
-  const float t = 2.0f * u2;
-  n0 = r * cospif(t);
-  n1 = r * sinpif(t);
-}
-
-// The four normals of parameters 4 b .. 4 b + 3 of the global pair `pair` in `generation`.
-__device__ __forceinline__ void es_normals4(uint32_t k0, uint32_t k1, uint32_t b, uint32_t pair, uint32_t generation,
-                                            float e[4]) {
-  u4 c;
-  c.x = b;
-  c.y = pair;
-  c.z = generation;
-  c.w = ES_TAG;
-  const u4 x = philox4x32_10(c, k0, k1);
-  es_box_muller(x.x, x.y, e[0], e[1]);
-  es_box_muller(x.z, x.w, e[2], e[3]);
 }
 
 // grid (n_pairs, ceil(nb / 256)): a lane per (pair, block of 4 parameters)

@@ -3,10 +3,28 @@
 // costs ~150 VALU instructions per call (108 of them float64, half-rate); the physics' arguments are
 // joint angles and half-angle increments.  Here: Cody-Waite reduction by pi/2 (fdlibm's pio2_1 +
 // pio2_1t split, the reduced argument carried as a double-double), then the minimax kernels of FreeBSD
-// msun's k_sin.c / k_cos.c on [-pi/4, pi/4] (the published coefficients), ~45 instructions, no branch.  tests/test_sincos64.py checks the host build of this header against long-double
-// sinl / cosl: within 0.8 ulp for |x| <= 1e5 (the C library: 0.52) and 1e-15 absolute up to 1e6 (past
-// 1e5 a result near a zero of sin loses relative accuracy: the neglected part of pi/2 times n); the
-// float64 parity bound is 1e-9.  NaN / inf give NaN.
+// msun's k_sin.c / k_cos.c on [-pi/4, pi/4] (the published coefficients), ~45 instructions, no branch.
+//
+// Accuracy, for |x| <= 1e5 and n = rint(x 2/pi):   |err| <= 1 ulp(exact) + (|n| + 1) 2^-87.
+// The second term is the reduction's: pio2_1 + pio2_1t carry pi/2 to ~86 bits (2^-87 is half an ulp of
+// pio2_1t), so the reduced argument is off by up to that times n.  Away from the multiples of pi/2 it
+// vanishes under the first (random arguments: 0.77 ulp, the C library 0.52); next to one, where the result
+// is tiny, it is all of the error: x = fl(pi) gives sin = 1.224646799076922e-16 for 1.2246467991473532e-16,
+// 3e5 ulp, and over fl(n pi/2) and its neighbours up to 1e5 the relative error reaches 4e9 ulp while the
+// absolute one stays below 0.55 of the bound.  1e-15 absolute up to 1e6.  The float64 parity bound of the
+// physics is 1e-9.
+// The reduction's TwoProd / TwoSum lines are error-free only as written: contracted (hipcc's default on
+// the device), r = r1 - p and p + bb become fmas of n and pio2_1t, r is then the rounding of the exact
+// r1 - n pio2_1t and y subtracts pe a second time -- measured on an MI355X, 2.44 times the bound on the
+// directed arguments.  sincos_reduced64 therefore switches contraction off for its own body (the
+// polynomial kernels keep the build's setting); with it the device meets the bound like the host builds.
+// Special values: sin(-0) is +0 (n = -0 makes the reduced argument +0; the C library returns -0); NaN and
+// +-inf give NaN; the smallest denormal returns (x, 1).  Huge finite arguments get no Payne-Hanek
+// reduction: from about 1e16 (n no longer exact) the remainder is not reduced and the polynomials return
+// garbage of any magnitude (+-inf from ~1e40), and NaN once the remainder's square overflows (every
+// |x| >= 1e171; in practice from ~1e120).  The physics stays below 1e5.
+// tests/test_sincos64.py and tests/test_devmath_host.py check the host build (with mpmath on the directed
+// arguments next to n pi/2), tests/test_devmath_gpu.py the device build under the product's flags.
 // Plain C++ (no HIP types), so the host test compiles it with g++.
 #pragma once
 
@@ -33,6 +51,9 @@ PBG_SC64_FN void sincos_kernel64(double r, double y, double* sp, double* cp) {
 // __ieee754_rem_pio2 medium case with FMAs: n pio2_1 is exact, the product n pio2_1t and the
 // subtraction are carried exactly by TwoProd / TwoSum), then the quadrant
 PBG_SC64_FN void sincos_reduced64(double x, double* sp, double* cp) {
+#if defined(__clang__)
+#pragma clang fp contract(off)  // p, r, bb, y below must round exactly as written (header comment)
+#endif
   const double n = __builtin_rint(x * 6.36619772367581382433e-01);  // 2 / pi
   const double r1 = __builtin_fma(-n, 1.57079632673412561417e+00, x);  // pio2_1: pi/2, first 33 bits
   const double p = n * 6.07710050650619224932e-11;                     // pio2_1t = pi/2 - pio2_1

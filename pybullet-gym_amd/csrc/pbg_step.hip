@@ -25,6 +25,7 @@
 
 #include "models_gen.h"
 #include "pbg_math.h"
+#include "pbg_lanes.h"
 #include "pbg_records.h"
 #include "pbg_types.h"
 #include "sim_params.h"
@@ -1407,16 +1408,6 @@ struct PackOut {
 
 // robot_locomotors.py:31-64 calc_state + gym_locomotion_envs.py:59-114 reward/done.
 // GEN: any part count (golden-vector pack_kernel); otherwise the step's NP or NP + 1 parts.
-// Broadcast lane K of each DPP quad (a float64 as two dword moves).
-template <int K>
-PBG_DEV double quad_bcast_f64(double x) {
-  constexpr int CTRL = K * 85;  // quad_perm [K, K, K, K]
-  const uint64_t u = __builtin_bit_cast(uint64_t, x);
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_mov_dpp((int)(uint32_t)u, CTRL, 0xF, 0xF, true);
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_mov_dpp((int)(uint32_t)(u >> 32), CTRL, 0xF, 0xF, true);
-  return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
-}
-
 // Q = 4: the four lanes of each DPP quad hold the same env and identical inputs (quad and
 // gang kernels); the float64 transcendentals are dealt over them -- lane 0 roll, 1 pitch,
 // 2 yaw, 3 target angle (atan2 / asin), then lanes 0-1 sin/cos(-yaw) and 2-3 sin/cos(ang)

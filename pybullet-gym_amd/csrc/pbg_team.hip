@@ -22,44 +22,7 @@
 
 namespace pbg {
 
-// ------------------------------------------------------------------ quad (DPP) helpers
-// bound_ctrl set: every permutation used here reads a valid lane, and with it the
-// compiler folds `x + mov_dpp(x)` into one v_add_f32_dpp (no mov, no DPP hazard nop).
-template <int CTRL>
-PBG_DEV float qperm(float x) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, x), CTRL, 0xF, 0xF, true));
-}
-template <int CTRL>
-PBG_DEV int qperm_i(int x) {
-  return __builtin_amdgcn_mov_dpp(x, CTRL, 0xF, 0xF, true);
-}
-// sum over the quad; identical bits in all four lanes ((x0+x1)+(x2+x3), addition commutes)
-PBG_DEV float quad_sum(float x) {
-  x = x + qperm<0xB1>(x);  // quad_perm [1,0,3,2]
-  return x + qperm<0x4E>(x);  // quad_perm [2,3,0,1]
-}
-PBG_DEV int quad_sum_i(int x) {
-  x = x + qperm_i<0xB1>(x);
-  return x + qperm_i<0x4E>(x);
-}
-template <int K>
-PBG_DEV float quad_bcast(float x) { return qperm<K | (K << 2) | (K << 4) | (K << 6)>(x); }
-template <int K>
-PBG_DEV int quad_bcast_i(int x) { return qperm_i<K | (K << 2) | (K << 4) | (K << 6)>(x); }
-// float64 (F64<R>: the reference-precision path): a double moves as its two dwords
-template <int CTRL>
-PBG_DEV double qperm(double x) {
-  const uint64_t u = __builtin_bit_cast(uint64_t, x);
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_mov_dpp((int)(uint32_t)u, CTRL, 0xF, 0xF, true);
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_mov_dpp((int)(uint32_t)(u >> 32), CTRL, 0xF, 0xF, true);
-  return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
-}
-PBG_DEV double quad_sum(double x) {
-  x = x + qperm<0xB1>(x);
-  return x + qperm<0x4E>(x);
-}
-template <int K>
-PBG_DEV double quad_bcast(double x) { return qperm<K | (K << 2) | (K << 4) | (K << 6)>(x); }
+// the quad (DPP) helpers -- qperm, quad_sum, quad_bcast -- live in pbg_lanes.h
 // LDS written by one lane and read by another lane of the same wave: a compiler fence
 // (the wave's LDS operations execute in order).
 #define PBG_QUAD_SYNC                                    \

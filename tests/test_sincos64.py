@@ -6,12 +6,20 @@ test compiles it with g++ and measures the error against long-double sinl / cosl
 random arguments in ranges from 1e-8 to 1e6, next to the C library's own error.  Bound: 1 ulp for
 |x| <= 1e5 (the joint angles and half-angle increments of the physics are far smaller), and 1e-15
 absolute in every range.  The float64 parity tests hold the state to 1e-9 relative, ~1e7 ulp.
+
+Random arguments never land next to a multiple of pi/2, where the reduction's error (pi/2 carried to ~86
+bits, times n) is all of the result's: the second test feeds the same g++ builds the directed arguments
+fl(n pi/2) and neighbours (tests/devmath.py) and holds them to the header's contract,
+|err| <= 1 ulp + (|n| + 1) 2^-87, against mpmath.
 """
 import os
 import shutil
 import subprocess
 
+import numpy as np
 import pytest
+
+import devmath as dm
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(os.path.dirname(HERE), "pybullet-gym_amd", "csrc")
@@ -65,3 +73,50 @@ def test_sincos64_within_one_ulp(tmp_path):
         assert ma <= 1e-15, (R, ma)  # absolute, every range (near a zero of sin at |x| ~ 1e6 the
         # relative error of a ~1e-12 result can reach 1e-9: the neglected part of pi/2 times n)
     assert [l for l in out if l.startswith("nan")] == ["nan 1 1"]
+
+
+DIRECTED = r'''
+#include <cstdio>
+#include <vector>
+#include "pbg_sincos64.h"
+int main(int argc, char** argv) {  // argv[1]: doubles in, argv[2]: (sin, cos) pairs out
+  if (argc != 3) return 2;
+  FILE* f = fopen(argv[1], "rb");
+  if (!f) return 3;
+  std::vector<double> x, o;
+  double v;
+  while (fread(&v, sizeof v, 1, f) == 1) x.push_back(v);
+  fclose(f);
+  o.resize(2 * x.size());
+  for (size_t i = 0; i < x.size(); i++) pbg::sincos_reduced64(x[i], &o[2 * i], &o[2 * i + 1]);
+  f = fopen(argv[2], "wb");
+  if (!f || fwrite(o.data(), sizeof(double), o.size(), f) != o.size()) return 4;
+  return fclose(f) ? 5 : 0;
+}
+'''
+
+
+def _cpu_has_fma():
+    try:
+        with open("/proc/cpuinfo") as f:
+            return any(l.startswith("flags") and " fma " in l + " " for l in f)
+    except OSError:
+        return False
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
+def test_sincos64_directed_arguments_within_the_contract(tmp_path):
+    """fl(n pi/2) and neighbours (|n| <= 4,096, every 16th n to 63,662) through the g++ build, and through
+    the contracted one (-mfma -ffp-contract=fast: other output bits) where the CPU has fma."""
+    src = tmp_path / "d.cpp"
+    src.write_text(DIRECTED)
+    x = dm.directed64()[0]
+    (tmp_path / "x.bin").write_bytes(x.tobytes())
+    builds = [("g++", [])] + ([("g++ contracted", ["-mfma", "-ffp-contract=fast"])] if _cpu_has_fma() else [])
+    for label, flags in builds:
+        exe = tmp_path / "d"
+        subprocess.check_call(["g++", "-O2", "-std=c++17", *flags, "-I", CSRC, "-o", str(exe), str(src)])
+        subprocess.check_call([str(exe), str(tmp_path / "x.bin"), str(tmp_path / "o.bin")])
+        o = np.fromfile(tmp_path / "o.bin", np.float64).reshape(-1, 2)
+        assert o.shape[0] == x.size
+        dm.check_directed64(o[:, 0].copy(), o[:, 1].copy(), label)
