@@ -384,6 +384,77 @@ int pbg_population_fitness(const pbg_population* p, int n, const double* cur_ret
 int pbg_population_grad(const pbg_population* p, const float* w, uint64_t seed, uint32_t generation, float* g_out,
                         void* stream);
 
+/* ---- Running observation normalisation (appended; nothing above changes) ----
+ * The evolution-strategy recipe (Salimans et al. 2017; Mania et al. 2018 "state normalisation") keeps the
+ * running per-component mean and variance of every observation the population visits and feeds each policy
+ *   clip((obs - mean) / std, -clip, clip)
+ * instead of obs.  The observations of a rollout never leave the two-launch loop, so the statistics are
+ * gathered inside the actor kernels, where the tile's observations already sit in LDS, and the
+ * normalisation is applied there too.
+ *
+ * A pbg_obs_stats lives on one device and holds, for K = obs_dim,
+ *   totals  float64 [1 + 2 K] = count, sum[K], sumsq[K]; initially OpenAI ES's RunningStat(eps = 1e-2):
+ *           count = 1e-2, sum = 0, sumsq = 1e-2;
+ *   n_slots partial accumulators: slot_count int64, slot_sum[K], slot_sumsq[K] float64, initially zero.
+ * One slot belongs to one workgroup of a launch (a tile of at most 16 rows), so nothing is atomic and the
+ * order of every sum is stated:
+ *
+ * Tile accumulation (one device function, shared by both actors and pbg_obs_stats_update).  A row of the
+ * tile counts when it is active and finite (no NaN or inf component).  For component k the tile's counted
+ * rows are added in ascending row order straight onto the slot's running values,
+ *   slot_sum[k] += (double)x;  slot_sumsq[k] += (double)x * (double)x;
+ * (the product of two float32 values is exact in float64, so a contraction into an fma changes no bit),
+ * and slot_count grows by the number of counted rows.  Over several launches a slot therefore sums in the
+ * order (launch ascending, row-in-tile ascending). */
+typedef struct pbg_obs_stats pbg_obs_stats;
+
+/* PBG_E_ARG (before any HIP call) for obs_dim outside pbg_policy_create's 1..256, n_slots < 1 or
+ * device < 0; PBG_E_HIP for a device that does not exist.  *out is NULL after every failure. */
+int pbg_obs_stats_create(int device, int obs_dim, int n_slots, pbg_obs_stats** out);
+/* Detach it from every actor first (pbg_*_attach_obs_stats with NULL): the actors keep only the pointer. */
+void pbg_obs_stats_destroy(pbg_obs_stats* s);
+/* One launch over obs (DEVICE [n, K] float32); active: DEVICE [n] uint8 (0 = skip the row), NULL = every
+ * row active.  group = G > 0: the rows are n / G groups of G consecutive rows and the tiles are cut per
+ * group exactly as pbg_population_act cuts them, tile t of group m is workgroup (and slot)
+ * m ceil(G / 16) + t; group = 0: one group of n rows, pbg_policy_act's tiling.  PBG_E_ARG when n is no
+ * multiple of group or the launch needs more slots than the object has. */
+int pbg_obs_stats_update(pbg_obs_stats* s, int n, int group, const float* obs, const uint8_t* active, void* stream);
+/* Folds the slots into the totals and zeroes them: for each k sum[k] and sumsq[k] take the slots' values
+ * by slot-ascending sequential float64 adds; the int64 slot counts are summed exactly and added to count
+ * as one float64.  Then, into the nullable DEVICE float32 [K] outputs,
+ *   mean[k]    = (float)(sum[k] / count)
+ *   inv_std[k] = (float)(1 / sqrt(max(sumsq[k] / count - m m, 1e-2)))   with m = sum[k] / count,
+ * all in float64 and nothing contracted; the variance floor bounds inv_std by 10. */
+int pbg_obs_stats_finalize(pbg_obs_stats* s, float* mean_out, float* inv_std_out, void* stream);
+/* The totals as DEVICE float64 [1 + 2 K] (count, sum, sumsq), copied on `stream`: to resume a run, or to
+ * merge the statistics of several shards by adding their totals. */
+int pbg_obs_stats_get_totals(const pbg_obs_stats* s, double* totals_out, void* stream);
+int pbg_obs_stats_set_totals(pbg_obs_stats* s, const double* totals, void* stream);
+
+/* The normaliser of an actor.  With one set, every path that evaluates the MLP (pbg_policy_act,
+ * pbg_policy_act_host, pbg_population_act, pbg_rollout, pbg_rollout_population) feeds the first layer
+ *   v = (x - mean[k]) * inv_std[k];  xn = v < -clip ? -clip : (v > clip ? clip : v)
+ * instead of x: one float32 rounding for the subtraction, one for the multiply, a NaN passes through;
+ * host and device agree bit for bit.  obs_traj keeps the raw observation.  With none set every path
+ * computes exactly what it computed before normalisers existed.
+ * pbg_policy_set_obs_norm: HOST float32 [obs_dim] arrays, copied (host-only policies too); for a device
+ * policy it waits for the device first, so that no launch already enqueued sees half of the new arrays.
+ * pbg_population_set_obs_norm: DEVICE float32 [obs_dim] arrays, copied on `stream` into the population's
+ * own buffers (no host work: a training loop sets a new normaliser every generation).
+ * Both arrays NULL: the normaliser is switched off.  PBG_E_ARG for one NULL array or a clip that is not > 0. */
+int pbg_policy_set_obs_norm(pbg_policy* p, const float* mean, const float* inv_std, float clip);
+int pbg_population_set_obs_norm(pbg_population* p, const float* mean, const float* inv_std, float clip, void* stream);
+
+/* Attach statistics to an actor (NULL detaches).  While attached, every step of pbg_rollout /
+ * pbg_rollout_population with that actor accumulates its tiles' raw observations, workgroup b into slot b,
+ * inside the actor launch (a rollout stays 2 T + 1 launches).  A row is active when the action computed
+ * from it will be booked: autoreset != 0, or done_episodes[e] == 0 after the previous step's bookkeeping.
+ * The plain *_act calls never collect.  The rollout returns PBG_E_ARG when the attached object is on
+ * another device, has another obs_dim, or has fewer slots than the actor launch has workgroups
+ * (ceil(n / 16), for a population P ceil(G / 16)). */
+int pbg_policy_attach_obs_stats(pbg_policy* p, pbg_obs_stats* s);
+int pbg_population_attach_obs_stats(pbg_population* p, pbg_obs_stats* s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -145,6 +145,22 @@ def lib():
         for f in POPULATION_EXPORTED:
             if f != "pbg_population_destroy":
                 getattr(L, f).restype = I
+    if hasattr(L, "pbg_obs_stats_create"):  # running observation normalisation
+        F = ctypes.c_float
+        L.pbg_obs_stats_create.argtypes = [I, I, I, ctypes.POINTER(H)]
+        L.pbg_obs_stats_destroy.argtypes = [H]
+        L.pbg_obs_stats_destroy.restype = None
+        L.pbg_obs_stats_update.argtypes = [H, I, I, P, P, P]
+        L.pbg_obs_stats_finalize.argtypes = [H, P, P, P]
+        L.pbg_obs_stats_get_totals.argtypes = [H, P, P]
+        L.pbg_obs_stats_set_totals.argtypes = [H, P, P]
+        L.pbg_policy_set_obs_norm.argtypes = [H, P, P, F]
+        L.pbg_population_set_obs_norm.argtypes = [H, P, P, F, P]
+        L.pbg_policy_attach_obs_stats.argtypes = [H, H]
+        L.pbg_population_attach_obs_stats.argtypes = [H, H]
+        for f in OBS_NORM_EXPORTED:
+            if f != "pbg_obs_stats_destroy":
+                getattr(L, f).restype = I
     for f in ("pbg_info", "pbg_reset", "pbg_step", "pbg_step_ex", "pbg_get_state", "pbg_set_state",
               "pbg_pack_record_sizes", "pbg_pack", "pbg_create_debug", "pbg_sample_actions", "pbg_create_ex",
               "pbg_default_sim_params", "pbg_get_sim_params", "pbg_create_v2", "pbg_precision"):
@@ -162,7 +178,15 @@ EXPORTED = ("pbg_create", "pbg_create_debug", "pbg_create_ex", "pbg_create_v2", 
             "pbg_population_create", "pbg_population_destroy", "pbg_population_noise",
             "pbg_population_noise_host", "pbg_population_perturb", "pbg_population_set_member",
             "pbg_population_get_member", "pbg_population_act", "pbg_rollout_population",
-            "pbg_population_fitness", "pbg_population_grad")
+            "pbg_population_fitness", "pbg_population_grad",
+            "pbg_obs_stats_create", "pbg_obs_stats_destroy", "pbg_obs_stats_update", "pbg_obs_stats_finalize",
+            "pbg_obs_stats_get_totals", "pbg_obs_stats_set_totals", "pbg_policy_set_obs_norm",
+            "pbg_population_set_obs_norm", "pbg_policy_attach_obs_stats", "pbg_population_attach_obs_stats")
+
+
+OBS_NORM_EXPORTED = ("pbg_obs_stats_create", "pbg_obs_stats_destroy", "pbg_obs_stats_update", "pbg_obs_stats_finalize",
+                     "pbg_obs_stats_get_totals", "pbg_obs_stats_set_totals", "pbg_policy_set_obs_norm",
+                     "pbg_population_set_obs_norm", "pbg_policy_attach_obs_stats", "pbg_population_attach_obs_stats")
 
 
 POPULATION_EXPORTED = ("pbg_population_create", "pbg_population_destroy", "pbg_population_noise",

@@ -26,13 +26,17 @@ __global__ __launch_bounds__(256) void book_kernel(Book b, int n) {
 
 // act[n, act_dim] = pi(obs[n, obs_dim]); optional copies of both into the rollout's trajectories; the
 // bookkeeping of the previous env step (bk.rew64 != NULL) for the tile's envs comes first.
-__global__ __launch_bounds__(PB) void policy_act_kernel(Weights P, int n, const float* __restrict__ obs,
+// nm: the policy's normaliser (mean NULL: none); st: slot 0 of the statistics to collect into (sum NULL:
+// none), workgroup b adds to slot b; MODE (pbg_policy_dev.h) says which of the two the instantiation looks at.
+template <int MODE>
+__global__ __launch_bounds__(PB) void policy_act_kernel(Weights P, Norm nm, Slot st, int n, const float* __restrict__ obs,
                                                         float* __restrict__ act, float* __restrict__ obs_traj,
                                                         float* __restrict__ act_traj, Book bk) {
   __shared__ __attribute__((aligned(16))) float bufA[PD * PT];
   __shared__ __attribute__((aligned(16))) float bufB[PD * PT];
   const int env0 = blockIdx.x * PT;
-  act_tile(P, env0, min(PT, n - env0), obs, act, obs_traj, act_traj, bk, bufA, bufB);  // rows >= 1: the grid is ceil(n / PT)
+  act_tile<MODE>(P, nm, slot_at(st, P.obs_dim, blockIdx.x), env0, min(PT, n - env0), obs, act, obs_traj, act_traj, bk, bufA,
+           bufB);  // rows >= 1: the grid is ceil(n / PT)
 }
 
 }  // namespace
@@ -43,6 +47,13 @@ struct pbg_policy {
   size_t off[6], words;  // w1 b1 w2 b2 w3 b3 inside one array
   float* host;
   float* dev;
+  // the normaliser (pbg_policy_set_obs_norm): mean [obs_dim] then inv_std [obs_dim], on the host and, for a
+  // device policy, on the device; norm_on 0 = none
+  float* norm_host;
+  float* norm_dev;
+  float clip;
+  int norm_on;
+  pbg_obs_stats* stats;  // attached (pbg_policy_attach_obs_stats), not owned
 };
 
 namespace {
@@ -52,17 +63,35 @@ Weights weights_at(const pbg_policy* p, const float* base) {
                  base + p->off[5], p->obs_dim, p->h1, p->h2, p->act_dim};
 }
 
+Norm norm_at(const pbg_policy* p, const float* base) {
+  if (!p->norm_on) return Norm{nullptr, nullptr, 0.f};
+  return Norm{base, base + p->obs_dim, p->clip};
+}
+
 int launch_act(const pbg_policy* p, int n, const float* obs, float* act, float* obs_traj, float* act_traj,
-               const Book& bk, hipStream_t stream) {
+               const Book& bk, bool collect, hipStream_t stream) {
   const unsigned grid = (unsigned)((n + PT - 1) / PT);
-  hipLaunchKernelGGL(policy_act_kernel, dim3(grid), dim3(PB), 0, stream, weights_at(p, p->dev), n, obs, act, obs_traj,
-                     act_traj, bk);
+  const Slot st = collect && p->stats ? p->stats->slot0() : Slot{nullptr, nullptr, nullptr};
+  const Norm nm = norm_at(p, p->norm_dev);
+  const Weights W = weights_at(p, p->dev);
+  switch (mode_of(nm, st)) {
+    case PLAIN:
+      hipLaunchKernelGGL(policy_act_kernel<PLAIN>, dim3(grid), dim3(PB), 0, stream, W, nm, st, n, obs, act, obs_traj, act_traj, bk);
+      break;
+    case NORM:
+      hipLaunchKernelGGL(policy_act_kernel<NORM>, dim3(grid), dim3(PB), 0, stream, W, nm, st, n, obs, act, obs_traj, act_traj, bk);
+      break;
+    case COLLECT:
+      hipLaunchKernelGGL(policy_act_kernel<COLLECT>, dim3(grid), dim3(PB), 0, stream, W, nm, st, n, obs, act, obs_traj, act_traj,
+                         bk);
+      break;
+  }
   return (int)hipGetLastError();
 }
 
 int act_of_policy(const void* actor, int n, const float* obs, float* act, float* obs_traj, float* act_traj,
-                  const Book& bk, hipStream_t stream) {
-  return launch_act(static_cast<const pbg_policy*>(actor), n, obs, act, obs_traj, act_traj, bk, stream);
+                  const Book& bk, bool collect, hipStream_t stream) {
+  return launch_act(static_cast<const pbg_policy*>(actor), n, obs, act, obs_traj, act_traj, bk, collect, stream);
 }
 
 int hip_fail(int e, const char* what) {
@@ -116,6 +145,10 @@ int pbg_policy_create(int device, int obs_dim, int h1, int h2, int act_dim, cons
   }
   p->words = at;
   p->dev = nullptr;
+  p->norm_host = p->norm_dev = nullptr;
+  p->clip = 0.f;
+  p->norm_on = 0;
+  p->stats = nullptr;
   p->host = (float*)calloc(at, sizeof(float));
   if (!p->host) {
     delete p;
@@ -149,16 +182,66 @@ void pbg_policy_destroy(pbg_policy* p) {
     DeviceGuard dg(p->device);
     (void)hipFree(p->dev);
   }
+  if (p->norm_dev) {
+    DeviceGuard dg(p->device);
+    (void)hipFree(p->norm_dev);
+  }
+  free(p->norm_host);
   free(p->host);
   delete p;
+}
+
+int pbg_policy_set_obs_norm(pbg_policy* p, const float* mean, const float* inv_std, float clip) {
+  if (!p) return pbg::capi_fail(PBG_E_ARG, "pbg_policy_set_obs_norm: policy is NULL");
+  if (!mean && !inv_std) {
+    p->norm_on = 0;
+    return PBG_OK;
+  }
+  if (!mean || !inv_std) return pbg::capi_fail(PBG_E_ARG, "pbg_policy_set_obs_norm: mean and inv_std must both be given (or both NULL)");
+  if (!(clip > 0.f)) return pbg::capi_fail(PBG_E_ARG, "pbg_policy_set_obs_norm: clip must be > 0");
+  const size_t K = (size_t)p->obs_dim;
+  if (!p->norm_host) {
+    p->norm_host = (float*)calloc(2 * K, sizeof(float));
+    if (!p->norm_host) return pbg::capi_fail(PBG_E_NOMEM, "pbg_policy_set_obs_norm: out of host memory");
+  }
+  if (p->device >= 0) {
+    // a launch enqueued earlier may still read the device copy: upload through the (synchronous) null-stream
+    // copy into place only after every stream of the device has drained
+    DeviceGuard dg(p->device);
+    int e = p->norm_dev ? 0 : (int)hipMalloc(&p->norm_dev, 2 * K * sizeof(float));
+    if (!e) e = (int)hipDeviceSynchronize();
+    if (!e) e = (int)hipMemcpy(p->norm_dev, mean, K * sizeof(float), hipMemcpyHostToDevice);
+    if (!e) e = (int)hipMemcpy(p->norm_dev + K, inv_std, K * sizeof(float), hipMemcpyHostToDevice);
+    if (e) {
+      p->norm_on = 0;
+      return hip_fail(e, "pbg_policy_set_obs_norm: upload");
+    }
+  }
+  memcpy(p->norm_host, mean, K * sizeof(float));
+  memcpy(p->norm_host + K, inv_std, K * sizeof(float));
+  p->clip = clip;
+  p->norm_on = 1;
+  return PBG_OK;
+}
+
+int pbg_policy_attach_obs_stats(pbg_policy* p, pbg_obs_stats* s) {
+  if (!p) return pbg::capi_fail(PBG_E_ARG, "pbg_policy_attach_obs_stats: policy is NULL");
+  p->stats = s;
+  return PBG_OK;
 }
 
 int pbg_policy_act_host(const pbg_policy* p, int n, const float* obs, float* act) {
   if (!p || n < 0 || (n > 0 && (!obs || !act))) return pbg::capi_fail(PBG_E_ARG, "pbg_policy_act_host: bad arguments");
   const Weights P = weights_at(p, p->host);
+  const Norm nm = norm_at(p, p->norm_host);
   float a[PBG_POLICY_MAX_DIM], b[PBG_POLICY_MAX_DIM];
   for (int i = 0; i < n; i++) {
-    host_layer(P.w1, P.b1, P.obs_dim, P.h1, true, obs + (size_t)i * P.obs_dim, a);
+    const float* x = obs + (size_t)i * P.obs_dim;
+    if (nm.mean) {
+      for (int k = 0; k < P.obs_dim; k++) b[k] = normalise(x[k], nm.mean[k], nm.inv_std[k], nm.clip);
+      x = b;
+    }
+    host_layer(P.w1, P.b1, P.obs_dim, P.h1, true, x, a);
     host_layer(P.w2, P.b2, P.h1, P.h2, true, a, b);
     host_layer(P.w3, P.b3, P.h2, P.act_dim, false, b, act + (size_t)i * P.act_dim);
   }
@@ -174,20 +257,21 @@ int pbg_policy_act(const pbg_policy* p, int n, const float* obs, float* act, voi
   DeviceGuard dg(p->device);
   Book none;
   memset(&none, 0, sizeof(none));
-  const int e = launch_act(p, n, obs, act, nullptr, nullptr, none, (hipStream_t)stream);
+  const int e = launch_act(p, n, obs, act, nullptr, nullptr, none, false, (hipStream_t)stream);
   return e ? hip_fail(e, "policy_act_kernel launch") : PBG_OK;
 }
 
 int pbg_rollout(pbg_handle* h, const pbg_policy* p, const pbg_rollout_io_t* uio, void* stream) {
   if (!h || !p || !uio) return pbg::capi_fail(PBG_E_ARG, "pbg_rollout: NULL handle, policy or io");
   if (p->device < 0 || !p->dev) return pbg::capi_fail(PBG_E_ARG, "pbg_rollout: host-only policy");
-  return rollout_loop("pbg_rollout", h, uio, stream, p->device, p->obs_dim, p->act_dim, 1, act_of_policy, p);
+  return rollout_loop("pbg_rollout", h, uio, stream, p->device, p->obs_dim, p->act_dim, 1, act_of_policy, p, p->stats);
 }
 
 }  // extern "C"
 
 int pbg::policy::rollout_loop(const char* who, pbg_handle* h, const pbg_rollout_io_t* uio, void* stream, int actor_device,
-                              int obs_dim, int act_dim, int group, ActLaunch launch, const void* actor) {
+                              int obs_dim, int act_dim, int group, ActLaunch launch, const void* actor,
+                              const pbg_obs_stats* stats) {
   char msg[200];
   // versioned like pbg_create_opts_t: the first version ends with done_traj; read only what the caller's
   // struct holds, fields appended later take zero (their default) for an older caller
@@ -217,6 +301,14 @@ int pbg::policy::rollout_loop(const char* who, pbg_handle* h, const pbg_rollout_
              info.n_envs, group);
     return pbg::capi_fail(PBG_E_ARG, msg);
   }
+  if (stats) {
+    const long long need = tiles_of(info.n_envs, info.n_envs / (group > 1 ? group : 1));
+    if (stats->device != dev || stats->obs_dim != obs_dim || (long long)stats->n_slots < need) {
+      snprintf(msg, sizeof(msg), "%s: the attached obs stats (device %d, obs_dim %d, %d slots) do not fit device %d, obs_dim "
+               "%d and the actor's %lld workgroups", who, stats->device, stats->obs_dim, stats->n_slots, dev, obs_dim, need);
+      return pbg::capi_fail(PBG_E_ARG, msg);
+    }
+  }
   if (io->n_steps < 1) {
     snprintf(msg, sizeof(msg), "%s: n_steps must be >= 1", who);
     return pbg::capi_fail(PBG_E_ARG, msg);
@@ -241,7 +333,7 @@ int pbg::policy::rollout_loop(const char* who, pbg_handle* h, const pbg_rollout_
   for (int t = 0; t < io->n_steps; t++) {
     // actor: the bookkeeping of step t - 1, then act = pi(obs)
     int e = launch(actor, n, io->obs, io->act, io->obs_traj ? io->obs_traj + (size_t)t * no : nullptr,
-                   io->act_traj ? io->act_traj + (size_t)t * na : nullptr, bk, s);
+                   io->act_traj ? io->act_traj + (size_t)t * na : nullptr, bk, stats != nullptr, s);
     if (e) return hip_fail(e, "actor kernel launch");
     // the step writes reward and done straight into the trajectory rows when there are any
     st.rew = io->rew_traj ? io->rew_traj + (size_t)t * n : io->rew;

@@ -14,6 +14,10 @@
 // x[k][e0 .. e0 + EL) are wave-uniform float4 LDS broadcasts.  A layer of H <= 64 columns splits the
 // 16 envs over the four waves (EL = 4), H <= 128 over two wave pairs (EL = 8), wider layers give
 // every lane all 16: no wave idles through a narrow layer.
+//
+// Observation normalisation and statistics (pbg.h "Running observation normalisation", DESIGN.md section
+// 12): normalise() is the one spelling of the transform, host and device; stats_tile() the one spelling of
+// the tile accumulation, used by both actors and by pbg_obsnorm.hip's stand-alone kernel.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -62,6 +66,94 @@ struct Weights {
   const float *w1, *b1, *w2, *b2, *w3, *b3;
   int obs_dim, h1, h2, act_dim;
 };
+
+// an actor's normaliser: mean, inv_std [obs_dim] (device pointers in a kernel); mean NULL = none
+struct Norm {
+  const float* mean;
+  const float* inv_std;
+  float clip;
+};
+
+// pbg.h's transform: a subtraction and a multiply, one float32 rounding each (the subtraction feeds the
+// multiply, so there is nothing to contract), then the clamp as two comparisons: a NaN passes through
+__host__ __device__ __forceinline__ float normalise(float x, float mean, float inv_std, float clip) {
+  const float d = x - mean;
+  const float v = d * inv_std;
+  return v < -clip ? -clip : (v > clip ? clip : v);
+}
+
+// one workgroup's slot of a pbg_obs_stats (sum NULL = nothing is collected)
+struct Slot {
+  int64_t* count;
+  double* sum;    // [K]
+  double* sumsq;  // [K]
+};
+
+// slot b of the object whose slot 0 is `base` (K = obs_dim)
+__host__ __device__ __forceinline__ Slot slot_at(const Slot base, int K, unsigned b) {
+  if (!base.sum) return base;
+  return Slot{base.count + b, base.sum + (size_t)b * K, base.sumsq + (size_t)b * K};
+}
+
+// The flags of a tile while statistics are collected, PT ints each: [0] the row is active, [1 + w] wave w
+// of the workgroup met a non-finite component of the row while loading it.  A flag plane per wave needs no
+// zeroing barrier: a wave's LDS stores retire in program order, so its lanes 0 .. PT - 1 clear the wave's
+// plane and the loads that follow in the same wave set it.  The flags live at the start of the
+// workgroup's second LDS plane, which is idle until the first layer writes it.
+constexpr int WAVE = 64;  // gfx950
+constexpr int FLAG_WORDS = PT * (1 + PB / WAVE);
+static_assert(FLAG_WORDS <= PD * PT, "the flags fit the idle plane");
+
+__device__ __forceinline__ bool finite_bits(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
+
+// The tile's observations (rows * K0 contiguous floats from row env0) -> xT [K0][PT], zero past `rows`,
+// with a copy into obs_traj (nullable) of what was read.  nm.mean != NULL: the normalised value is stored.
+// fl != NULL: the per-wave non-finite flags are written (the caller has written the active flags fl[0 .. PT)).
+__device__ __forceinline__ void load_tile(int K0, int env0, int rows, const float* __restrict__ obs,
+                                          float* __restrict__ obs_traj, const Norm nm, float* xT, int* fl) {
+  const int tid = threadIdx.x;
+  int* nf = fl ? fl + PT * (1 + tid / WAVE) : nullptr;
+  if (nf && (tid & (WAVE - 1)) < PT) nf[tid & (WAVE - 1)] = 0;
+  for (int i = tid; i < PT * K0; i += PB) {
+    const int e = i / K0, k = i - e * K0;
+    float v = 0.f;
+    if (e < rows) {
+      const size_t at = (size_t)env0 * K0 + i;
+      v = obs[at];
+      if (obs_traj) obs_traj[at] = v;
+      if (nf && !finite_bits(v)) nf[e] = 1;
+      if (nm.mean) v = normalise(v, nm.mean[k], nm.inv_std[k], nm.clip);
+    }
+    xT[k * PT + e] = v;
+  }
+}
+
+// pbg.h's tile accumulation: lane k < K walks the PT rows of its column of the raw tile xT [K][PT] in
+// ascending order and adds every counted (active and finite) row straight onto the slot's running values;
+// lane 0 also adds the number of counted rows.  Call between the barrier after load_tile and the next one.
+__device__ __forceinline__ void stats_tile(const Slot s, int K, const float* xT, const int* fl) {
+  const int tid = threadIdx.x;
+  if (tid >= K) return;
+  unsigned counted = 0;
+#pragma unroll
+  for (int e = 0; e < PT; e++) {
+    int bad = 0;
+#pragma unroll
+    for (int w = 0; w < PB / WAVE; w++) bad |= fl[PT * (1 + w) + e];
+    counted |= (fl[e] != 0 && bad == 0 ? 1u : 0u) << e;
+  }
+  double a = s.sum[tid], q = s.sumsq[tid];
+#pragma unroll
+  for (int e = 0; e < PT; e++)
+    if ((counted >> e) & 1u) {
+      const double x = (double)xT[tid * PT + e];
+      a += x;
+      q += x * x;  // exact product: the same bits contracted or not
+    }
+  s.sum[tid] = a;
+  s.sumsq[tid] = q;
+  if (tid == 0) *s.count += (int64_t)__popc(counted);
+}
 
 // One layer for this lane's column j and envs e0 .. e0 + EL of the tile: xT [K][PT] -> yT [H][PT], both LDS.
 template <int EL>
@@ -115,26 +207,41 @@ __device__ __forceinline__ void layer(const float* __restrict__ W, const float* 
 }
 
 // One workgroup's tile: envs env0 .. env0 + rows (1 <= rows <= PT) with the weights P.
-// act[e] = pi(obs[e]); optional copies of both into the rollout's trajectories; the bookkeeping of the
-// previous env step (bk.rew64 != NULL) for the tile's envs comes first.  Rows past `rows` are zero-filled
-// in LDS and neither read from nor written to memory.  bufA / bufB: the workgroup's two [PD][PT] LDS planes.
-__device__ __forceinline__ void act_tile(const Weights P, int env0, int rows, const float* __restrict__ obs,
-                                         float* __restrict__ act, float* __restrict__ obs_traj,
-                                         float* __restrict__ act_traj, const Book bk, float* bufA, float* bufB) {
+// act[e] = pi(obs[e]), through the normaliser nm when it has one; optional copies of the raw observation
+// and the action into the rollout's trajectories; the bookkeeping of the previous env step (bk.rew64 !=
+// NULL) for the tile's envs comes first.  Rows past `rows` are zero-filled in LDS and neither read from nor
+// written to memory.  bufA / bufB: the workgroup's two [PD][PT] LDS planes.
+// MODE picks the instantiation, so that the plain path stays the code it was before normalisers existed:
+// PLAIN: nm and st are ignored.  NORM (nm.mean != NULL): the transform is applied as the tile is stored.
+// COLLECT (a rollout step with statistics attached, st.sum != NULL; nm.mean may be NULL): the tile is stored
+// raw, lane k adds its column to the slot and then normalises that same column in place, which costs one
+// more barrier than NORM.  NORM and COLLECT give the same bits.
+enum Mode { PLAIN = 0, NORM = 1, COLLECT = 2 };
+
+inline Mode mode_of(const Norm& nm, const Slot& st) { return st.sum ? COLLECT : (nm.mean ? NORM : PLAIN); }
+
+template <int MODE>
+__device__ __forceinline__ void act_tile(const Weights P, const Norm nm, const Slot st, int env0, int rows,
+                                         const float* __restrict__ obs, float* __restrict__ act,
+                                         float* __restrict__ obs_traj, float* __restrict__ act_traj, const Book bk,
+                                         float* bufA, float* bufB) {
   const int tid = threadIdx.x;
   if (bk.rew64 && tid < rows) book_env(bk, env0 + tid);
 
-  // the tile's observations (rows * obs_dim contiguous floats) -> bufA [obs_dim][PT], zero past `rows`
   const int K0 = P.obs_dim;
-  for (int i = tid; i < PT * K0; i += PB) {
-    const int e = i / K0, k = i - e * K0;
-    float v = 0.f;
-    if (e < rows) {
-      const size_t at = (size_t)env0 * K0 + i;
-      v = obs[at];
-      if (obs_traj) obs_traj[at] = v;
+  if (MODE == COLLECT) {
+    int* fl = reinterpret_cast<int*>(bufB);
+    // active: the action computed from this row will be booked (this lane did the row's bookkeeping above)
+    if (tid < PT) fl[tid] = tid < rows && (bk.autoreset || bk.done_episodes[env0 + tid] == 0) ? 1 : 0;
+    load_tile(K0, env0, rows, obs, obs_traj, Norm{nullptr, nullptr, 0.f}, bufA, fl);
+    __syncthreads();
+    stats_tile(st, K0, bufA, fl);
+    if (nm.mean && tid < K0) {
+      const float mean = nm.mean[tid], inv_std = nm.inv_std[tid];
+      for (int e = 0; e < rows; e++) bufA[tid * PT + e] = normalise(bufA[tid * PT + e], mean, inv_std, nm.clip);
     }
-    bufA[k * PT + e] = v;
+  } else {
+    load_tile(K0, env0, rows, obs, obs_traj, MODE == NORM ? nm : Norm{nullptr, nullptr, 0.f}, bufA, nullptr);
   }
   __syncthreads();
   layer(P.w1, P.b1, K0, P.h1, true, bufA, bufB);
@@ -155,15 +262,32 @@ __device__ __forceinline__ void act_tile(const Weights P, int env0, int rows, co
 
 // The actor launch of a rollout: act = pi(obs) for the handle's n envs after the bookkeeping `bk`,
 // enqueued on `stream`; returns the hipError_t of the launch.
+// `collect`: accumulate the actor's attached statistics (rollout steps only; the loop has validated them).
 typedef int (*ActLaunch)(const void* actor, int n, const float* obs, float* act, float* obs_traj, float* act_traj,
-                         const Book& bk, hipStream_t stream);
+                         const Book& bk, bool collect, hipStream_t stream);
 
 // The closed loop of pbg_rollout / pbg_rollout_population (pbg_policy.hip): validates `io` against the
 // handle and the actor's device and dims, then enqueues per step the actor and the handle's step, and
 // one closing bookkeeping launch.  `who` names the entry point in error messages; `group` > 1: the
-// handle's n_envs must be a multiple of it (the population's member count).
+// handle's n_envs must be a multiple of it (the population's member count).  `stats`: the actor's attached
+// statistics or NULL; refused unless on the actor's device, of its obs_dim and with a slot per workgroup.
 int rollout_loop(const char* who, pbg_handle* h, const pbg_rollout_io_t* io, void* stream, int actor_device,
-                 int obs_dim, int act_dim, int group, ActLaunch launch, const void* actor);
+                 int obs_dim, int act_dim, int group, ActLaunch launch, const void* actor, const pbg_obs_stats* stats);
+
+// workgroups (= slots) of an actor launch over n rows in groups of G (n a multiple of G > 0)
+inline long long tiles_of(int n, int G) { return (long long)(n / G) * ((G + PT - 1) / PT); }
 
 }  // namespace policy
 }  // namespace pbg
+
+// pbg.h pbg_obs_stats: one device allocation of 8-byte words, totals [1 + 2 K] | slot_sum [n_slots, K] |
+// slot_sumsq [n_slots, K] | slot_count [n_slots] (pbg_obsnorm.hip owns it; the actors read the pointers)
+struct pbg_obs_stats {
+  int device, obs_dim, n_slots;
+  double* totals;
+  double* slot_sum;
+  double* slot_sumsq;
+  int64_t* slot_count;
+
+  pbg::policy::Slot slot0() const { return pbg::policy::Slot{slot_count, slot_sum, slot_sumsq}; }
+};

@@ -30,6 +30,12 @@ struct pbg_population {
   int n_pairs, pair0;
   int D;           // parameters per member
   float* members;  // device [2 n_pairs, D]
+  // the normaliser every member shares (pbg_population_set_obs_norm): device mean [obs_dim] then inv_std
+  // [obs_dim], allocated with the members; norm_on 0 = none
+  float* norm;
+  float clip;
+  int norm_on;
+  pbg_obs_stats* stats;  // attached (pbg_population_attach_obs_stats), not owned
 };
 
 namespace {
@@ -127,7 +133,11 @@ __global__ __launch_bounds__(256) void copy_rows_kernel(int D, size_t src_stride
 // grid = P * tpm workgroups, tpm = ceil(G / PT) tiles per member: workgroup (m, t) owns envs
 // m G + t PT .. + rows of member m; the last tile of a member whose G is no multiple of PT has fewer rows
 // (zero-filled in LDS, nothing read or written past them).
+// nm / st / MODE: the population's normaliser, slot 0 of the statistics to collect into and the instantiation,
+// as policy_act_kernel's.
+template <int MODE>
 __global__ __launch_bounds__(PB) void population_act_kernel(const float* __restrict__ members, Dims dm, int D, int G, int tpm,
+                                                            Norm nm, Slot st,
                                                             const float* __restrict__ obs, float* __restrict__ act,
                                                             float* __restrict__ obs_traj, float* __restrict__ act_traj,
                                                             Book bk) {
@@ -144,18 +154,34 @@ __global__ __launch_bounds__(PB) void population_act_kernel(const float* __restr
   W.b2 = W.w2 + dm.h1 * dm.h2;
   W.w3 = W.b2 + dm.h2;
   W.b3 = W.w3 + dm.h2 * dm.act_dim;
-  act_tile(W, m * G + t * PT, min(PT, G - t * PT), obs, act, obs_traj, act_traj, bk, bufA, bufB);
+  act_tile<MODE>(W, nm, slot_at(st, dm.obs_dim, blockIdx.x), m * G + t * PT, min(PT, G - t * PT), obs, act, obs_traj, act_traj, bk,
+           bufA, bufB);
 }
 
 int launch_population_act(const void* actor, int n, const float* obs, float* act, float* obs_traj, float* act_traj,
-                          const Book& bk, hipStream_t stream) {
+                          const Book& bk, bool collect, hipStream_t stream) {
   const pbg_population* p = static_cast<const pbg_population*>(actor);
   const int P = 2 * p->n_pairs;
   const int G = n / P;  // the callers have checked n % P == 0 and n > 0
   const int tpm = (G + PT - 1) / PT;
   const Dims dm{p->obs_dim, p->h1, p->h2, p->act_dim};
-  hipLaunchKernelGGL(population_act_kernel, dim3((unsigned)P * (unsigned)tpm), dim3(PB), 0, stream, p->members, dm, p->D, G,
-                     tpm, obs, act, obs_traj, act_traj, bk);
+  const Norm nm = p->norm_on ? Norm{p->norm, p->norm + p->obs_dim, p->clip} : Norm{nullptr, nullptr, 0.f};
+  const Slot st = collect && p->stats ? p->stats->slot0() : Slot{nullptr, nullptr, nullptr};
+  const dim3 grid((unsigned)P * (unsigned)tpm);
+  switch (mode_of(nm, st)) {
+    case PLAIN:
+      hipLaunchKernelGGL(population_act_kernel<PLAIN>, grid, dim3(PB), 0, stream, p->members, dm, p->D, G, tpm, nm, st, obs, act,
+                         obs_traj, act_traj, bk);
+      break;
+    case NORM:
+      hipLaunchKernelGGL(population_act_kernel<NORM>, grid, dim3(PB), 0, stream, p->members, dm, p->D, G, tpm, nm, st, obs, act,
+                         obs_traj, act_traj, bk);
+      break;
+    case COLLECT:
+      hipLaunchKernelGGL(population_act_kernel<COLLECT>, grid, dim3(PB), 0, stream, p->members, dm, p->D, G, tpm, nm, st, obs, act,
+                         obs_traj, act_traj, bk);
+      break;
+  }
   return (int)hipGetLastError();
 }
 
@@ -240,10 +266,16 @@ int pbg_population_create(int device, int obs_dim, int h1, int h2, int act_dim, 
   p->pair0 = pair0;
   p->D = param_count(Dims{obs_dim, h1, h2, act_dim});
   p->members = nullptr;
+  p->norm = nullptr;
+  p->clip = 0.f;
+  p->norm_on = 0;
+  p->stats = nullptr;
   DeviceGuard dg(device);
   const size_t bytes = (size_t)2 * n_pairs * p->D * sizeof(float);
   int e = (int)hipMalloc(&p->members, bytes);
   if (!e) e = (int)hipMemset(p->members, 0, bytes);
+  if (!e) e = (int)hipMalloc(&p->norm, (size_t)2 * obs_dim * sizeof(float));
+  if (!e) e = (int)hipMemset(p->norm, 0, (size_t)2 * obs_dim * sizeof(float));
   if (e) {
     pbg_population_destroy(p);
     return hip_fail(e, "pbg_population_create: member storage");
@@ -258,7 +290,36 @@ void pbg_population_destroy(pbg_population* p) {
     DeviceGuard dg(p->device);
     (void)hipFree(p->members);
   }
+  if (p->norm) {
+    DeviceGuard dg(p->device);
+    (void)hipFree(p->norm);
+  }
   delete p;
+}
+
+int pbg_population_set_obs_norm(pbg_population* p, const float* mean, const float* inv_std, float clip, void* stream) {
+  if (!p) return pbg::capi_fail(PBG_E_ARG, "pbg_population_set_obs_norm: population is NULL");
+  if (!mean && !inv_std) {
+    p->norm_on = 0;
+    return PBG_OK;
+  }
+  if (!mean || !inv_std)
+    return pbg::capi_fail(PBG_E_ARG, "pbg_population_set_obs_norm: mean and inv_std must both be given (or both NULL)");
+  if (!(clip > 0.f)) return pbg::capi_fail(PBG_E_ARG, "pbg_population_set_obs_norm: clip must be > 0");
+  DeviceGuard dg(p->device);
+  const size_t bytes = (size_t)p->obs_dim * sizeof(float);
+  int e = (int)hipMemcpyAsync(p->norm, mean, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+  if (!e) e = (int)hipMemcpyAsync(p->norm + p->obs_dim, inv_std, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+  if (e) return hip_fail(e, "pbg_population_set_obs_norm: copy");
+  p->clip = clip;
+  p->norm_on = 1;
+  return PBG_OK;
+}
+
+int pbg_population_attach_obs_stats(pbg_population* p, pbg_obs_stats* s) {
+  if (!p) return pbg::capi_fail(PBG_E_ARG, "pbg_population_attach_obs_stats: population is NULL");
+  p->stats = s;
+  return PBG_OK;
 }
 
 int pbg_population_noise_host(int obs_dim, int h1, int h2, int act_dim, uint64_t seed, uint32_t generation, int pair0,
@@ -341,14 +402,14 @@ int pbg_population_act(const pbg_population* p, int n, const float* obs, float* 
   DeviceGuard dg(p->device);
   Book none;
   memset(&none, 0, sizeof(none));
-  const int e = launch_population_act(p, n, obs, act, nullptr, nullptr, none, (hipStream_t)stream);
+  const int e = launch_population_act(p, n, obs, act, nullptr, nullptr, none, false, (hipStream_t)stream);
   return e ? hip_fail(e, "population_act_kernel launch") : PBG_OK;
 }
 
 int pbg_rollout_population(pbg_handle* h, const pbg_population* p, const pbg_rollout_io_t* io, void* stream) {
   if (!h || !p || !io) return pbg::capi_fail(PBG_E_ARG, "pbg_rollout_population: NULL handle, population or io");
   return rollout_loop("pbg_rollout_population", h, io, stream, p->device, p->obs_dim, p->act_dim, 2 * p->n_pairs,
-                      launch_population_act, p);
+                      launch_population_act, p, p->stats);
 }
 
 int pbg_population_fitness(const pbg_population* p, int n, const double* cur_return, const double* done_return,

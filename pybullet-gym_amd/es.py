@@ -22,11 +22,17 @@ class EvolutionStrategy:
     ``lr``: the step size; ``steps``: env steps per rollout; ``seed``: of the initial centre
     (``population.init_theta``) and of the noise.  ``init_q``: ``[num_envs, reset_dofs]`` joint positions
     every reset starts from (None: the env's own reset noise, fresh each generation).
+    ``obs_norm=True``: running observation normalisation (Salimans et al. 2017, Mania et al. 2018): an
+    ``ObsStats`` (``obs_stats``) is attached to the population during ``step()``'s rollouts, and after each
+    generation's rollout it is finalized into the population's normaliser (``clip`` = ``obs_clip``), so
+    generation g + 1 acts under the statistics of generations 0 .. g, all members under the same ones;
+    generation 0 under the initial totals (mean 0, inv_std 1).  ``evaluate()`` does not move the statistics.
 
     ``theta`` (device float32 ``[n_params]``) is the centre and ``generation`` the number of ``step()``
     calls so far; both may be assigned (to resume a run)."""
 
-    def __init__(self, env, population, sigma: float, lr: float, steps: int, seed: int = 0, init_q=None):
+    def __init__(self, env, population, sigma: float, lr: float, steps: int, seed: int = 0, init_q=None,
+                 obs_norm: bool = False, obs_clip: float = 5.0):
         env_idx = env.device.index if env.device.index is not None else torch.cuda.current_device()
         if population.device != torch.device("cuda", env_idx):
             raise _native.PbgError(f"EvolutionStrategy: the population is on {population.device}, the env on {env.device}")
@@ -50,6 +56,11 @@ class EvolutionStrategy:
         self._centred = torch.arange(P, dtype=torch.float32, **kw) / (P - 1) - 0.5
         self._ranks = torch.zeros(P, dtype=torch.float32, **kw)
         self._g = torch.zeros(population.n_params, dtype=torch.float32, **kw)
+        self.obs_stats, self.obs_clip = None, float(obs_clip)
+        if obs_norm:
+            from .policy import ObsStats
+            self.obs_stats = ObsStats(population.obs_dim, env.num_envs, group=env.num_envs // P, device=population.device)
+            population.set_obs_norm(*self.obs_stats.finalize(), clip=self.obs_clip)  # the initial totals' normaliser
 
     def _rollout(self):
         self.env.reset(init_q=self.init_q)
@@ -60,7 +71,12 @@ class EvolutionStrategy:
         pop, gen = self.population, self.generation
         self.env.reset(init_q=self.init_q)
         pop.perturb(self.theta, self.sigma, self.seed, gen)
+        if self.obs_stats is not None:
+            pop.attach_obs_stats(self.obs_stats)
         res = self.env.rollout(pop, self.steps, fresh=True)
+        if self.obs_stats is not None:
+            pop.attach_obs_stats(None)
+            pop.set_obs_norm(*self.obs_stats.finalize(), clip=self.obs_clip)
         self.update(res, gen)
         self.generation = gen + 1
         return self.fitness
@@ -81,5 +97,10 @@ class EvolutionStrategy:
         """Every member = the centre, one rollout: per-env ``(returns float64 [n], lengths int32 [n])``
         (of the first episode with ``autoreset=False``), fresh tensors."""
         self.population.set_all(self.theta)
+        attached = self.population.obs_stats
+        if attached is not None:
+            self.population.attach_obs_stats(None)  # evaluating does not move the statistics
         res = self._rollout()
+        if attached is not None:
+            self.population.attach_obs_stats(attached)
         return res.done_return + res.cur_return, res.done_length + res.cur_length

@@ -15,6 +15,116 @@ from . import _native
 
 NPZ_KEYS = ("weights_dense1_w", "weights_dense1_b", "weights_dense2_w", "weights_dense2_b",
             "weights_final_w", "weights_final_b")  # the reference's names (enjoy_TF_*.py:21-24)
+NORM_KEYS = ("obs_mean", "obs_inv_std", "obs_clip")  # this project's: a normaliser saved next to the weights
+
+
+def _need(name):
+    if not hasattr(_native.lib(), name):
+        raise _native.PbgError(f"{_native.LIB_PATH} has no {name}: a build without observation normalisation")
+    return getattr(_native.lib(), name)
+
+
+class ObsStats:
+    """Running per-component statistics of observations on one GPU (include/pbg.h pbg_obs_stats_*): float64
+    totals ``count, sum[K], sumsq[K]`` (initially OpenAI ES's ``RunningStat(eps=1e-2)``) and one partial
+    accumulator ("slot") per 16-row tile, so nothing is atomic and every sum has a stated order.
+
+    ``n_envs`` and ``group`` size the slots for the launches the object will see: ``group=None`` for batches
+    of up to ``n_envs`` rows tiled as ``MLPPolicy`` tiles them, ``group=G`` for ``n_envs / G`` groups of
+    ``G`` consecutive rows tiled per group as ``MLPPopulation`` tiles its members' envs.  Attached to an
+    actor (``attach_obs_stats``), every step of ``VecEnv.rollout`` with that actor adds the observations
+    whose actions are booked; ``update`` adds a batch directly.  ``finalize`` folds the slots into the
+    totals and returns ``(mean, inv_std)``.  Everything is asynchronous on the current stream."""
+
+    def __init__(self, obs_dim: int, n_envs: int, group=None, device="cuda:0"):
+        import torch
+        self.obs_dim, self.n_envs = int(obs_dim), int(n_envs)
+        self.group = None if group is None else int(group)
+        if self.n_envs < 1 or (self.group is not None and (self.group < 1 or self.n_envs % self.group != 0)):
+            raise _native.PbgError(f"ObsStats: n_envs {n_envs} must be >= 1 and a multiple of group {group}")
+        G = self.n_envs if self.group is None else self.group
+        self.n_slots = (self.n_envs // G) * ((G + 15) // 16)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise _native.PbgError(f"ObsStats: device must be a GPU, got {device!r}")
+        idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
+        self.device = torch.device("cuda", idx)
+        h = ctypes.c_void_p()
+        _native.check(_need("pbg_obs_stats_create")(idx, self.obs_dim, self.n_slots, ctypes.byref(h)),
+                      "pbg_obs_stats_create")
+        self._s = h
+        self.mean = torch.zeros(self.obs_dim, dtype=torch.float32, device=self.device)
+        self.inv_std = torch.ones(self.obs_dim, dtype=torch.float32, device=self.device)
+
+    def close(self):
+        """Destroy the native object; detach it from every actor first."""
+        if getattr(self, "_s", None):
+            _native.lib().pbg_obs_stats_destroy(self._s)
+            self._s = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _open(self, what):
+        if not getattr(self, "_s", None):
+            raise _native.PbgError(f"ObsStats.{what}: the object is closed")
+        return self._s
+
+    def _stream(self):
+        import torch
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    def update(self, obs, active=None):
+        """Add ``obs`` (``[n, obs_dim]`` float32 on the device) to the slots: the rows whose ``active`` flag
+        (``[n]`` uint8, None = all) is set and that hold no NaN or inf."""
+        import torch
+        s = self._open("update")
+        if not isinstance(obs, torch.Tensor) or obs.dtype != torch.float32 or obs.device != self.device or \
+                not obs.is_contiguous() or obs.dim() != 2 or obs.shape[1] != self.obs_dim:
+            raise _native.PbgError(f"ObsStats.update: obs must be a contiguous float32 tensor [n, {self.obs_dim}] on "
+                                   f"{self.device}")
+        n = obs.shape[0]
+        if active is not None and (not isinstance(active, torch.Tensor) or active.dtype != torch.uint8 or
+                                   active.device != self.device or not active.is_contiguous() or
+                                   tuple(active.shape) != (n,)):
+            raise _native.PbgError(f"ObsStats.update: active must be a contiguous uint8 tensor [{n}] on {self.device}")
+        _native.check(_native.lib().pbg_obs_stats_update(s, n, self.group or 0, obs.data_ptr(),
+                                                         None if active is None else active.data_ptr(), self._stream()),
+                      "pbg_obs_stats_update")
+
+    def finalize(self):
+        """Fold the slots into the totals (slot-ascending float64 adds), zero them and return ``(mean,
+        inv_std)``: float32 ``[obs_dim]`` device tensors this object owns and overwrites, ``inv_std =
+        1 / sqrt(max(var, 1e-2))``."""
+        s = self._open("finalize")
+        _native.check(_native.lib().pbg_obs_stats_finalize(s, self.mean.data_ptr(), self.inv_std.data_ptr(),
+                                                           self._stream()), "pbg_obs_stats_finalize")
+        return self.mean, self.inv_std
+
+    @property
+    def totals(self):
+        """``[1 + 2 obs_dim]`` float64 on the device: count, sum, sumsq (a fresh tensor; what the slots hold
+        is not in it before ``finalize``).  Assignable, to resume a run or to merge shards by adding totals."""
+        import torch
+        s = self._open("totals")
+        out = torch.empty(1 + 2 * self.obs_dim, dtype=torch.float64, device=self.device)
+        _native.check(_native.lib().pbg_obs_stats_get_totals(s, out.data_ptr(), self._stream()),
+                      "pbg_obs_stats_get_totals")
+        return out
+
+    @totals.setter
+    def totals(self, value):
+        import torch
+        s = self._open("totals")
+        t = torch.as_tensor(value).to(device=self.device, dtype=torch.float64).contiguous()
+        if tuple(t.shape) != (1 + 2 * self.obs_dim,):
+            raise _native.PbgError(f"ObsStats.totals: shape {tuple(t.shape)}, expected ({1 + 2 * self.obs_dim},)")
+        _native.check(_native.lib().pbg_obs_stats_set_totals(s, t.data_ptr(), self._stream()),
+                      "pbg_obs_stats_set_totals")
+        self._totals_src = t  # alive until the stream has copied it
 
 
 class MLPPolicy:
@@ -24,9 +134,10 @@ class MLPPolicy:
     ``b3 [act_dim]``: numpy arrays (or anything ``np.asarray`` takes), the reference's layout.
     ``device``: None = a host policy (``act`` takes and returns numpy, no GPU needed); a torch device
     (``"cuda:0"``) = the weights live there and ``act`` takes and returns torch tensors on it.
-    Dims: 1..256 for obs_dim / h1 / h2, 1..64 for act_dim, no multiple of anything required."""
+    Dims: 1..256 for obs_dim / h1 / h2, 1..64 for act_dim, no multiple of anything required.
+    ``obs_norm=(mean, inv_std, clip)``: a normaliser (``set_obs_norm``)."""
 
-    def __init__(self, w1, b1, w2, b2, w3, b3, device=None):
+    def __init__(self, w1, b1, w2, b2, w3, b3, device=None, obs_norm=None):
         ws = [np.ascontiguousarray(np.asarray(a), dtype=np.float32) for a in (w1, b1, w2, b2, w3, b3)]
         w1, b1, w2, b2, w3, b3 = ws
         if w1.ndim != 2 or w2.ndim != 2 or w3.ndim != 2 or b1.ndim != 1 or b2.ndim != 1 or b3.ndim != 1:
@@ -53,12 +164,48 @@ class MLPPolicy:
                                                       *[a.ctypes.data_as(FP) for a in ws], ctypes.byref(h)),
                       "pbg_policy_create")
         self._p = h
+        self.obs_norm = None    # (mean, inv_std, clip) as numpy float32 / float, or None
+        self.obs_stats = None   # the attached ObsStats, or None
+        if obs_norm is not None:
+            self.set_obs_norm(*obs_norm)
 
     @classmethod
     def from_npz(cls, path, device=None) -> "MLPPolicy":
-        """Weights from an npz with the reference's names (``weights_dense1_w`` ... ``weights_final_b``)."""
+        """Weights from an npz with the reference's names (``weights_dense1_w`` ... ``weights_final_b``), and
+        the normaliser when the file holds one (``obs_mean``, ``obs_inv_std``, ``obs_clip``)."""
         with np.load(path) as z:
-            return cls(*[z[k] for k in NPZ_KEYS], device=device)
+            norm = (z["obs_mean"], z["obs_inv_std"], float(z["obs_clip"])) if all(k in z for k in NORM_KEYS) else None
+            return cls(*[z[k] for k in NPZ_KEYS], device=device, obs_norm=norm)
+
+    def set_obs_norm(self, mean, inv_std=None, clip: float = 5.0):
+        """Every later ``act`` / rollout feeds the MLP ``clip((obs - mean) * inv_std, -clip, clip)`` (float32,
+        one rounding per operation); ``mean``, ``inv_std``: ``[obs_dim]`` arrays (or CPU / GPU tensors),
+        copied.  ``set_obs_norm(None)`` switches the normaliser off.  Synchronises the device."""
+        if not self._p:
+            raise _native.PbgError("MLPPolicy.set_obs_norm: the policy is closed")
+        f = _need("pbg_policy_set_obs_norm")
+        if mean is None and inv_std is None:
+            _native.check(f(self._p, None, None, 0.0), "pbg_policy_set_obs_norm")
+            self.obs_norm = None
+            return
+        arrs = []
+        for a in (mean, inv_std):
+            a = a.detach().cpu().numpy() if hasattr(a, "detach") else a
+            a = np.ascontiguousarray(np.asarray(a), dtype=np.float32)
+            if a.shape != (self.obs_dim,):
+                raise _native.PbgError(f"MLPPolicy.set_obs_norm: mean and inv_std must have shape ({self.obs_dim},)")
+            arrs.append(a.copy())
+        _native.check(f(self._p, arrs[0].ctypes.data, arrs[1].ctypes.data, float(clip)), "pbg_policy_set_obs_norm")
+        self.obs_norm = (arrs[0], arrs[1], float(clip))
+
+    def attach_obs_stats(self, stats):
+        """While an ``ObsStats`` is attached, every step of ``VecEnv.rollout`` with this policy adds its
+        observations to it (``act`` never does); None detaches."""
+        if not self._p:
+            raise _native.PbgError("MLPPolicy.attach_obs_stats: the policy is closed")
+        _native.check(_need("pbg_policy_attach_obs_stats")(self._p, None if stats is None else stats._open("attach")),
+                      "pbg_policy_attach_obs_stats")
+        self.obs_stats = stats
 
     def close(self):
         if getattr(self, "_p", None):
@@ -164,6 +311,9 @@ class MLPPopulation:
         _native.check(_native.lib().pbg_population_create(idx, *self.dims, self.n_pairs, self.pair0, ctypes.byref(h)),
                       "pbg_population_create")
         self._pop = h
+        self.obs_clip = None    # the normaliser's clip, None = no normaliser (set_obs_norm)
+        self._norm = None       # this object's copies of its mean and inv_std, allocated by the first set_obs_norm
+        self.obs_stats = None   # the attached ObsStats, or None
 
     def close(self):
         if getattr(self, "_pop", None):
@@ -196,6 +346,43 @@ class MLPPopulation:
             raise _native.PbgError(f"MLPPopulation.{what}: {name} must be a contiguous {dtype} tensor of shape "
                                    f"{tuple(shape)} on {self.device}")
         return t
+
+    # ------------------------------------------------------------------ normaliser
+    def set_obs_norm(self, mean, inv_std=None, clip: float = 5.0):
+        """Every member feeds its MLP ``clip((obs - mean) * inv_std, -clip, clip)`` from now on (stream
+        order); ``mean``, ``inv_std``: contiguous float32 ``[obs_dim]`` tensors on the device, copied on the
+        current stream (no host work after the first call, which allocates this object's copies for
+        ``save_npz``).  ``set_obs_norm(None)`` switches the normaliser off."""
+        import torch
+        p = self._open("set_obs_norm")
+        f = _need("pbg_population_set_obs_norm")
+        if mean is None and inv_std is None:
+            _native.check(f(p, None, None, 0.0, self._stream()), "pbg_population_set_obs_norm")
+            self.obs_clip = None
+            return
+        mean = self._vec(mean, "set_obs_norm", "mean", (self.obs_dim,))
+        inv_std = self._vec(inv_std, "set_obs_norm", "inv_std", (self.obs_dim,))
+        _native.check(f(p, mean.data_ptr(), inv_std.data_ptr(), float(clip), self._stream()),
+                      "pbg_population_set_obs_norm")
+        if self._norm is None:
+            self._norm = torch.empty((2, self.obs_dim), dtype=torch.float32, device=self.device)
+        self._norm[0].copy_(mean)
+        self._norm[1].copy_(inv_std)
+        self.obs_clip = float(clip)
+
+    @property
+    def obs_norm(self):
+        """``(mean, inv_std, clip)`` of the normaliser in force (device tensors, views of this object's
+        copies), or None."""
+        return None if self.obs_clip is None else (self._norm[0], self._norm[1], self.obs_clip)
+
+    def attach_obs_stats(self, stats):
+        """While an ``ObsStats`` (sized with ``group`` = the envs per member) is attached, every step of
+        ``VecEnv.rollout`` with this population adds its observations to it; None detaches."""
+        p = self._open("attach_obs_stats")
+        _native.check(_need("pbg_population_attach_obs_stats")(p, None if stats is None else stats._open("attach")),
+                      "pbg_population_attach_obs_stats")
+        self.obs_stats = stats
 
     # ------------------------------------------------------------------ parameters
     def init_theta(self, seed: int = 0):
@@ -283,13 +470,18 @@ class MLPPopulation:
 
     def save_npz(self, path, theta_or_member):
         """Write a parameter vector (a tensor or array ``[n_params]``) or member (an int) as an npz with the
-        reference's key names: ``MLPPolicy.from_npz`` and tools/enjoy.py load it."""
+        reference's key names: ``MLPPolicy.from_npz`` and tools/enjoy.py load it.  With a normaliser set the
+        file also gets ``obs_mean``, ``obs_inv_std`` and ``obs_clip``."""
         if isinstance(theta_or_member, (int, np.integer)):
             ws = self.member_weights(int(theta_or_member))
         else:
             t = theta_or_member
             ws = unpack_theta(self.dims, t.detach().cpu().numpy() if hasattr(t, "detach") else t)
-        np.savez(path, **dict(zip(NPZ_KEYS, ws)))
+        extra = {}
+        if self.obs_clip is not None:
+            extra = dict(obs_mean=self._norm[0].cpu().numpy(), obs_inv_std=self._norm[1].cpu().numpy(),
+                         obs_clip=np.float32(self.obs_clip))
+        np.savez(path, **dict(zip(NPZ_KEYS, ws)), **extra)
 
     # ------------------------------------------------------------------ actor
     def act(self, obs, out=None):

@@ -17,7 +17,14 @@ Also measured: a device-to-device copy's bandwidth on the same box (the yardstic
 stream) and the once-per-generation work outside the rollout (perturb + fitness + ranks + grad + update,
 one HIP graph) at 512 pairs.
 
+With --obs-norm the rollout legs are A and B, each of them again with a normaliser applied (`_norm`) and
+again with a normaliser applied and observation statistics collected (`_norm_stats`, an ObsStats attached
+to the actor), written to profiles/obs_norm_rollout.json.  The normaliser is the identity (mean 0, inv_std
+1, a clip no observation reaches): the same three float32 operations per loaded element as any other, and
+all six legs stay in the same state bit for bit (asserted on the final observations).
+
   python tools/bench_population.py [--out profiles/population_rollout.json]
+  python tools/bench_population.py --obs-norm [--out profiles/obs_norm_rollout.json]
   python tools/bench_population.py --actor-only [--members 1024]   # actor launches alone, for a kernel trace
 """
 from __future__ import annotations
@@ -124,6 +131,60 @@ def bench_rollout(args, dev):
     return out
 
 
+NORM_LEGS = {"A": (None, ""), "B": (1024, ""), "A_norm": (None, "norm"), "B_norm": (1024, "norm"),
+             "A_norm_stats": (None, "norm+stats"), "B_norm_stats": (1024, "norm+stats")}
+
+
+def bench_obs_norm(args, dev):
+    """Legs A and B of bench_rollout, each plain, with a normaliser, and with a normaliser and statistics."""
+    import torch
+    from pybulletgym_amd.policy import ObsStats
+    from pybulletgym_amd.vec_env import VecEnv
+    pis, dims, _ = actors(dev, {leg: m for leg, (m, _) in NORM_LEGS.items()})
+    mean, inv_std = torch.zeros(dims[0], device=dev), torch.ones(dims[0], device=dev)
+    stats = {}
+    for leg, (m, mode) in NORM_LEGS.items():
+        if "norm" in mode:
+            pis[leg].set_obs_norm(mean, inv_std, clip=1e30)
+        if "stats" in mode:
+            stats[leg] = ObsStats(dims[0], N, group=None if m is None else N // m, device=dev)
+            pis[leg].attach_obs_stats(stats[leg])
+    envs = {leg: VecEnv(ENV_ID, N, device=dev, seed=0, autoreset=True, precision=64) for leg in NORM_LEGS}
+    for e in envs.values():
+        e.reset()
+    pre = (args.preroll + args.warmup + K - 1) // K
+    for _ in range(pre):
+        for leg in NORM_LEGS:
+            envs[leg].rollout(pis[leg], K)
+    torch.cuda.synchronize(dev)
+    graphs = {leg: capture(lambda leg=leg: envs[leg].rollout(pis[leg], K), dev) for leg in NORM_LEGS}
+    for leg in NORM_LEGS:
+        graphs[leg].replay()
+    w = timed(args.windows, args.replays, list(NORM_LEGS), lambda leg: graphs[leg].replay(), dev, K)
+    out = summary(w)
+    med = out["median"]
+    counted = {}
+    for leg, st in stats.items():
+        st.finalize()
+        counted[leg] = float(st.totals[0]) - 1e-2
+    out.update({"env_id": ENV_ID, "n_envs": N, "precision": 64, "steps_per_graph": K, "replays_per_window": args.replays,
+                "unit": "us per env-batch step", "legs": {leg: {"members": m, "mode": mode or "plain"}
+                                                          for leg, (m, mode) in NORM_LEGS.items()},
+                "mlp_dims": dims, "normaliser": "identity (mean 0, inv_std 1, clip 1e30)",
+                "delta_us": {leg: med[leg] - med[leg[0]] for leg in NORM_LEGS if leg not in ("A", "B")},
+                "parent_leg_spread_us": {leg: out["max"][leg] - out["min"][leg] for leg in ("A", "B")},
+                "observations_counted": counted,
+                "final_obs_equal": bool(all(torch.equal(envs["A"].obs, envs[leg].obs) for leg in NORM_LEGS))})
+    for e in envs.values():
+        e.close()
+    for p in pis.values():
+        p.attach_obs_stats(None)
+        p.close()
+    for st in stats.values():
+        st.close()
+    return out
+
+
 def bench_copy(args, dev):
     """Device-to-device copy of 1 GiB: bytes read plus bytes written over the time."""
     import torch
@@ -183,7 +244,9 @@ def actor_only(args, dev):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "population_rollout.json"))
+    ap.add_argument("--out", default=None, help="default: profiles/population_rollout.json "
+                    "(--obs-norm: profiles/obs_norm_rollout.json)")
+    ap.add_argument("--obs-norm", action="store_true", help="the observation-normalisation legs only")
     ap.add_argument("--preroll", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--windows", type=int, default=5)
@@ -196,6 +259,19 @@ def main():
     dev = torch.device("cuda:0")
     if args.actor_only:
         return actor_only(args, dev)
+    if args.out is None:
+        args.out = os.path.join(REPO, "profiles", "obs_norm_rollout.json" if args.obs_norm else "population_rollout.json")
+    if args.obs_norm:
+        res = {"rollout": bench_obs_norm(args, dev)}
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+        r = res["rollout"]
+        print("rollout us/step median [min, max]: " + "  ".join(
+            f"{leg} {r['median'][leg]:.1f} [{r['min'][leg]:.1f}, {r['max'][leg]:.1f}]" for leg in NORM_LEGS) +
+            f"  same states: {r['final_obs_equal']}")
+        print(json.dumps({"done": bool(r["final_obs_equal"]), "out": args.out}))
+        return
     res = {"rollout": bench_rollout(args, dev), "copy": bench_copy(args, dev), "generation": bench_generation(args, dev)}
     bw = res["copy"]["GB_per_s_read_plus_write"]["median"]
     res["actor_weight_stream_at_copy_bandwidth_us"] = {

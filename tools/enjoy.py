@@ -18,7 +18,8 @@ sys.path.insert(0, REPO)
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("env_id")
-    ap.add_argument("--weights", required=True, help="npz with weights_dense1_w ... weights_final_b")
+    ap.add_argument("--weights", required=True, help="npz with weights_dense1_w ... weights_final_b (and, from "
+                    "train_es.py --obs-norm, the normaliser obs_mean / obs_inv_std / obs_clip, applied when present)")
     ap.add_argument("--envs", type=int, default=64)
     ap.add_argument("--precision", type=int, choices=(32, 64), default=64)
     ap.add_argument("--seed", type=int, default=0)

@@ -5,6 +5,11 @@ MLPPolicy.from_npz load.
 
   python tools/train_es.py InvertedPendulumPyBulletEnv-v0 [--pairs 32] [--envs-per-member 4] [--steps 200]
          [--generations 60] [--sigma 0.1] [--lr 0.2] [--seed 0] [--precision 64] [--hidden 16 8] [--out es_policy.npz]
+         [--obs-norm] [--obs-clip 5.0] [--curve curve.json]
+
+--obs-norm trains under running observation normalisation (EvolutionStrategy(obs_norm=True)) and saves the
+final normaliser in the npz (obs_mean, obs_inv_std, obs_clip), which MLPPolicy.from_npz picks up; --curve
+writes the per-generation centre returns and lengths as JSON.
 
 Per generation it prints the centre's mean first-episode return and length over all envs (one extra
 rollout with every member set to the centre; --eval-every N does it every N-th generation only)."""
@@ -32,7 +37,12 @@ def main():
     ap.add_argument("--hidden", type=int, nargs=2, default=(16, 8), metavar=("H1", "H2"))
     ap.add_argument("--eval-every", type=int, default=1)
     ap.add_argument("--out", default="es_policy.npz")
+    ap.add_argument("--obs-norm", action="store_true", help="running observation normalisation")
+    ap.add_argument("--obs-clip", type=float, default=5.0)
+    ap.add_argument("--curve", default=None, help="write the per-generation centre evaluation here (JSON)")
     args = ap.parse_args()
+
+    import json
 
     import torch
     import pybulletgym_amd  # noqa: F401
@@ -44,12 +54,17 @@ def main():
     env = VecEnv(args.env_id, n, device="cuda:0", seed=args.seed, autoreset=False, precision=args.precision)
     dims = (env.info.obs_dim, args.hidden[0], args.hidden[1], env.info.action_dim)
     pop = MLPPopulation(dims, args.pairs, env.device)
-    es = EvolutionStrategy(env, pop, args.sigma, args.lr, args.steps, seed=args.seed)
+    es = EvolutionStrategy(env, pop, args.sigma, args.lr, args.steps, seed=args.seed, obs_norm=args.obs_norm,
+                           obs_clip=args.obs_clip)
     print(f"{args.env_id} (float{args.precision}): {pop.n_members} members x {args.envs_per_member} envs, MLP {dims}, "
-          f"{pop.n_params} parameters, sigma {args.sigma} lr {args.lr}, {args.steps}-step rollouts")
+          f"{pop.n_params} parameters, sigma {args.sigma} lr {args.lr}, {args.steps}-step rollouts, "
+          f"observation normalisation {'on' if args.obs_norm else 'off'}")
+    curve = []
 
     def report(gen):
         ret, length = es.evaluate()
+        curve.append(dict(generation=gen, return_mean=ret.mean().item(), return_min=ret.min().item(),
+                          length_mean=length.double().mean().item()))
         print(f"generation {gen:4d}: centre return mean {ret.mean().item():9.2f} min {ret.min().item():9.2f}  "
               f"first-episode length mean {length.double().mean().item():6.1f} of {args.steps}", flush=True)
 
@@ -61,6 +76,12 @@ def main():
     torch.cuda.synchronize()
     pop.save_npz(args.out, es.theta)
     print(f"wrote {args.out}")
+    if args.curve:
+        with open(args.curve, "w") as f:
+            json.dump(dict(env_id=args.env_id, obs_norm=args.obs_norm, obs_clip=args.obs_clip, pairs=args.pairs,
+                           envs_per_member=args.envs_per_member, steps=args.steps, sigma=args.sigma, lr=args.lr,
+                           seed=args.seed, precision=args.precision, hidden=list(args.hidden), curve=curve), f, indent=1)
+        print(f"wrote {args.curve}")
     pop.close()
     env.close()
 
