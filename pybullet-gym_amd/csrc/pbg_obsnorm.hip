@@ -1,6 +1,6 @@
 // pbg_obsnorm.hip -- running observation statistics (include/pbg.h pbg_obs_stats_*): the object, the
 // stand-alone update kernel and the finalize kernel.  The tile accumulation itself (stats_tile) and the
-// tile load that sets the flags (load_tile) are pbg_policy_dev.h's, the very functions the two actors run
+// tile load that sets the flags (load_tile) are pbg_policy_dev.h's, the very functions the actor kernel runs
 // during a rollout: the stand-alone kernel is those two around one barrier.
 //
 // Order of every sum (pbg.h): inside a slot (launch ascending, row-in-tile ascending), written by one lane
@@ -20,18 +20,16 @@ namespace {
 using namespace pbg::policy;
 using pbg::DeviceGuard;
 
-// grid = groups * tpm workgroups, tpm = ceil(G / PT): workgroup (m, t) owns rows m G + t PT .. + rows, as
-// population_act_kernel's (G = n: policy_act_kernel's tiling); `active` NULL = every row
+// grid = groups * tpm workgroups, tpm = ceil(G / PT): workgroup b owns the rows of tile_of(b), as in the
+// actor kernel (G = n: a shared-weight policy's tiling); `active` NULL = every row
 __global__ __launch_bounds__(PB) void obs_stats_update_kernel(Slot st, int K, int G, int tpm, const float* __restrict__ obs,
                                                               const uint8_t* __restrict__ active) {
   __shared__ __attribute__((aligned(16))) float xT[PD * PT];
   __shared__ int fl[FLAG_WORDS];
   const int tid = threadIdx.x;
-  const int m = blockIdx.x / tpm;
-  const int t = blockIdx.x - m * tpm;
-  const int row0 = m * G + t * PT, rows = min(PT, G - t * PT);
-  if (tid < PT) fl[tid] = tid < rows && (!active || active[row0 + tid] != 0) ? 1 : 0;
-  load_tile(K, row0, rows, obs, nullptr, Norm{nullptr, nullptr, 0.f}, xT, fl);
+  const Tile t = tile_of(blockIdx.x, G, tpm);
+  if (tid < PT) fl[tid] = tid < t.rows && (!active || active[t.row0 + tid] != 0) ? 1 : 0;
+  load_tile(K, t.row0, t.rows, obs, nullptr, Norm{nullptr, nullptr, 0.f}, xT, fl);
   __syncthreads();
   stats_tile(slot_at(st, K, blockIdx.x), K, xT, fl);
 }
@@ -71,12 +69,6 @@ __global__ __launch_bounds__(PB) void obs_stats_finalize_kernel(int K, int n_slo
   for (int s = k; s < n_slots; s += PB) slot_count[s] = 0;
 }
 
-int hip_fail(int e, const char* what) {
-  char msg[160];
-  snprintf(msg, sizeof(msg), "%s: HIP error %d", what, e);
-  return pbg::capi_fail(PBG_E_HIP, msg);
-}
-
 }  // namespace
 
 extern "C" {
@@ -90,13 +82,7 @@ int pbg_obs_stats_create(int device, int obs_dim, int n_slots, pbg_obs_stats** o
              PBG_POLICY_MAX_DIM, n_slots, device);
     return pbg::capi_fail(PBG_E_ARG, msg);
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device >= ndev) {
-    (void)hipGetLastError();
-    char msg[64];
-    snprintf(msg, sizeof(msg), "pbg_obs_stats_create: no HIP device %d", device);
-    return pbg::capi_fail(PBG_E_HIP, msg);
-  }
+  if (const int rc = check_device("pbg_obs_stats_create", device)) return rc;
   pbg_obs_stats* s = new (std::nothrow) pbg_obs_stats();
   if (!s) return pbg::capi_fail(PBG_E_NOMEM, "pbg_obs_stats_create: out of host memory");
   const size_t K = (size_t)obs_dim, nt = 1 + 2 * K, words = nt + (2 * K + 1) * (size_t)n_slots;

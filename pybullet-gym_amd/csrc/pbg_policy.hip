@@ -1,10 +1,11 @@
-// pbg_policy.hip -- the pretrained-policy MLP (include/pbg.h pbg_policy_*) and the closed-loop
-// rollout (pbg_rollout).  The reference's enjoy scripts evaluate SmallReactivePolicy.act
+// pbg_policy.hip -- the pretrained-policy MLP (include/pbg.h pbg_policy_*), the actor kernel and its launch,
+// and the closed-loop rollout (pbg_rollout).  The reference's enjoy scripts evaluate SmallReactivePolicy.act
 // (examples/roboschool-weights/enjoy_TF_*.py:25-31) once per env per step on the host; here one
 // launch evaluates all three layers for every env, the hidden activations never leave LDS.
 //
-// The MLP tile, its numeric contract and geometry, the bookkeeping and the loop's declaration are in
-// pbg_policy_dev.h, shared with the population actor (pbg_population.hip).
+// One kernel serves every actor (pbg_policy_dev.h Actor): a pbg_policy is the population of one member whose
+// group is the whole batch, pbg_population.hip launches the same kernel with its 2 n_pairs members.  The MLP
+// tile, its numeric contract and geometry, the bookkeeping and the declarations are in pbg_policy_dev.h.
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdio.h>
@@ -15,92 +16,39 @@
 
 #include "pbg_policy_dev.h"
 
-namespace {
-
 using namespace pbg::policy;
+using pbg::DeviceGuard;
+
+namespace {
 
 __global__ __launch_bounds__(256) void book_kernel(Book b, int n) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e < n) book_env(b, e);
 }
 
-// act[n, act_dim] = pi(obs[n, obs_dim]); optional copies of both into the rollout's trajectories; the
-// bookkeeping of the previous env step (bk.rew64 != NULL) for the tile's envs comes first.
-// nm: the policy's normaliser (mean NULL: none); st: slot 0 of the statistics to collect into (sum NULL:
+// act[n, act_dim] = pi_m(obs[n, obs_dim]), n = n_members G rows: grid = n_members * tpm workgroups, workgroup
+// (m, t) (tile_of) runs its rows through member m's weights, params + m D in the flat layout (a shared-weight
+// policy: one member, G = n, tpm = the grid).  Optional copies of observation and action into the rollout's
+// trajectories; the bookkeeping of the previous env step (bk.rew64 != NULL) for the tile's envs comes first.
+// nm: the actor's normaliser (mean NULL: none); st: slot 0 of the statistics to collect into (sum NULL:
 // none), workgroup b adds to slot b; MODE (pbg_policy_dev.h) says which of the two the instantiation looks at.
 template <int MODE>
-__global__ __launch_bounds__(PB) void policy_act_kernel(Weights P, Norm nm, Slot st, int n, const float* __restrict__ obs,
-                                                        float* __restrict__ act, float* __restrict__ obs_traj,
-                                                        float* __restrict__ act_traj, Book bk) {
+__global__ __launch_bounds__(PB) void actor_kernel(const float* __restrict__ params, int obs_dim, int h1, int h2, int act_dim,
+                                                   int D, int G, int tpm, Norm nm, Slot st, const float* __restrict__ obs,
+                                                   float* __restrict__ act, float* __restrict__ obs_traj,
+                                                   float* __restrict__ act_traj, Book bk) {
   __shared__ __attribute__((aligned(16))) float bufA[PD * PT];
   __shared__ __attribute__((aligned(16))) float bufB[PD * PT];
-  const int env0 = blockIdx.x * PT;
-  act_tile<MODE>(P, nm, slot_at(st, P.obs_dim, blockIdx.x), env0, min(PT, n - env0), obs, act, obs_traj, act_traj, bk, bufA,
-           bufB);  // rows >= 1: the grid is ceil(n / PT)
+  const Tile t = tile_of(blockIdx.x, G, tpm);
+  act_tile<MODE>(weights_at(params + (size_t)t.m * D, obs_dim, h1, h2, act_dim), nm, slot_at(st, obs_dim, blockIdx.x), t.row0,
+                 t.rows, obs, act, obs_traj, act_traj, bk, bufA, bufB);
 }
 
-}  // namespace
-
-struct pbg_policy {
-  int device;  // -1: host only
-  int obs_dim, h1, h2, act_dim;
-  size_t off[6], words;  // w1 b1 w2 b2 w3 b3 inside one array
-  float* host;
-  float* dev;
-  // the normaliser (pbg_policy_set_obs_norm): mean [obs_dim] then inv_std [obs_dim], on the host and, for a
-  // device policy, on the device; norm_on 0 = none
-  float* norm_host;
-  float* norm_dev;
-  float clip;
-  int norm_on;
-  pbg_obs_stats* stats;  // attached (pbg_policy_attach_obs_stats), not owned
-};
-
-namespace {
-
-Weights weights_at(const pbg_policy* p, const float* base) {
-  return Weights{base + p->off[0], base + p->off[1], base + p->off[2], base + p->off[3], base + p->off[4],
-                 base + p->off[5], p->obs_dim, p->h1, p->h2, p->act_dim};
+// the actor's normaliser with its arrays at `base` (the device's, or a policy's host copy)
+Norm norm_of(const Actor& a, const float* base) {
+  if (!a.norm_on) return Norm{nullptr, nullptr, 0.f};
+  return Norm{base, base + a.obs_dim, a.clip};
 }
-
-Norm norm_at(const pbg_policy* p, const float* base) {
-  if (!p->norm_on) return Norm{nullptr, nullptr, 0.f};
-  return Norm{base, base + p->obs_dim, p->clip};
-}
-
-int launch_act(const pbg_policy* p, int n, const float* obs, float* act, float* obs_traj, float* act_traj,
-               const Book& bk, bool collect, hipStream_t stream) {
-  const unsigned grid = (unsigned)((n + PT - 1) / PT);
-  const Slot st = collect && p->stats ? p->stats->slot0() : Slot{nullptr, nullptr, nullptr};
-  const Norm nm = norm_at(p, p->norm_dev);
-  const Weights W = weights_at(p, p->dev);
-  switch (mode_of(nm, st)) {
-    case PLAIN:
-      hipLaunchKernelGGL(policy_act_kernel<PLAIN>, dim3(grid), dim3(PB), 0, stream, W, nm, st, n, obs, act, obs_traj, act_traj, bk);
-      break;
-    case NORM:
-      hipLaunchKernelGGL(policy_act_kernel<NORM>, dim3(grid), dim3(PB), 0, stream, W, nm, st, n, obs, act, obs_traj, act_traj, bk);
-      break;
-    case COLLECT:
-      hipLaunchKernelGGL(policy_act_kernel<COLLECT>, dim3(grid), dim3(PB), 0, stream, W, nm, st, n, obs, act, obs_traj, act_traj,
-                         bk);
-      break;
-  }
-  return (int)hipGetLastError();
-}
-
-int act_of_policy(const void* actor, int n, const float* obs, float* act, float* obs_traj, float* act_traj,
-                  const Book& bk, bool collect, hipStream_t stream) {
-  return launch_act(static_cast<const pbg_policy*>(actor), n, obs, act, obs_traj, act_traj, bk, collect, stream);
-}
-
-int hip_fail(int e, const char* what) {
-  char msg[160];
-  snprintf(msg, sizeof(msg), "%s: HIP error %d", what, e);
-  return pbg::capi_fail(PBG_E_HIP, msg);
-}
-
-using pbg::DeviceGuard;
 
 // the contract's chain on the CPU: y[j] = fmaf chain over k ascending from the bias
 void host_layer(const float* W, const float* b, int K, int H, bool relu, const float* x, float* y) {
@@ -116,57 +64,97 @@ void host_layer(const float* W, const float* b, int K, int H, bool relu, const f
 
 }  // namespace
 
+// an Actor with one member, plus the host's copies: pbg_policy_act_host and host-only policies run on them
+struct pbg_policy {
+  Actor a;
+  float* host;       // [D], the flat layout
+  float* norm_host;  // mean [obs_dim] then inv_std [obs_dim]
+};
+
+int pbg::policy::launch_actor(const Actor& a, int n, const float* obs, float* act, float* obs_traj, float* act_traj,
+                              const Book& bk, bool collect, hipStream_t stream) {
+  const int G = n / a.n_members;  // the callers have checked n % n_members == 0 and n > 0
+  const Norm nm = norm_of(a, a.norm);
+  const Slot st = collect && a.stats ? a.stats->slot0() : Slot{nullptr, nullptr, nullptr};
+  decltype(&actor_kernel<PLAIN>) kernel = nullptr;
+  switch (mode_of(nm, st)) {
+    case PLAIN: kernel = actor_kernel<PLAIN>; break;
+    case NORM: kernel = actor_kernel<NORM>; break;
+    case COLLECT: kernel = actor_kernel<COLLECT>; break;
+  }
+  hipLaunchKernelGGL(kernel, dim3((unsigned)tiles_of(n, G)), dim3(PB), 0, stream, a.params, a.obs_dim, a.h1, a.h2, a.act_dim, a.D,
+                     G, (G + PT - 1) / PT, nm, st, obs, act, obs_traj, act_traj, bk);
+  return (int)hipGetLastError();
+}
+
+int pbg::policy::actor_init(const char* who, Actor& a, int device, int obs_dim, int h1, int h2, int act_dim, int n_members) {
+  a = Actor{device, obs_dim, h1, h2, act_dim, n_members, param_count(obs_dim, h1, h2, act_dim), nullptr, nullptr, 0.f, 0, nullptr};
+  if (device < 0) return PBG_OK;
+  if (const int rc = check_device(who, device)) return rc;
+  DeviceGuard dg(device);
+  const size_t bytes = (size_t)n_members * a.D * sizeof(float), norm_bytes = (size_t)2 * obs_dim * sizeof(float);
+  int e = (int)hipMalloc(&a.params, bytes);
+  if (!e) e = (int)hipMemset(a.params, 0, bytes);
+  if (!e) e = (int)hipMalloc(&a.norm, norm_bytes);
+  if (!e) e = (int)hipMemset(a.norm, 0, norm_bytes);
+  if (!e) return PBG_OK;
+  actor_free(a);
+  char what[96];
+  snprintf(what, sizeof(what), "%s: actor storage", who);
+  return hip_fail(e, what);
+}
+
+void pbg::policy::actor_free(Actor& a) {
+  if (!a.params && !a.norm) return;
+  DeviceGuard dg(a.device);
+  (void)hipFree(a.params);
+  (void)hipFree(a.norm);
+  a.params = a.norm = nullptr;
+}
+
+int pbg::policy::norm_args(const char* who, Actor& a, const float* mean, const float* inv_std, float clip) {
+  if (!mean && !inv_std) {
+    a.norm_on = 0;
+    return 1;
+  }
+  char msg[128];
+  if (!mean || !inv_std) {
+    snprintf(msg, sizeof(msg), "%s: mean and inv_std must both be given (or both NULL)", who);
+    return pbg::capi_fail(PBG_E_ARG, msg);
+  }
+  if (clip > 0.f) return 0;
+  snprintf(msg, sizeof(msg), "%s: clip must be > 0", who);
+  return pbg::capi_fail(PBG_E_ARG, msg);
+}
+
 extern "C" {
 
 int pbg_policy_create(int device, int obs_dim, int h1, int h2, int act_dim, const float* w1, const float* b1,
                       const float* w2, const float* b2, const float* w3, const float* b3, pbg_policy** out) {
   if (!out) return pbg::capi_fail(PBG_E_ARG, "pbg_policy_create: out is NULL");
   *out = nullptr;
-  if (obs_dim < 1 || obs_dim > PBG_POLICY_MAX_DIM || h1 < 1 || h1 > PBG_POLICY_MAX_DIM || h2 < 1 ||
-      h2 > PBG_POLICY_MAX_DIM || act_dim < 1 || act_dim > PBG_POLICY_MAX_ACT) {
-    char msg[200];
-    snprintf(msg, sizeof(msg), "pbg_policy_create: dims (%d, %d, %d, %d) outside 1..%d (obs_dim, h1, h2), 1..%d (act_dim)",
-             obs_dim, h1, h2, act_dim, PBG_POLICY_MAX_DIM, PBG_POLICY_MAX_ACT);
-    return pbg::capi_fail(PBG_E_ARG, msg);
-  }
+  if (const int rc = check_dims("pbg_policy_create", obs_dim, h1, h2, act_dim)) return rc;
   if (!w1 || !b1 || !w2 || !b2 || !w3 || !b3) return pbg::capi_fail(PBG_E_ARG, "pbg_policy_create: NULL weight array");
   if (device < -1) return pbg::capi_fail(PBG_E_ARG, "pbg_policy_create: device must be >= 0, or -1 for a host-only policy");
   pbg_policy* p = new (std::nothrow) pbg_policy();
-  if (!p) return pbg::capi_fail(PBG_E_NOMEM, "pbg_policy_create: out of host memory");
-  p->device = device;
-  p->obs_dim = obs_dim; p->h1 = h1; p->h2 = h2; p->act_dim = act_dim;
-  const size_t cnt[6] = {(size_t)obs_dim * h1, (size_t)h1, (size_t)h1 * h2, (size_t)h2, (size_t)h2 * act_dim,
-                         (size_t)act_dim};
-  const float* src[6] = {w1, b1, w2, b2, w3, b3};
-  size_t at = 0;
-  for (int i = 0; i < 6; i++) {
-    p->off[i] = at;
-    at += (cnt[i] + 3) & ~(size_t)3;  // each array 16-byte aligned
-  }
-  p->words = at;
-  p->dev = nullptr;
-  p->norm_host = p->norm_dev = nullptr;
-  p->clip = 0.f;
-  p->norm_on = 0;
-  p->stats = nullptr;
-  p->host = (float*)calloc(at, sizeof(float));
-  if (!p->host) {
-    delete p;
+  const int D = param_count(obs_dim, h1, h2, act_dim);
+  if (p) p->host = (float*)calloc((size_t)D, sizeof(float));
+  if (p) p->norm_host = (float*)calloc((size_t)2 * obs_dim, sizeof(float));
+  if (!p || !p->host || !p->norm_host) {
+    pbg_policy_destroy(p);
     return pbg::capi_fail(PBG_E_NOMEM, "pbg_policy_create: out of host memory");
   }
-  for (int i = 0; i < 6; i++) memcpy(p->host + p->off[i], src[i], cnt[i] * sizeof(float));
+  const Weights H = weights_at(p->host, obs_dim, h1, h2, act_dim);
+  const float* src[6] = {w1, b1, w2, b2, w3, b3};
+  const float* dst[7] = {H.w1, H.b1, H.w2, H.b2, H.w3, H.b3, p->host + D};
+  for (int i = 0; i < 6; i++) memcpy(p->host + (dst[i] - dst[0]), src[i], (size_t)(dst[i + 1] - dst[i]) * sizeof(float));
+  if (const int rc = actor_init("pbg_policy_create", p->a, device, obs_dim, h1, h2, act_dim, 1)) {
+    pbg_policy_destroy(p);
+    return rc;
+  }
   if (device >= 0) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device >= ndev) {
-      (void)hipGetLastError();
-      pbg_policy_destroy(p);
-      char msg[64];
-      snprintf(msg, sizeof(msg), "pbg_policy_create: no HIP device %d", device);
-      return pbg::capi_fail(PBG_E_HIP, msg);
-    }
     DeviceGuard dg(device);
-    int e = (int)hipMalloc(&p->dev, at * sizeof(float));
-    if (!e) e = (int)hipMemcpy(p->dev, p->host, at * sizeof(float), hipMemcpyHostToDevice);
+    const int e = (int)hipMemcpy(p->a.params, p->host, (size_t)D * sizeof(float), hipMemcpyHostToDevice);
     if (e) {
       pbg_policy_destroy(p);
       return hip_fail(e, "pbg_policy_create: weight upload");
@@ -178,14 +166,7 @@ int pbg_policy_create(int device, int obs_dim, int h1, int h2, int act_dim, cons
 
 void pbg_policy_destroy(pbg_policy* p) {
   if (!p) return;
-  if (p->dev) {
-    DeviceGuard dg(p->device);
-    (void)hipFree(p->dev);
-  }
-  if (p->norm_dev) {
-    DeviceGuard dg(p->device);
-    (void)hipFree(p->norm_dev);
-  }
+  actor_free(p->a);
   free(p->norm_host);
   free(p->host);
   delete p;
@@ -193,47 +174,38 @@ void pbg_policy_destroy(pbg_policy* p) {
 
 int pbg_policy_set_obs_norm(pbg_policy* p, const float* mean, const float* inv_std, float clip) {
   if (!p) return pbg::capi_fail(PBG_E_ARG, "pbg_policy_set_obs_norm: policy is NULL");
-  if (!mean && !inv_std) {
-    p->norm_on = 0;
-    return PBG_OK;
-  }
-  if (!mean || !inv_std) return pbg::capi_fail(PBG_E_ARG, "pbg_policy_set_obs_norm: mean and inv_std must both be given (or both NULL)");
-  if (!(clip > 0.f)) return pbg::capi_fail(PBG_E_ARG, "pbg_policy_set_obs_norm: clip must be > 0");
-  const size_t K = (size_t)p->obs_dim;
-  if (!p->norm_host) {
-    p->norm_host = (float*)calloc(2 * K, sizeof(float));
-    if (!p->norm_host) return pbg::capi_fail(PBG_E_NOMEM, "pbg_policy_set_obs_norm: out of host memory");
-  }
-  if (p->device >= 0) {
+  const int r = norm_args("pbg_policy_set_obs_norm", p->a, mean, inv_std, clip);
+  if (r) return r > 0 ? PBG_OK : r;
+  const size_t K = (size_t)p->a.obs_dim;
+  if (p->a.device >= 0) {
     // a launch enqueued earlier may still read the device copy: upload through the (synchronous) null-stream
     // copy into place only after every stream of the device has drained
-    DeviceGuard dg(p->device);
-    int e = p->norm_dev ? 0 : (int)hipMalloc(&p->norm_dev, 2 * K * sizeof(float));
-    if (!e) e = (int)hipDeviceSynchronize();
-    if (!e) e = (int)hipMemcpy(p->norm_dev, mean, K * sizeof(float), hipMemcpyHostToDevice);
-    if (!e) e = (int)hipMemcpy(p->norm_dev + K, inv_std, K * sizeof(float), hipMemcpyHostToDevice);
+    DeviceGuard dg(p->a.device);
+    int e = (int)hipDeviceSynchronize();
+    if (!e) e = (int)hipMemcpy(p->a.norm, mean, K * sizeof(float), hipMemcpyHostToDevice);
+    if (!e) e = (int)hipMemcpy(p->a.norm + K, inv_std, K * sizeof(float), hipMemcpyHostToDevice);
     if (e) {
-      p->norm_on = 0;
+      p->a.norm_on = 0;
       return hip_fail(e, "pbg_policy_set_obs_norm: upload");
     }
   }
   memcpy(p->norm_host, mean, K * sizeof(float));
   memcpy(p->norm_host + K, inv_std, K * sizeof(float));
-  p->clip = clip;
-  p->norm_on = 1;
+  p->a.clip = clip;
+  p->a.norm_on = 1;
   return PBG_OK;
 }
 
 int pbg_policy_attach_obs_stats(pbg_policy* p, pbg_obs_stats* s) {
   if (!p) return pbg::capi_fail(PBG_E_ARG, "pbg_policy_attach_obs_stats: policy is NULL");
-  p->stats = s;
+  p->a.stats = s;
   return PBG_OK;
 }
 
 int pbg_policy_act_host(const pbg_policy* p, int n, const float* obs, float* act) {
   if (!p || n < 0 || (n > 0 && (!obs || !act))) return pbg::capi_fail(PBG_E_ARG, "pbg_policy_act_host: bad arguments");
-  const Weights P = weights_at(p, p->host);
-  const Norm nm = norm_at(p, p->norm_host);
+  const Weights P = weights_at(p->host, p->a.obs_dim, p->a.h1, p->a.h2, p->a.act_dim);
+  const Norm nm = norm_of(p->a, p->norm_host);
   float a[PBG_POLICY_MAX_DIM], b[PBG_POLICY_MAX_DIM];
   for (int i = 0; i < n; i++) {
     const float* x = obs + (size_t)i * P.obs_dim;
@@ -250,28 +222,26 @@ int pbg_policy_act_host(const pbg_policy* p, int n, const float* obs, float* act
 
 int pbg_policy_act(const pbg_policy* p, int n, const float* obs, float* act, void* stream) {
   if (!p) return pbg::capi_fail(PBG_E_ARG, "pbg_policy_act: policy is NULL");
-  if (p->device < 0 || !p->dev)
+  if (p->a.device < 0)
     return pbg::capi_fail(PBG_E_ARG, "pbg_policy_act: host-only policy (device -1): use pbg_policy_act_host");
   if (n < 0 || (n > 0 && (!obs || !act))) return pbg::capi_fail(PBG_E_ARG, "pbg_policy_act: bad arguments");
   if (n == 0) return PBG_OK;
-  DeviceGuard dg(p->device);
+  DeviceGuard dg(p->a.device);
   Book none;
   memset(&none, 0, sizeof(none));
-  const int e = launch_act(p, n, obs, act, nullptr, nullptr, none, false, (hipStream_t)stream);
-  return e ? hip_fail(e, "policy_act_kernel launch") : PBG_OK;
+  const int e = launch_actor(p->a, n, obs, act, nullptr, nullptr, none, false, (hipStream_t)stream);
+  return e ? hip_fail(e, "actor_kernel launch") : PBG_OK;
 }
 
 int pbg_rollout(pbg_handle* h, const pbg_policy* p, const pbg_rollout_io_t* uio, void* stream) {
   if (!h || !p || !uio) return pbg::capi_fail(PBG_E_ARG, "pbg_rollout: NULL handle, policy or io");
-  if (p->device < 0 || !p->dev) return pbg::capi_fail(PBG_E_ARG, "pbg_rollout: host-only policy");
-  return rollout_loop("pbg_rollout", h, uio, stream, p->device, p->obs_dim, p->act_dim, 1, act_of_policy, p, p->stats);
+  if (p->a.device < 0) return pbg::capi_fail(PBG_E_ARG, "pbg_rollout: host-only policy");
+  return rollout_loop("pbg_rollout", h, uio, stream, p->a);
 }
 
 }  // extern "C"
 
-int pbg::policy::rollout_loop(const char* who, pbg_handle* h, const pbg_rollout_io_t* uio, void* stream, int actor_device,
-                              int obs_dim, int act_dim, int group, ActLaunch launch, const void* actor,
-                              const pbg_obs_stats* stats) {
+int pbg::policy::rollout_loop(const char* who, pbg_handle* h, const pbg_rollout_io_t* uio, void* stream, const Actor& a) {
   char msg[200];
   // versioned like pbg_create_opts_t: the first version ends with done_traj; read only what the caller's
   // struct holds, fields appended later take zero (their default) for an older caller
@@ -285,27 +255,28 @@ int pbg::policy::rollout_loop(const char* who, pbg_handle* h, const pbg_rollout_
   memcpy(&io_copy, uio, uio->struct_size);
   const pbg_rollout_io_t* io = &io_copy;
   const int dev = pbg::handle_device(h);
-  if (actor_device != dev) {
+  if (a.device != dev) {
     snprintf(msg, sizeof(msg), "%s: the policy lives on another device than the handle", who);
     return pbg::capi_fail(PBG_E_ARG, msg);
   }
   pbg_info_t info;
   if (pbg_info(h, &info)) return PBG_E_ARG;
-  if (obs_dim != info.obs_dim || act_dim != info.action_dim) {
-    snprintf(msg, sizeof(msg), "%s: policy maps %d -> %d, the env's obs_dim / action_dim are %d / %d", who, obs_dim,
-             act_dim, info.obs_dim, info.action_dim);
+  if (a.obs_dim != info.obs_dim || a.act_dim != info.action_dim) {
+    snprintf(msg, sizeof(msg), "%s: policy maps %d -> %d, the env's obs_dim / action_dim are %d / %d", who, a.obs_dim,
+             a.act_dim, info.obs_dim, info.action_dim);
     return pbg::capi_fail(PBG_E_ARG, msg);
   }
-  if (group > 1 && info.n_envs % group != 0) {
+  if (info.n_envs % a.n_members != 0) {
     snprintf(msg, sizeof(msg), "%s: the handle's %d envs are not a multiple of the population's %d members", who,
-             info.n_envs, group);
+             info.n_envs, a.n_members);
     return pbg::capi_fail(PBG_E_ARG, msg);
   }
-  if (stats) {
-    const long long need = tiles_of(info.n_envs, info.n_envs / (group > 1 ? group : 1));
-    if (stats->device != dev || stats->obs_dim != obs_dim || (long long)stats->n_slots < need) {
+  if (a.stats) {
+    const long long need = tiles_of(info.n_envs, info.n_envs / a.n_members);
+    if (a.stats->device != dev || a.stats->obs_dim != a.obs_dim || (long long)a.stats->n_slots < need) {
       snprintf(msg, sizeof(msg), "%s: the attached obs stats (device %d, obs_dim %d, %d slots) do not fit device %d, obs_dim "
-               "%d and the actor's %lld workgroups", who, stats->device, stats->obs_dim, stats->n_slots, dev, obs_dim, need);
+               "%d and the actor's %lld workgroups", who, a.stats->device, a.stats->obs_dim, a.stats->n_slots, dev, a.obs_dim,
+               need);
       return pbg::capi_fail(PBG_E_ARG, msg);
     }
   }
@@ -332,8 +303,8 @@ int pbg::policy::rollout_loop(const char* who, pbg_handle* h, const pbg_rollout_
   st.autoreset = io->autoreset ? 1 : 0;
   for (int t = 0; t < io->n_steps; t++) {
     // actor: the bookkeeping of step t - 1, then act = pi(obs)
-    int e = launch(actor, n, io->obs, io->act, io->obs_traj ? io->obs_traj + (size_t)t * no : nullptr,
-                   io->act_traj ? io->act_traj + (size_t)t * na : nullptr, bk, stats != nullptr, s);
+    int e = launch_actor(a, n, io->obs, io->act, io->obs_traj ? io->obs_traj + (size_t)t * no : nullptr,
+                         io->act_traj ? io->act_traj + (size_t)t * na : nullptr, bk, a.stats != nullptr, s);
     if (e) return hip_fail(e, "actor kernel launch");
     // the step writes reward and done straight into the trajectory rows when there are any
     st.rew = io->rew_traj ? io->rew_traj + (size_t)t * n : io->rew;

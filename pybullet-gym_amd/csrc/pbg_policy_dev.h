@@ -1,8 +1,9 @@
-// pbg_policy_dev.h -- what the two actor translation units share: the MLP tile (pbg_policy.hip's
-// policy_act_kernel evaluates it with one weight set for every workgroup, pbg_population.hip's
-// population_act_kernel with the workgroup's own member's), the rollout bookkeeping and the rollout
-// loop itself (pbg_rollout and pbg_rollout_population enqueue the same 2 T + 1 launches and differ in
-// the actor launch only).
+// pbg_policy_dev.h -- what the actor translation units (pbg_policy.hip, pbg_population.hip, pbg_obsnorm.hip)
+// share: the description of an actor (Actor: a pbg_policy is one with a single member whose group is the
+// whole batch, a pbg_population one with 2 n_pairs), the MLP tile that pbg_policy.hip's actor_kernel
+// evaluates with the workgroup's member's weights, the rollout bookkeeping, the one actor launch and the
+// rollout loop (pbg_rollout and pbg_rollout_population are the same 2 T + 1 launches), and the host helpers
+// of the three objects.
 //
 // Numeric contract (pbg.h): out[j] = fmaf-chain over k ascending, started from b[j]; ReLU as
 // `v < 0 ? 0 : v`.  One fma per (k, j, env), nothing split over k, nothing left for the compiler to
@@ -17,11 +18,12 @@
 //
 // Observation normalisation and statistics (pbg.h "Running observation normalisation", DESIGN.md section
 // 12): normalise() is the one spelling of the transform, host and device; stats_tile() the one spelling of
-// the tile accumulation, used by both actors and by pbg_obsnorm.hip's stand-alone kernel.
+// the tile accumulation, used by the actor and by pbg_obsnorm.hip's stand-alone kernel.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+#include <stdio.h>
 
 #include "pbg_internal.h"
 
@@ -67,6 +69,25 @@ struct Weights {
   int obs_dim, h1, h2, act_dim;
 };
 
+// pbg.h "Flat parameter layout": a weight set is the unpadded concatenation w1 b1 w2 b2 w3 b3 from `base`
+// (layer_cols reads one float per lane, so no array needs an alignment), host or device
+__host__ __device__ __forceinline__ Weights weights_at(const float* base, int obs_dim, int h1, int h2, int act_dim) {
+  Weights W;
+  W.obs_dim = obs_dim; W.h1 = h1; W.h2 = h2; W.act_dim = act_dim;
+  W.w1 = base;
+  W.b1 = W.w1 + obs_dim * h1;
+  W.w2 = W.b1 + h1;
+  W.b2 = W.w2 + h1 * h2;
+  W.w3 = W.b2 + h2;
+  W.b3 = W.w3 + h2 * act_dim;
+  return W;
+}
+
+// D, the floats of one weight set: where weights_at's last array ends
+inline int param_count(int obs_dim, int h1, int h2, int act_dim) {
+  return obs_dim * h1 + h1 + h1 * h2 + h2 + h2 * act_dim + act_dim;
+}
+
 // an actor's normaliser: mean, inv_std [obs_dim] (device pointers in a kernel); mean NULL = none
 struct Norm {
   const float* mean;
@@ -87,6 +108,23 @@ struct Slot {
   int64_t* count;
   double* sum;    // [K]
   double* sumsq;  // [K]
+};
+
+// An actor: n_members weight sets of one MLP shape on one device, the normaliser they share and the
+// statistics attached to them.  A launch over n rows cuts them into n_members groups of G = n / n_members
+// consecutive rows, group m runs member m (a pbg_policy: one member, G = n).
+struct Actor {
+  int device;  // -1: host only (a pbg_policy), nothing below `D` is allocated
+  int obs_dim, h1, h2, act_dim;
+  int n_members;
+  int D;          // parameters per member
+  float* params;  // device [n_members, D], each row in the flat layout
+  // the normaliser (pbg_*_set_obs_norm): device mean [obs_dim] then inv_std [obs_dim], allocated with the
+  // parameters; norm_on 0 = none
+  float* norm;
+  float clip;
+  int norm_on;
+  pbg_obs_stats* stats;  // attached (pbg_*_attach_obs_stats), not owned
 };
 
 // slot b of the object whose slot 0 is `base` (K = obs_dim)
@@ -260,22 +298,69 @@ __device__ __forceinline__ void act_tile(const Weights P, const Norm nm, const S
   }
 }
 
-// The actor launch of a rollout: act = pi(obs) for the handle's n envs after the bookkeeping `bk`,
-// enqueued on `stream`; returns the hipError_t of the launch.
-// `collect`: accumulate the actor's attached statistics (rollout steps only; the loop has validated them).
-typedef int (*ActLaunch)(const void* actor, int n, const float* obs, float* act, float* obs_traj, float* act_traj,
-                         const Book& bk, bool collect, hipStream_t stream);
-
-// The closed loop of pbg_rollout / pbg_rollout_population (pbg_policy.hip): validates `io` against the
-// handle and the actor's device and dims, then enqueues per step the actor and the handle's step, and
-// one closing bookkeeping launch.  `who` names the entry point in error messages; `group` > 1: the
-// handle's n_envs must be a multiple of it (the population's member count).  `stats`: the actor's attached
-// statistics or NULL; refused unless on the actor's device, of its obs_dim and with a slot per workgroup.
-int rollout_loop(const char* who, pbg_handle* h, const pbg_rollout_io_t* io, void* stream, int actor_device,
-                 int obs_dim, int act_dim, int group, ActLaunch launch, const void* actor, const pbg_obs_stats* stats);
-
 // workgroups (= slots) of an actor launch over n rows in groups of G (n a multiple of G > 0)
 inline long long tiles_of(int n, int G) { return (long long)(n / G) * ((G + PT - 1) / PT); }
+
+// Workgroup b of such a launch, tpm = ceil(G / PT) tiles per group: tile t = b % tpm of group m = b / tpm owns
+// rows row0 = m G + t PT .. row0 + rows; the last tile of a group whose G is no multiple of PT has fewer rows.
+struct Tile {
+  int m, row0, rows;
+};
+
+__device__ __forceinline__ Tile tile_of(unsigned b, int G, int tpm) {
+  const int m = b / (unsigned)tpm, t = b - m * tpm;  // unsigned: no sign fix-up around the uniform division
+  return Tile{m, m * G + t * PT, min(PT, G - t * PT)};
+}
+
+// The one actor launch (pbg_policy.hip): act = pi_m(obs) for n rows (n > 0, a multiple of a.n_members) after
+// the bookkeeping `bk`, enqueued on `stream`; returns the hipError_t of the launch.
+// `collect`: accumulate the actor's attached statistics (rollout steps only; the loop has validated them).
+int launch_actor(const Actor& a, int n, const float* obs, float* act, float* obs_traj, float* act_traj, const Book& bk,
+                 bool collect, hipStream_t stream);
+
+// The closed loop of pbg_rollout / pbg_rollout_population (pbg_policy.hip): validates `io` against the
+// handle and the actor's device and dims (the handle's n_envs a multiple of the actor's members; attached
+// statistics on the actor's device, of its obs_dim and with a slot per workgroup), then enqueues per step the
+// actor and the handle's step, and one closing bookkeeping launch.  `who` names the entry point in error
+// messages.
+int rollout_loop(const char* who, pbg_handle* h, const pbg_rollout_io_t* io, void* stream, const Actor& a);
+
+// ---------------------------------------------------------------- host helpers of the three objects
+inline int hip_fail(int e, const char* what) {
+  char msg[160];
+  snprintf(msg, sizeof(msg), "%s: HIP error %d", what, e);
+  return pbg::capi_fail(PBG_E_HIP, msg);
+}
+
+// PBG_OK when HIP device `device` exists
+inline int check_device(const char* who, int device) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) == hipSuccess && device < ndev) return PBG_OK;
+  (void)hipGetLastError();
+  char msg[96];
+  snprintf(msg, sizeof(msg), "%s: no HIP device %d", who, device);
+  return pbg::capi_fail(PBG_E_HIP, msg);
+}
+
+// PBG_OK when the four dims are inside pbg_policy_create's ranges
+inline int check_dims(const char* who, int obs_dim, int h1, int h2, int act_dim) {
+  if (obs_dim >= 1 && obs_dim <= PBG_POLICY_MAX_DIM && h1 >= 1 && h1 <= PBG_POLICY_MAX_DIM && h2 >= 1 &&
+      h2 <= PBG_POLICY_MAX_DIM && act_dim >= 1 && act_dim <= PBG_POLICY_MAX_ACT)
+    return PBG_OK;
+  char msg[200];
+  snprintf(msg, sizeof(msg), "%s: dims (%d, %d, %d, %d) outside 1..%d (obs_dim, h1, h2), 1..%d (act_dim)", who, obs_dim, h1,
+           h2, act_dim, PBG_POLICY_MAX_DIM, PBG_POLICY_MAX_ACT);
+  return pbg::capi_fail(PBG_E_ARG, msg);
+}
+
+// An actor's dims, member count and (zeroed) device storage; device < 0: the dims only.  PBG_OK, or the
+// failure with nothing left allocated.
+int actor_init(const char* who, Actor& a, int device, int obs_dim, int h1, int h2, int act_dim, int n_members);
+void actor_free(Actor& a);
+
+// What both pbg_*_set_obs_norm check before they copy: 1 = both arrays NULL, the normaliser is now off;
+// 0 = go on: copy them, then set a.clip and a.norm_on; < 0 = refused
+int norm_args(const char* who, Actor& a, const float* mean, const float* inv_std, float clip);
 
 }  // namespace policy
 }  // namespace pbg

@@ -2,9 +2,9 @@
 // pbg_population_*, pbg_rollout_population).  A population is P = 2 n_pairs weight sets of one MLP shape
 // in device memory, member m's flat parameter vector at members + m D (pbg.h "Flat parameter layout").
 //
-// The actor (population_act_kernel) is pbg_policy.hip's tile (pbg_policy_dev.h act_tile: 256 lanes, 16
-// envs, the same k-ascending fma chain) with the grid over (member, tile of that member's G envs): a tile
-// never straddles two members and the workgroup's weight pointers start at its member.  The once-per-
+// The actor is pbg_policy.hip's (pbg_policy_dev.h Actor, launch_actor): the grid over (member, tile of that
+// member's G envs), so a tile never straddles two members and the workgroup's weight pointers start at its
+// member; a population adds only its pair bookkeeping to the Actor.  The once-per-
 // generation kernels (noise, perturb, grad, fitness, member copies) are written for the stated summation
 // order, not for speed.
 //
@@ -24,18 +24,10 @@
 #include "pbg_es_noise.h"
 #include "pbg_policy_dev.h"
 
+// an Actor of 2 n_pairs members (a.params: member m's vector at m D) and the global index of its first pair
 struct pbg_population {
-  int device;
-  int obs_dim, h1, h2, act_dim;
+  pbg::policy::Actor a;
   int n_pairs, pair0;
-  int D;           // parameters per member
-  float* members;  // device [2 n_pairs, D]
-  // the normaliser every member shares (pbg_population_set_obs_norm): device mean [obs_dim] then inv_std
-  // [obs_dim], allocated with the members; norm_on 0 = none
-  float* norm;
-  float clip;
-  int norm_on;
-  pbg_obs_stats* stats;  // attached (pbg_population_attach_obs_stats), not owned
 };
 
 namespace {
@@ -43,14 +35,6 @@ namespace {
 using namespace pbg::policy;
 using namespace pbg::es;  // es_box_muller, es_normals4, ES_TAG (pbg_es_noise.h)
 using pbg::DeviceGuard;
-
-struct Dims {
-  int obs_dim, h1, h2, act_dim;
-};
-
-__host__ __device__ inline int param_count(const Dims& d) {
-  return d.obs_dim * d.h1 + d.h1 + d.h1 * d.h2 + d.h2 + d.h2 * d.act_dim + d.act_dim;
-}
 
 // grid (n_pairs, ceil(nb / 256)): a lane per (pair, block of 4 parameters)
 __global__ __launch_bounds__(256) void noise_kernel(int D, uint32_t k0, uint32_t k1, uint32_t pair0, uint32_t generation,
@@ -129,84 +113,10 @@ __global__ __launch_bounds__(256) void copy_rows_kernel(int D, size_t src_stride
   if (d < D) dst[(size_t)blockIdx.x * D + d] = src[(size_t)blockIdx.x * src_stride + d];
 }
 
-// ---------------------------------------------------------------- actor
-// grid = P * tpm workgroups, tpm = ceil(G / PT) tiles per member: workgroup (m, t) owns envs
-// m G + t PT .. + rows of member m; the last tile of a member whose G is no multiple of PT has fewer rows
-// (zero-filled in LDS, nothing read or written past them).
-// nm / st / MODE: the population's normaliser, slot 0 of the statistics to collect into and the instantiation,
-// as policy_act_kernel's.
-template <int MODE>
-__global__ __launch_bounds__(PB) void population_act_kernel(const float* __restrict__ members, Dims dm, int D, int G, int tpm,
-                                                            Norm nm, Slot st,
-                                                            const float* __restrict__ obs, float* __restrict__ act,
-                                                            float* __restrict__ obs_traj, float* __restrict__ act_traj,
-                                                            Book bk) {
-  __shared__ __attribute__((aligned(16))) float bufA[PD * PT];
-  __shared__ __attribute__((aligned(16))) float bufB[PD * PT];
-  const int m = blockIdx.x / tpm;
-  const int t = blockIdx.x - m * tpm;
-  const float* base = members + (size_t)m * D;
-  Weights W;
-  W.obs_dim = dm.obs_dim; W.h1 = dm.h1; W.h2 = dm.h2; W.act_dim = dm.act_dim;
-  W.w1 = base;
-  W.b1 = W.w1 + dm.obs_dim * dm.h1;
-  W.w2 = W.b1 + dm.h1;
-  W.b2 = W.w2 + dm.h1 * dm.h2;
-  W.w3 = W.b2 + dm.h2;
-  W.b3 = W.w3 + dm.h2 * dm.act_dim;
-  act_tile<MODE>(W, nm, slot_at(st, dm.obs_dim, blockIdx.x), m * G + t * PT, min(PT, G - t * PT), obs, act, obs_traj, act_traj, bk,
-           bufA, bufB);
-}
-
-int launch_population_act(const void* actor, int n, const float* obs, float* act, float* obs_traj, float* act_traj,
-                          const Book& bk, bool collect, hipStream_t stream) {
-  const pbg_population* p = static_cast<const pbg_population*>(actor);
-  const int P = 2 * p->n_pairs;
-  const int G = n / P;  // the callers have checked n % P == 0 and n > 0
-  const int tpm = (G + PT - 1) / PT;
-  const Dims dm{p->obs_dim, p->h1, p->h2, p->act_dim};
-  const Norm nm = p->norm_on ? Norm{p->norm, p->norm + p->obs_dim, p->clip} : Norm{nullptr, nullptr, 0.f};
-  const Slot st = collect && p->stats ? p->stats->slot0() : Slot{nullptr, nullptr, nullptr};
-  const dim3 grid((unsigned)P * (unsigned)tpm);
-  switch (mode_of(nm, st)) {
-    case PLAIN:
-      hipLaunchKernelGGL(population_act_kernel<PLAIN>, grid, dim3(PB), 0, stream, p->members, dm, p->D, G, tpm, nm, st, obs, act,
-                         obs_traj, act_traj, bk);
-      break;
-    case NORM:
-      hipLaunchKernelGGL(population_act_kernel<NORM>, grid, dim3(PB), 0, stream, p->members, dm, p->D, G, tpm, nm, st, obs, act,
-                         obs_traj, act_traj, bk);
-      break;
-    case COLLECT:
-      hipLaunchKernelGGL(population_act_kernel<COLLECT>, grid, dim3(PB), 0, stream, p->members, dm, p->D, G, tpm, nm, st, obs, act,
-                         obs_traj, act_traj, bk);
-      break;
-  }
-  return (int)hipGetLastError();
-}
-
 // ---------------------------------------------------------------- host side
-int hip_fail(int e, const char* what) {
-  char msg[160];
-  snprintf(msg, sizeof(msg), "%s: HIP error %d", what, e);
-  return pbg::capi_fail(PBG_E_HIP, msg);
-}
-
 int launched(const char* what) {
   const int e = (int)hipGetLastError();
   return e ? hip_fail(e, what) : PBG_OK;
-}
-
-bool dims_ok(int obs_dim, int h1, int h2, int act_dim) {
-  return obs_dim >= 1 && obs_dim <= PBG_POLICY_MAX_DIM && h1 >= 1 && h1 <= PBG_POLICY_MAX_DIM && h2 >= 1 &&
-         h2 <= PBG_POLICY_MAX_DIM && act_dim >= 1 && act_dim <= PBG_POLICY_MAX_ACT;
-}
-
-int bad_dims(const char* who, int obs_dim, int h1, int h2, int act_dim) {
-  char msg[200];
-  snprintf(msg, sizeof(msg), "%s: dims (%d, %d, %d, %d) outside 1..%d (obs_dim, h1, h2), 1..%d (act_dim)", who, obs_dim, h1,
-           h2, act_dim, PBG_POLICY_MAX_DIM, PBG_POLICY_MAX_ACT);
-  return pbg::capi_fail(PBG_E_ARG, msg);
 }
 
 // the largest population whose member count and whose global pair indices stay inside an int
@@ -233,7 +143,7 @@ void host_box_muller(uint32_t a, uint32_t b, float* n0, float* n1) {
   *n1 = (float)(r * sin(ang));
 }
 
-dim3 pair_grid(const pbg_population* p) { return dim3((unsigned)p->n_pairs, (unsigned)(((p->D + 3) / 4 + 255) / 256)); }
+dim3 pair_grid(const pbg_population* p) { return dim3((unsigned)p->n_pairs, (unsigned)(((p->a.D + 3) / 4 + 255) / 256)); }
 
 }  // namespace
 
@@ -243,7 +153,7 @@ int pbg_population_create(int device, int obs_dim, int h1, int h2, int act_dim, 
                           pbg_population** out) {
   if (!out) return pbg::capi_fail(PBG_E_ARG, "pbg_population_create: out is NULL");
   *out = nullptr;
-  if (!dims_ok(obs_dim, h1, h2, act_dim)) return bad_dims("pbg_population_create", obs_dim, h1, h2, act_dim);
+  if (const int rc = check_dims("pbg_population_create", obs_dim, h1, h2, act_dim)) return rc;
   if (!pairs_ok(n_pairs, pair0)) {
     char msg[160];
     snprintf(msg, sizeof(msg), "pbg_population_create: n_pairs %d must be >= 1 and pair0 %d >= 0 (and their sum an int)",
@@ -251,34 +161,13 @@ int pbg_population_create(int device, int obs_dim, int h1, int h2, int act_dim, 
     return pbg::capi_fail(PBG_E_ARG, msg);
   }
   if (device < 0) return pbg::capi_fail(PBG_E_ARG, "pbg_population_create: device must be >= 0 (the members live on a GPU)");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device >= ndev) {
-    (void)hipGetLastError();
-    char msg[64];
-    snprintf(msg, sizeof(msg), "pbg_population_create: no HIP device %d", device);
-    return pbg::capi_fail(PBG_E_HIP, msg);
-  }
   pbg_population* p = new (std::nothrow) pbg_population();
   if (!p) return pbg::capi_fail(PBG_E_NOMEM, "pbg_population_create: out of host memory");
-  p->device = device;
-  p->obs_dim = obs_dim; p->h1 = h1; p->h2 = h2; p->act_dim = act_dim;
   p->n_pairs = n_pairs;
   p->pair0 = pair0;
-  p->D = param_count(Dims{obs_dim, h1, h2, act_dim});
-  p->members = nullptr;
-  p->norm = nullptr;
-  p->clip = 0.f;
-  p->norm_on = 0;
-  p->stats = nullptr;
-  DeviceGuard dg(device);
-  const size_t bytes = (size_t)2 * n_pairs * p->D * sizeof(float);
-  int e = (int)hipMalloc(&p->members, bytes);
-  if (!e) e = (int)hipMemset(p->members, 0, bytes);
-  if (!e) e = (int)hipMalloc(&p->norm, (size_t)2 * obs_dim * sizeof(float));
-  if (!e) e = (int)hipMemset(p->norm, 0, (size_t)2 * obs_dim * sizeof(float));
-  if (e) {
-    pbg_population_destroy(p);
-    return hip_fail(e, "pbg_population_create: member storage");
+  if (const int rc = actor_init("pbg_population_create", p->a, device, obs_dim, h1, h2, act_dim, 2 * n_pairs)) {
+    delete p;
+    return rc;
   }
   *out = p;
   return PBG_OK;
@@ -286,48 +175,36 @@ int pbg_population_create(int device, int obs_dim, int h1, int h2, int act_dim, 
 
 void pbg_population_destroy(pbg_population* p) {
   if (!p) return;
-  if (p->members) {
-    DeviceGuard dg(p->device);
-    (void)hipFree(p->members);
-  }
-  if (p->norm) {
-    DeviceGuard dg(p->device);
-    (void)hipFree(p->norm);
-  }
+  actor_free(p->a);
   delete p;
 }
 
 int pbg_population_set_obs_norm(pbg_population* p, const float* mean, const float* inv_std, float clip, void* stream) {
   if (!p) return pbg::capi_fail(PBG_E_ARG, "pbg_population_set_obs_norm: population is NULL");
-  if (!mean && !inv_std) {
-    p->norm_on = 0;
-    return PBG_OK;
-  }
-  if (!mean || !inv_std)
-    return pbg::capi_fail(PBG_E_ARG, "pbg_population_set_obs_norm: mean and inv_std must both be given (or both NULL)");
-  if (!(clip > 0.f)) return pbg::capi_fail(PBG_E_ARG, "pbg_population_set_obs_norm: clip must be > 0");
-  DeviceGuard dg(p->device);
-  const size_t bytes = (size_t)p->obs_dim * sizeof(float);
-  int e = (int)hipMemcpyAsync(p->norm, mean, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream);
-  if (!e) e = (int)hipMemcpyAsync(p->norm + p->obs_dim, inv_std, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+  const int r = norm_args("pbg_population_set_obs_norm", p->a, mean, inv_std, clip);
+  if (r) return r > 0 ? PBG_OK : r;
+  DeviceGuard dg(p->a.device);
+  const size_t bytes = (size_t)p->a.obs_dim * sizeof(float);
+  int e = (int)hipMemcpyAsync(p->a.norm, mean, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+  if (!e) e = (int)hipMemcpyAsync(p->a.norm + p->a.obs_dim, inv_std, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream);
   if (e) return hip_fail(e, "pbg_population_set_obs_norm: copy");
-  p->clip = clip;
-  p->norm_on = 1;
+  p->a.clip = clip;
+  p->a.norm_on = 1;
   return PBG_OK;
 }
 
 int pbg_population_attach_obs_stats(pbg_population* p, pbg_obs_stats* s) {
   if (!p) return pbg::capi_fail(PBG_E_ARG, "pbg_population_attach_obs_stats: population is NULL");
-  p->stats = s;
+  p->a.stats = s;
   return PBG_OK;
 }
 
 int pbg_population_noise_host(int obs_dim, int h1, int h2, int act_dim, uint64_t seed, uint32_t generation, int pair0,
                               int n_pairs, float* eps_out) {
-  if (!dims_ok(obs_dim, h1, h2, act_dim)) return bad_dims("pbg_population_noise_host", obs_dim, h1, h2, act_dim);
+  if (const int rc = check_dims("pbg_population_noise_host", obs_dim, h1, h2, act_dim)) return rc;
   if (!pairs_ok(n_pairs, pair0) || !eps_out)
     return pbg::capi_fail(PBG_E_ARG, "pbg_population_noise_host: n_pairs must be >= 1, pair0 >= 0 and eps_out not NULL");
-  const int D = param_count(Dims{obs_dim, h1, h2, act_dim});
+  const int D = param_count(obs_dim, h1, h2, act_dim);
   const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
   for (int i = 0; i < n_pairs; i++) {
     float* row = eps_out + (size_t)i * D;
@@ -345,8 +222,8 @@ int pbg_population_noise_host(int obs_dim, int h1, int h2, int act_dim, uint64_t
 
 int pbg_population_noise(const pbg_population* p, uint64_t seed, uint32_t generation, float* eps_out, void* stream) {
   if (!p || !eps_out) return pbg::capi_fail(PBG_E_ARG, "pbg_population_noise: NULL population or eps_out");
-  DeviceGuard dg(p->device);
-  hipLaunchKernelGGL(noise_kernel, pair_grid(p), dim3(256), 0, (hipStream_t)stream, p->D, (uint32_t)seed,
+  DeviceGuard dg(p->a.device);
+  hipLaunchKernelGGL(noise_kernel, pair_grid(p), dim3(256), 0, (hipStream_t)stream, p->a.D, (uint32_t)seed,
                      (uint32_t)(seed >> 32), (uint32_t)p->pair0, generation, eps_out);
   return launched("noise_kernel launch");
 }
@@ -354,75 +231,74 @@ int pbg_population_noise(const pbg_population* p, uint64_t seed, uint32_t genera
 int pbg_population_perturb(pbg_population* p, const float* theta, float sigma, uint64_t seed, uint32_t generation,
                            void* stream) {
   if (!p || !theta) return pbg::capi_fail(PBG_E_ARG, "pbg_population_perturb: NULL population or theta");
-  DeviceGuard dg(p->device);
-  hipLaunchKernelGGL(perturb_kernel, pair_grid(p), dim3(256), 0, (hipStream_t)stream, p->D, theta, sigma, (uint32_t)seed,
-                     (uint32_t)(seed >> 32), (uint32_t)p->pair0, generation, p->members);
+  DeviceGuard dg(p->a.device);
+  hipLaunchKernelGGL(perturb_kernel, pair_grid(p), dim3(256), 0, (hipStream_t)stream, p->a.D, theta, sigma, (uint32_t)seed,
+                     (uint32_t)(seed >> 32), (uint32_t)p->pair0, generation, p->a.params);
   return launched("perturb_kernel launch");
 }
 
 int pbg_population_set_member(pbg_population* p, int m, const float* theta, void* stream) {
   if (!p || !theta) return pbg::capi_fail(PBG_E_ARG, "pbg_population_set_member: NULL population or theta");
-  const int P = 2 * p->n_pairs;
+  const int P = p->a.n_members;
   if (m < -1 || m >= P) {
     char msg[96];
     snprintf(msg, sizeof(msg), "pbg_population_set_member: member %d outside 0..%d (or -1 for every member)", m, P - 1);
     return pbg::capi_fail(PBG_E_ARG, msg);
   }
-  DeviceGuard dg(p->device);
+  DeviceGuard dg(p->a.device);
   const unsigned rows = m < 0 ? (unsigned)P : 1u;
-  float* dst = p->members + (m < 0 ? (size_t)0 : (size_t)m * p->D);
-  hipLaunchKernelGGL(copy_rows_kernel, dim3(rows, (unsigned)((p->D + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p->D,
+  float* dst = p->a.params + (m < 0 ? (size_t)0 : (size_t)m * p->a.D);
+  hipLaunchKernelGGL(copy_rows_kernel, dim3(rows, (unsigned)((p->a.D + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p->a.D,
                      (size_t)0, theta, dst);
   return launched("set_member launch");
 }
 
 int pbg_population_get_member(const pbg_population* p, int m, float* theta_out, void* stream) {
   if (!p || !theta_out) return pbg::capi_fail(PBG_E_ARG, "pbg_population_get_member: NULL population or theta_out");
-  const int P = 2 * p->n_pairs;
+  const int P = p->a.n_members;
   if (m < 0 || m >= P) {
     char msg[96];
     snprintf(msg, sizeof(msg), "pbg_population_get_member: member %d outside 0..%d", m, P - 1);
     return pbg::capi_fail(PBG_E_ARG, msg);
   }
-  DeviceGuard dg(p->device);
-  hipLaunchKernelGGL(copy_rows_kernel, dim3(1u, (unsigned)((p->D + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p->D,
-                     (size_t)0, p->members + (size_t)m * p->D, theta_out);
+  DeviceGuard dg(p->a.device);
+  hipLaunchKernelGGL(copy_rows_kernel, dim3(1u, (unsigned)((p->a.D + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p->a.D,
+                     (size_t)0, p->a.params + (size_t)m * p->a.D, theta_out);
   return launched("get_member launch");
 }
 
 int pbg_population_act(const pbg_population* p, int n, const float* obs, float* act, void* stream) {
   if (!p) return pbg::capi_fail(PBG_E_ARG, "pbg_population_act: population is NULL");
-  const int P = 2 * p->n_pairs;
+  const int P = p->a.n_members;
   if (n < 0 || n % P != 0 || (n > 0 && (!obs || !act))) {
     char msg[128];
     snprintf(msg, sizeof(msg), "pbg_population_act: n = %d must be a multiple of the %d members, obs and act not NULL", n, P);
     return pbg::capi_fail(PBG_E_ARG, msg);
   }
   if (n == 0) return PBG_OK;
-  DeviceGuard dg(p->device);
+  DeviceGuard dg(p->a.device);
   Book none;
   memset(&none, 0, sizeof(none));
-  const int e = launch_population_act(p, n, obs, act, nullptr, nullptr, none, false, (hipStream_t)stream);
-  return e ? hip_fail(e, "population_act_kernel launch") : PBG_OK;
+  const int e = launch_actor(p->a, n, obs, act, nullptr, nullptr, none, false, (hipStream_t)stream);
+  return e ? hip_fail(e, "actor_kernel launch") : PBG_OK;
 }
 
 int pbg_rollout_population(pbg_handle* h, const pbg_population* p, const pbg_rollout_io_t* io, void* stream) {
   if (!h || !p || !io) return pbg::capi_fail(PBG_E_ARG, "pbg_rollout_population: NULL handle, population or io");
-  return rollout_loop("pbg_rollout_population", h, io, stream, p->device, p->obs_dim, p->act_dim, 2 * p->n_pairs,
-                      launch_population_act, p, p->stats);
+  return rollout_loop("pbg_rollout_population", h, io, stream, p->a);
 }
 
 int pbg_population_fitness(const pbg_population* p, int n, const double* cur_return, const double* done_return,
                            double* fitness_out, void* stream) {
   if (!p || !cur_return || !done_return || !fitness_out)
     return pbg::capi_fail(PBG_E_ARG, "pbg_population_fitness: NULL population or buffer");
-  const int P = 2 * p->n_pairs;
+  const int P = p->a.n_members;
   if (n < P || n % P != 0) {
     char msg[128];
     snprintf(msg, sizeof(msg), "pbg_population_fitness: n = %d must be a positive multiple of the %d members", n, P);
     return pbg::capi_fail(PBG_E_ARG, msg);
   }
-  DeviceGuard dg(p->device);
+  DeviceGuard dg(p->a.device);
   hipLaunchKernelGGL(fitness_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, (hipStream_t)stream, P, n / P, cur_return,
                      done_return, fitness_out);
   return launched("fitness_kernel launch");
@@ -431,9 +307,9 @@ int pbg_population_fitness(const pbg_population* p, int n, const double* cur_ret
 int pbg_population_grad(const pbg_population* p, const float* w, uint64_t seed, uint32_t generation, float* g_out,
                         void* stream) {
   if (!p || !w || !g_out) return pbg::capi_fail(PBG_E_ARG, "pbg_population_grad: NULL population, w or g_out");
-  DeviceGuard dg(p->device);
-  const int nb = (p->D + 3) / 4;
-  hipLaunchKernelGGL(grad_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p->D, p->n_pairs, w,
+  DeviceGuard dg(p->a.device);
+  const int nb = (p->a.D + 3) / 4;
+  hipLaunchKernelGGL(grad_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p->a.D, p->n_pairs, w,
                      (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)p->pair0, generation, g_out);
   return launched("grad_kernel launch");
 }

@@ -24,7 +24,59 @@ def _need(name):
     return getattr(_native.lib(), name)
 
 
-class ObsStats:
+class _NativeObject:
+    """What the wrappers of a native object share: the handle ``_h`` and its destroy function, the guard
+    against use after ``close``, the device as ``cuda:<index>``, the current stream, and the check of a tensor
+    whose pointer goes to the library as it is."""
+    _DESTROY = None    # the library's destroy function
+    _NOUN = "object"   # what the closed guard calls the object
+    _h = None
+    device = None      # torch.device("cuda", index); None: a host object
+
+    def _set_device(self, device, rule="a GPU") -> int:
+        """Store ``device`` as ``torch.device("cuda", index)`` and return the index."""
+        import torch
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise _native.PbgError(f"{type(self).__name__}: device must be {rule}, got {device!r}")
+        idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
+        self.device = torch.device("cuda", idx)
+        return idx
+
+    def close(self):
+        """Destroy the native object (an ``ObsStats``: detach it from every actor first)."""
+        if self._h:
+            getattr(_native.lib(), self._DESTROY)(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _open(self, what):
+        if not self._h:
+            raise _native.PbgError(f"{type(self).__name__}.{what}: the {self._NOUN} is closed")
+        return self._h
+
+    def _stream(self):
+        import torch
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    def _vec(self, t, what, name, shape, dtype=None):
+        """``t`` must already be a contiguous tensor of ``shape`` and ``dtype`` on the device: the native
+        call takes its pointer as is, so nothing is converted (or written past) silently."""
+        import torch
+        dtype = torch.float32 if dtype is None else dtype
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.device != self.device or \
+                not t.is_contiguous() or tuple(t.shape) != tuple(shape):
+            raise _native.PbgError(f"{type(self).__name__}.{what}: {name} must be a contiguous {dtype} tensor of shape "
+                                   f"{tuple(shape)} on {self.device}")
+        return t
+
+
+class ObsStats(_NativeObject):
     """Running per-component statistics of observations on one GPU (include/pbg.h pbg_obs_stats_*): float64
     totals ``count, sum[K], sumsq[K]`` (initially OpenAI ES's ``RunningStat(eps=1e-2)``) and one partial
     accumulator ("slot") per 16-row tile, so nothing is atomic and every sum has a stated order.
@@ -35,6 +87,7 @@ class ObsStats:
     actor (``attach_obs_stats``), every step of ``VecEnv.rollout`` with that actor adds the observations
     whose actions are booked; ``update`` adds a batch directly.  ``finalize`` folds the slots into the
     totals and returns ``(mean, inv_std)``.  Everything is asynchronous on the current stream."""
+    _DESTROY = "pbg_obs_stats_destroy"
 
     def __init__(self, obs_dim: int, n_envs: int, group=None, device="cuda:0"):
         import torch
@@ -44,53 +97,23 @@ class ObsStats:
             raise _native.PbgError(f"ObsStats: n_envs {n_envs} must be >= 1 and a multiple of group {group}")
         G = self.n_envs if self.group is None else self.group
         self.n_slots = (self.n_envs // G) * ((G + 15) // 16)
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise _native.PbgError(f"ObsStats: device must be a GPU, got {device!r}")
-        idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
-        self.device = torch.device("cuda", idx)
+        idx = self._set_device(device)
         h = ctypes.c_void_p()
         _native.check(_need("pbg_obs_stats_create")(idx, self.obs_dim, self.n_slots, ctypes.byref(h)),
                       "pbg_obs_stats_create")
-        self._s = h
+        self._h = h
         self.mean = torch.zeros(self.obs_dim, dtype=torch.float32, device=self.device)
         self.inv_std = torch.ones(self.obs_dim, dtype=torch.float32, device=self.device)
-
-    def close(self):
-        """Destroy the native object; detach it from every actor first."""
-        if getattr(self, "_s", None):
-            _native.lib().pbg_obs_stats_destroy(self._s)
-            self._s = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _open(self, what):
-        if not getattr(self, "_s", None):
-            raise _native.PbgError(f"ObsStats.{what}: the object is closed")
-        return self._s
-
-    def _stream(self):
-        import torch
-        return torch.cuda.current_stream(self.device).cuda_stream
 
     def update(self, obs, active=None):
         """Add ``obs`` (``[n, obs_dim]`` float32 on the device) to the slots: the rows whose ``active`` flag
         (``[n]`` uint8, None = all) is set and that hold no NaN or inf."""
         import torch
         s = self._open("update")
-        if not isinstance(obs, torch.Tensor) or obs.dtype != torch.float32 or obs.device != self.device or \
-                not obs.is_contiguous() or obs.dim() != 2 or obs.shape[1] != self.obs_dim:
-            raise _native.PbgError(f"ObsStats.update: obs must be a contiguous float32 tensor [n, {self.obs_dim}] on "
-                                   f"{self.device}")
-        n = obs.shape[0]
-        if active is not None and (not isinstance(active, torch.Tensor) or active.dtype != torch.uint8 or
-                                   active.device != self.device or not active.is_contiguous() or
-                                   tuple(active.shape) != (n,)):
-            raise _native.PbgError(f"ObsStats.update: active must be a contiguous uint8 tensor [{n}] on {self.device}")
+        n = obs.shape[0] if isinstance(obs, torch.Tensor) and obs.dim() == 2 else -1
+        self._vec(obs, "update", "obs", (n, self.obs_dim))
+        if active is not None:
+            self._vec(active, "update", "active", (n,), torch.uint8)
         _native.check(_native.lib().pbg_obs_stats_update(s, n, self.group or 0, obs.data_ptr(),
                                                          None if active is None else active.data_ptr(), self._stream()),
                       "pbg_obs_stats_update")
@@ -127,7 +150,7 @@ class ObsStats:
         self._totals_src = t  # alive until the stream has copied it
 
 
-class MLPPolicy:
+class MLPPolicy(_NativeObject):
     """obs -> h1 -> h2 -> act, ReLU on the hidden layers, float32.
 
     ``w1 [obs_dim, h1]``, ``b1 [h1]``, ``w2 [h1, h2]``, ``b2 [h2]``, ``w3 [h2, act_dim]``,
@@ -136,6 +159,9 @@ class MLPPolicy:
     (``"cuda:0"``) = the weights live there and ``act`` takes and returns torch tensors on it.
     Dims: 1..256 for obs_dim / h1 / h2, 1..64 for act_dim, no multiple of anything required.
     ``obs_norm=(mean, inv_std, clip)``: a normaliser (``set_obs_norm``)."""
+    _DESTROY, _NOUN = "pbg_policy_destroy", "policy"
+    _ROLLOUT = "pbg_rollout"   # VecEnv.rollout's entry point for this actor
+    n_members = 1              # one weight set for the whole batch
 
     def __init__(self, w1, b1, w2, b2, w3, b3, device=None, obs_norm=None):
         ws = [np.ascontiguousarray(np.asarray(a), dtype=np.float32) for a in (w1, b1, w2, b2, w3, b3)]
@@ -147,15 +173,7 @@ class MLPPolicy:
         if w2.shape != (self.h1, self.h2) or b1.shape != (self.h1,) or b2.shape != (self.h2,) or \
                 b3.shape != (self.act_dim,):
             raise _native.PbgError(f"MLPPolicy: inconsistent shapes {[a.shape for a in ws]}")
-        self.device = None
-        idx = -1
-        if device is not None:
-            import torch
-            self.device = torch.device(device)
-            if self.device.type != "cuda":
-                raise _native.PbgError(f"MLPPolicy: device must be None (host) or a GPU, got {device!r}")
-            idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
-            self.device = torch.device("cuda", idx)
+        idx = -1 if device is None else self._set_device(device, "None (host) or a GPU")
         if not hasattr(_native.lib(), "pbg_policy_create"):
             raise _native.PbgError(f"{_native.LIB_PATH} has no pbg_policy_create: a build without the policy kernel")
         FP = ctypes.POINTER(ctypes.c_float)
@@ -163,7 +181,7 @@ class MLPPolicy:
         _native.check(_native.lib().pbg_policy_create(idx, self.obs_dim, self.h1, self.h2, self.act_dim,
                                                       *[a.ctypes.data_as(FP) for a in ws], ctypes.byref(h)),
                       "pbg_policy_create")
-        self._p = h
+        self._h = h
         self.obs_norm = None    # (mean, inv_std, clip) as numpy float32 / float, or None
         self.obs_stats = None   # the attached ObsStats, or None
         if obs_norm is not None:
@@ -181,11 +199,10 @@ class MLPPolicy:
         """Every later ``act`` / rollout feeds the MLP ``clip((obs - mean) * inv_std, -clip, clip)`` (float32,
         one rounding per operation); ``mean``, ``inv_std``: ``[obs_dim]`` arrays (or CPU / GPU tensors),
         copied.  ``set_obs_norm(None)`` switches the normaliser off.  Synchronises the device."""
-        if not self._p:
-            raise _native.PbgError("MLPPolicy.set_obs_norm: the policy is closed")
+        p = self._open("set_obs_norm")
         f = _need("pbg_policy_set_obs_norm")
         if mean is None and inv_std is None:
-            _native.check(f(self._p, None, None, 0.0), "pbg_policy_set_obs_norm")
+            _native.check(f(p, None, None, 0.0), "pbg_policy_set_obs_norm")
             self.obs_norm = None
             return
         arrs = []
@@ -195,35 +212,22 @@ class MLPPolicy:
             if a.shape != (self.obs_dim,):
                 raise _native.PbgError(f"MLPPolicy.set_obs_norm: mean and inv_std must have shape ({self.obs_dim},)")
             arrs.append(a.copy())
-        _native.check(f(self._p, arrs[0].ctypes.data, arrs[1].ctypes.data, float(clip)), "pbg_policy_set_obs_norm")
+        _native.check(f(p, arrs[0].ctypes.data, arrs[1].ctypes.data, float(clip)), "pbg_policy_set_obs_norm")
         self.obs_norm = (arrs[0], arrs[1], float(clip))
 
     def attach_obs_stats(self, stats):
         """While an ``ObsStats`` is attached, every step of ``VecEnv.rollout`` with this policy adds its
         observations to it (``act`` never does); None detaches."""
-        if not self._p:
-            raise _native.PbgError("MLPPolicy.attach_obs_stats: the policy is closed")
-        _native.check(_need("pbg_policy_attach_obs_stats")(self._p, None if stats is None else stats._open("attach")),
+        p = self._open("attach_obs_stats")
+        _native.check(_need("pbg_policy_attach_obs_stats")(p, None if stats is None else stats._open("attach")),
                       "pbg_policy_attach_obs_stats")
         self.obs_stats = stats
-
-    def close(self):
-        if getattr(self, "_p", None):
-            _native.lib().pbg_policy_destroy(self._p)
-            self._p = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def act(self, obs, out=None):
         """``[n, obs_dim]`` float32 observations -> ``[n, act_dim]`` actions.  Device policy: torch
         tensors on its device (``out``: an optional preallocated result, which keeps the call
         capturable).  Host policy: numpy in, numpy out."""
-        if not self._p:
-            raise _native.PbgError("MLPPolicy.act: the policy is closed")
+        p = self._open("act")
         if self.device is None:
             x = np.ascontiguousarray(obs, dtype=np.float32)
             if x.ndim != 2 or x.shape[1] != self.obs_dim:
@@ -233,7 +237,7 @@ class MLPPolicy:
                     not y.flags.c_contiguous or not y.flags.writeable:
                 raise _native.PbgError(f"MLPPolicy.act: out must be a writable C-contiguous float32 array of shape "
                                        f"({x.shape[0]}, {self.act_dim})")
-            _native.check(_native.lib().pbg_policy_act_host(self._p, x.shape[0], x.ctypes.data, y.ctypes.data),
+            _native.check(_native.lib().pbg_policy_act_host(p, x.shape[0], x.ctypes.data, y.ctypes.data),
                           "pbg_policy_act_host")
             return y
         import torch
@@ -243,12 +247,8 @@ class MLPPolicy:
         if x.dim() != 2 or x.shape[1] != self.obs_dim:
             raise _native.PbgError(f"MLPPolicy.act: obs shape {tuple(x.shape)}, expected [n, {self.obs_dim}]")
         y = torch.empty((x.shape[0], self.act_dim), dtype=torch.float32, device=self.device) if out is None else out
-        if not isinstance(y, torch.Tensor) or y.dtype != torch.float32 or y.device != self.device or \
-                not y.is_contiguous() or tuple(y.shape) != (x.shape[0], self.act_dim):
-            raise _native.PbgError(f"MLPPolicy.act: out must be a contiguous float32 tensor of shape "
-                                   f"({x.shape[0]}, {self.act_dim}) on {self.device}")
-        _native.check(_native.lib().pbg_policy_act(self._p, x.shape[0], x.data_ptr(), y.data_ptr(),
-                                                   torch.cuda.current_stream(self.device).cuda_stream),
+        y = self._vec(y, "act", "out", (x.shape[0], self.act_dim))
+        _native.check(_native.lib().pbg_policy_act(p, x.shape[0], x.data_ptr(), y.data_ptr(), self._stream()),
                       "pbg_policy_act")
         return y
 
@@ -279,7 +279,7 @@ def unpack_theta(dims, theta):
     return out
 
 
-class MLPPopulation:
+class MLPPopulation(_NativeObject):
     """``2 * n_pairs`` weight sets ("members") of one MLP shape on one GPU (include/pbg.h pbg_population_*):
     the population of an evolution strategy with mirrored sampling.  Members ``2 i`` and ``2 i + 1`` are the
     pair ``theta +- sigma eps_i``; ``pair0`` is the global index of the first pair when this object holds a
@@ -290,9 +290,10 @@ class MLPPopulation:
     and ``VecEnv.rollout`` split a batch of ``n = n_members * G`` envs into ``n_members`` consecutive
     groups of ``G``; group m runs member m.  Every method is asynchronous on the current stream and
     allocates only the results it is not handed (``out=``), so a generation captures into a HIP graph."""
+    _DESTROY, _NOUN = "pbg_population_destroy", "population"
+    _ROLLOUT = "pbg_rollout_population"   # VecEnv.rollout's entry point for this actor
 
     def __init__(self, dims, n_pairs: int, device, pair0: int = 0):
-        import torch
         self.dims = tuple(int(d) for d in dims)
         if len(self.dims) != 4:
             raise _native.PbgError(f"MLPPopulation: dims must be (obs_dim, h1, h2, act_dim), got {dims!r}")
@@ -300,52 +301,16 @@ class MLPPopulation:
         self.n_pairs, self.pair0 = int(n_pairs), int(pair0)
         self.n_members = 2 * self.n_pairs
         self.n_params = param_count(self.dims)
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise _native.PbgError(f"MLPPopulation: device must be a GPU, got {device!r}")
-        idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
-        self.device = torch.device("cuda", idx)
+        idx = self._set_device(device)
         if not hasattr(_native.lib(), "pbg_population_create"):
             raise _native.PbgError(f"{_native.LIB_PATH} has no pbg_population_create: a build without populations")
         h = ctypes.c_void_p()
         _native.check(_native.lib().pbg_population_create(idx, *self.dims, self.n_pairs, self.pair0, ctypes.byref(h)),
                       "pbg_population_create")
-        self._pop = h
+        self._h = h
         self.obs_clip = None    # the normaliser's clip, None = no normaliser (set_obs_norm)
         self._norm = None       # this object's copies of its mean and inv_std, allocated by the first set_obs_norm
         self.obs_stats = None   # the attached ObsStats, or None
-
-    def close(self):
-        if getattr(self, "_pop", None):
-            _native.lib().pbg_population_destroy(self._pop)
-            self._pop = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    # ------------------------------------------------------------------ helpers
-    def _open(self, what):
-        if not getattr(self, "_pop", None):
-            raise _native.PbgError(f"MLPPopulation.{what}: the population is closed")
-        return self._pop
-
-    def _stream(self):
-        import torch
-        return torch.cuda.current_stream(self.device).cuda_stream
-
-    def _vec(self, t, what, name, shape, dtype=None):
-        """``t`` must already be a contiguous tensor of ``shape`` and ``dtype`` on the device: the native
-        call takes its pointer as is, so nothing is converted (or written past) silently."""
-        import torch
-        dtype = torch.float32 if dtype is None else dtype
-        if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.device != self.device or \
-                not t.is_contiguous() or tuple(t.shape) != tuple(shape):
-            raise _native.PbgError(f"MLPPopulation.{what}: {name} must be a contiguous {dtype} tensor of shape "
-                                   f"{tuple(shape)} on {self.device}")
-        return t
 
     # ------------------------------------------------------------------ normaliser
     def set_obs_norm(self, mean, inv_std=None, clip: float = 5.0):

@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from . import _native
+from .policy import MLPPolicy, MLPPopulation
 from .spaces import Box
 
 
@@ -225,14 +226,13 @@ class VecEnv:
         if steps < 1:
             raise _native.PbgError(f"rollout: steps must be >= 1 (got {steps})")
         n, info, kw = self.num_envs, self.info, dict(device=self.device)
-        pop = getattr(policy, "_pop", None)  # an MLPPopulation: env e runs member e // (n // n_members)
-        if pop is not None:
-            if n % policy.n_members != 0:
-                raise _native.PbgError(f"rollout: {n} envs are not a multiple of the population's "
-                                       f"{policy.n_members} members")
-        elif getattr(policy, "_p", None) is None or not hasattr(_native.lib(), "pbg_rollout"):
+        if not isinstance(policy, (MLPPolicy, MLPPopulation)) or not policy._h or \
+                not hasattr(_native.lib(), policy._ROLLOUT):
             raise _native.PbgError("rollout: policy must be an open MLPPolicy or MLPPopulation (and the library "
                                    "built with pbg_rollout)")
+        if n % policy.n_members != 0:  # env e runs member e // (n // n_members); an MLPPolicy has one
+            raise _native.PbgError(f"rollout: {n} envs are not a multiple of the population's "
+                                   f"{policy.n_members} members")
         if self._ro_acc is None:
             self._ro_acc = dict(cur_return=torch.zeros(n, dtype=torch.float64, **kw),
                                 cur_length=torch.zeros(n, dtype=torch.int32, **kw),
@@ -256,12 +256,8 @@ class VecEnv:
             self._ro_io[key] = (io, traj)
         io, traj = self._ro_io[key]
         io.autoreset = 1 if self.autoreset else 0
-        if pop is not None:
-            _native.check(_native.lib().pbg_rollout_population(self._h, pop, ctypes.byref(io),
-                                                               _stream(self.device)), "pbg_rollout_population")
-        else:
-            _native.check(_native.lib().pbg_rollout(self._h, policy._p, ctypes.byref(io),
-                                                    _stream(self.device)), "pbg_rollout")
+        _native.check(getattr(_native.lib(), policy._ROLLOUT)(self._h, policy._h, ctypes.byref(io),
+                                                              _stream(self.device)), policy._ROLLOUT)
         return RolloutResult(obs=self.obs, **self._ro_acc, obs_traj=traj.get("obs_traj"),
                              act_traj=traj.get("act_traj"), rew_traj=traj.get("rew_traj"),
                              done_traj=traj.get("done_traj"))

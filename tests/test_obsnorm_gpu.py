@@ -161,9 +161,9 @@ def test_update_argument_errors():
     small.update(obs[:16])
     small.update(obs[:3])
     L = _native.lib()
-    assert L.pbg_obs_stats_update(small._s, 15, 4, obs.data_ptr(), None, None) == -1   # n no multiple of group
+    assert L.pbg_obs_stats_update(small._h, 15, 4, obs.data_ptr(), None, None) == -1   # n no multiple of group
     assert b"multiple" in L.pbg_last_error()
-    assert L.pbg_obs_stats_update(small._s, 16, 8, obs.data_ptr(), None, None) == -1   # two groups, two slots
+    assert L.pbg_obs_stats_update(small._h, 16, 8, obs.data_ptr(), None, None) == -1   # two groups, two slots
     assert b"slots" in L.pbg_last_error()
     grouped = ObsStats(K, 32, group=16, device=DEV)
     with pytest.raises(_native.PbgError):

@@ -146,16 +146,16 @@ def test_argument_errors_without_a_device():
     mean, inv_std = make_norm(5)
     m, s = mean.ctypes.data, inv_std.ctypes.data
     for clip in (0.0, -1.0, float("nan")):
-        assert L.pbg_policy_set_obs_norm(pi._p, m, s, clip) == -1, clip
+        assert L.pbg_policy_set_obs_norm(pi._h, m, s, clip) == -1, clip
         assert b"clip" in L.pbg_last_error()
-    assert L.pbg_policy_set_obs_norm(pi._p, m, None, 5.0) == -1
-    assert L.pbg_policy_set_obs_norm(pi._p, None, s, 5.0) == -1
+    assert L.pbg_policy_set_obs_norm(pi._h, m, None, 5.0) == -1
+    assert L.pbg_policy_set_obs_norm(pi._h, None, s, 5.0) == -1
     assert L.pbg_policy_set_obs_norm(None, m, s, 5.0) == -1
     assert pi.obs_norm is None
     obs = pd.seeded_obs(5, 8)
     want = pi.act(obs)
-    assert L.pbg_policy_set_obs_norm(pi._p, m, s, 5.0) == 0       # a refused call left nothing behind
-    assert L.pbg_policy_set_obs_norm(pi._p, None, None, 0.0) == 0  # off: clip is not looked at
+    assert L.pbg_policy_set_obs_norm(pi._h, m, s, 5.0) == 0       # a refused call left nothing behind
+    assert L.pbg_policy_set_obs_norm(pi._h, None, None, 0.0) == 0  # off: clip is not looked at
     assert np.array_equal(pi.act(obs), want)
     for bad in ((mean[:-1], inv_std[:-1]), (mean, inv_std[:-1]), (mean.reshape(1, 5), inv_std.reshape(1, 5))):
         with pytest.raises(_native.PbgError):
@@ -168,7 +168,7 @@ def test_argument_errors_without_a_device():
     assert L.pbg_policy_attach_obs_stats(None, None) == -1
     assert L.pbg_population_attach_obs_stats(None, None) == -1
     assert L.pbg_population_set_obs_norm(None, None, None, 5.0, None) == -1
-    assert L.pbg_policy_attach_obs_stats(pi._p, None) == 0
+    assert L.pbg_policy_attach_obs_stats(pi._h, None) == 0
     pi.close()
     with pytest.raises(_native.PbgError):
         pi.set_obs_norm(mean, inv_std)

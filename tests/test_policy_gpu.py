@@ -16,7 +16,7 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 SIZES = (1, 15, 16, 17, 31, 33, 65, 1000)  # around the kernel's 16-env tile, one to many workgroups
 DIMS = {"ant": "policy_ant.npz", "humanoid": "policy_humanoid.npz", "pendulum": "policy_invertedpendulum.npz",
-        "odd": (7, 33, 17, 3)}
+        "odd": (7, 33, 17, 3), "max": (256, 256, 256, 64)}  # max: every dim at its limit, on unpadded weights
 GUARD = 64
 
 

@@ -42,13 +42,20 @@ def test_host_act_within_apriori_bound(kind, what):
     assert (err <= bound).all(), (err / bound).max()
 
 
-@pytest.mark.parametrize("dims", [(70, 256, 128, 30), (28, 128, 64, 8), (7, 33, 17, 3)], ids=str)
+@pytest.mark.parametrize("dims", [(70, 256, 128, 30), (28, 128, 64, 8), (7, 33, 17, 3), (256, 256, 256, 64)], ids=str)
 def test_host_act_exact_on_integers(dims):
     """Weights from {-1,0,1}, obs from {-2..2}: every partial sum is an integer below 2^24
     (|h1| <= 2*70+1, |h2| <= 141*256+1 = 36097, |out| <= 36097*128+1 < 2^23), so every fma is
-    exact whatever it rounds like and the result equals the int64 evaluation."""
+    exact whatever it rounds like and the result equals the int64 evaluation.
+    The widest dims (256, 256, 256, 64) pass that worst case ((513*256+1)*256+1 > 2^24), so for them the
+    bound is taken from the (fixed) data: the sum of |term| over a layer bounds every partial sum."""
     ws = pd.integer_weights(dims)
     obs = pd.integer_obs(dims[0])
+    x = obs.astype(np.int64)
+    for w, b, relu in ((ws[0], ws[1], True), (ws[2], ws[3], True), (ws[4], ws[5], False)):
+        assert (np.abs(x) @ np.abs(w.astype(np.int64)) + np.abs(b.astype(np.int64))).max() < 2 ** 24
+        x = x @ w.astype(np.int64) + b.astype(np.int64)
+        x = np.maximum(x, 0) if relu else x
     pi = MLPPolicy(*ws)
     got = pi.act(obs)
     pi.close()

@@ -106,7 +106,7 @@ def test_grad_is_the_chain_on_the_devices_bits(dims, n_pairs):
     pop.close()
 
 
-@pytest.mark.parametrize("dims", [(7, 33, 17, 3), ANT], ids=str)
+@pytest.mark.parametrize("dims", [(7, 33, 17, 3), ANT, (256, 256, 256, 64)], ids=str)
 def test_population_act_equals_each_members_host_policy(dims):
     """Six members with distinct weights; G around the 16-env tile (one row, a part tile, a whole one, one
     more than a tile, two tiles and a row).  Every member's rows are the host chain of that member's
@@ -277,7 +277,7 @@ def test_population_rollout_argument_errors():
     with pytest.raises(_native.PbgError):
         env.rollout(pop, 4)
     io = _native.RolloutIO(n_steps=4)         # the native check too, before it looks at any buffer
-    assert _native.lib().pbg_rollout_population(env._h, pop._pop, io, None) == -1
+    assert _native.lib().pbg_rollout_population(env._h, pop._h, io, None) == -1
     assert b"multiple" in _native.lib().pbg_last_error()
     wrong = MLPPopulation((44, 256, 128, 17), 2, DEV)  # 4 members, the Humanoid's shape
     with pytest.raises(_native.PbgError):

@@ -229,8 +229,8 @@ def bench_generation(args, dev):
 
 
 def actor_only(args, dev):
-    """Launches of the actors alone at n = 16,384 (run under a kernel trace): the shared-weight kernel and
-    the population kernel at --members."""
+    """Launches of the actor alone at n = 16,384 (run under a kernel trace): actor_kernel with one member
+    (the shared-weight policy) and at --members."""
     import torch
     pis, dims, _ = actors(dev, {"A": None, "P": args.members})
     obs = torch.randn((N, dims[0]), device=dev)
@@ -239,7 +239,7 @@ def actor_only(args, dev):
         pis["A"].act(obs, out=out)
         pis["P"].act(obs, out=out)
     torch.cuda.synchronize(dev)
-    print(f"actor-only done: policy_act_kernel and population_act_kernel at {args.members} members x {N // args.members}")
+    print(f"actor-only done: actor_kernel with one member x {N} and at {args.members} members x {N // args.members}")
 
 
 def main():
