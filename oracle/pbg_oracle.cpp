@@ -166,15 +166,9 @@ double sim_env_dt(const MV& m) { return sim_dt(m) * sim_substeps(m); }
 int sim_flag_timeout(const MV& m) { return (600 + sim_substeps(m) - 1) / sim_substeps(m); }
 
 MV* model_views() {
-  static MV views[17] = {view<pbg_models::Pendulum>(), view<pbg_models::Hopper>(),
-                         view<pbg_models::HalfCheetah>(), view<pbg_models::Ant>(),
-                         view<pbg_models::Humanoid>(), view<pbg_models::Walker2D>(),
-                         view<pbg_models::PendulumSwingup>(), view<pbg_models::DoublePendulum>(),
-                         view<pbg_models::HumanoidFlagrun>(), view<pbg_models::HopperMuJoCo>(),
-                         view<pbg_models::Walker2DMuJoCo>(), view<pbg_models::HalfCheetahMuJoCo>(),
-                         view<pbg_models::AntMuJoCo>(), view<pbg_models::HumanoidMuJoCo>(),
-                         view<pbg_models::DoublePendulumMuJoCo>(), view<pbg_models::HumanoidFlagrunHarder>(),
-                         view<pbg_models::Atlas>()};
+#define PBG_VIEW(NAME, ID, ENV, KEY) view<pbg_models::NAME>(),
+  static MV views[PBG_N_ROBOTS] = {PBG_ROBOTS(PBG_VIEW)};
+#undef PBG_VIEW
   return views;
 }
 const MV* model(int robot) {
@@ -188,14 +182,14 @@ struct LinkDynOverride {
   double mass[MAXL], com[MAXL][3], inertia[MAXL][6], base_inertia[6], base_mass;
   MV orig;
 };
-LinkDynOverride g_dyn_ov[17];
+LinkDynOverride g_dyn_ov[PBG_N_ROBOTS];
 // joint damping replaced at run time (importer-rule study: MJCF <default> damping inheritance)
 struct DampOverride {
   bool on = false;
   double damping[MAXD];
   const double* orig = nullptr;
 };
-DampOverride g_damp_ov[17];
+DampOverride g_damp_ov[PBG_N_ROBOTS];
 
 // ------------------------------------------------------------------ physics (pbg_physics.h)
 #include "pbg_physics.h"

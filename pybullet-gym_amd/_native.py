@@ -8,16 +8,12 @@ from __future__ import annotations
 import ctypes
 import os
 
+from . import robots
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libpbg_amd.so")
 
-ROBOT_IDS = {"InvertedPendulumPyBulletEnv-v0": 0, "HopperPyBulletEnv-v0": 1, "HalfCheetahPyBulletEnv-v0": 2,
-             "AntPyBulletEnv-v0": 3, "HumanoidPyBulletEnv-v0": 4, "Walker2DPyBulletEnv-v0": 5,
-             "InvertedPendulumSwingupPyBulletEnv-v0": 6, "InvertedDoublePendulumPyBulletEnv-v0": 7,
-             "HumanoidFlagrunPyBulletEnv-v0": 8, "HopperMuJoCoEnv-v0": 9, "Walker2DMuJoCoEnv-v0": 10,
-             "HalfCheetahMuJoCoEnv-v0": 11, "AntMuJoCoEnv-v0": 12, "HumanoidMuJoCoEnv-v0": 13,
-             "InvertedDoublePendulumMuJoCoEnv-v0": 14, "HumanoidFlagrunHarderPyBulletEnv-v0": 15,
-             "AtlasPyBulletEnv-v0": 16}
+ROBOT_IDS = {s.env_id: s.robot_id for s in robots.BY_ID}
 
 
 class PbgError(RuntimeError):
@@ -169,30 +165,19 @@ def lib():
     return L
 
 
-EXPORTED = ("pbg_create", "pbg_create_debug", "pbg_create_ex", "pbg_create_v2", "pbg_precision",
-            "pbg_default_sim_params", "pbg_get_sim_params",
-            "pbg_destroy", "pbg_info", "pbg_reset", "pbg_step", "pbg_step_ex",
-            "pbg_get_state", "pbg_set_state", "pbg_pack_record_sizes", "pbg_pack", "pbg_sample_actions",
-            "pbg_debug_poison", "pbg_last_error",
-            "pbg_policy_create", "pbg_policy_destroy", "pbg_policy_act", "pbg_policy_act_host", "pbg_rollout",
-            "pbg_population_create", "pbg_population_destroy", "pbg_population_noise",
-            "pbg_population_noise_host", "pbg_population_perturb", "pbg_population_set_member",
-            "pbg_population_get_member", "pbg_population_act", "pbg_rollout_population",
-            "pbg_population_fitness", "pbg_population_grad",
-            "pbg_obs_stats_create", "pbg_obs_stats_destroy", "pbg_obs_stats_update", "pbg_obs_stats_finalize",
-            "pbg_obs_stats_get_totals", "pbg_obs_stats_set_totals", "pbg_policy_set_obs_norm",
-            "pbg_population_set_obs_norm", "pbg_policy_attach_obs_stats", "pbg_population_attach_obs_stats")
-
-
-OBS_NORM_EXPORTED = ("pbg_obs_stats_create", "pbg_obs_stats_destroy", "pbg_obs_stats_update", "pbg_obs_stats_finalize",
-                     "pbg_obs_stats_get_totals", "pbg_obs_stats_set_totals", "pbg_policy_set_obs_norm",
-                     "pbg_population_set_obs_norm", "pbg_policy_attach_obs_stats", "pbg_population_attach_obs_stats")
-
-
+POLICY_EXPORTED = ("pbg_policy_create", "pbg_policy_destroy", "pbg_policy_act", "pbg_policy_act_host", "pbg_rollout")
 POPULATION_EXPORTED = ("pbg_population_create", "pbg_population_destroy", "pbg_population_noise",
                        "pbg_population_noise_host", "pbg_population_perturb", "pbg_population_set_member",
                        "pbg_population_get_member", "pbg_population_act", "pbg_rollout_population",
                        "pbg_population_fitness", "pbg_population_grad")
+OBS_NORM_EXPORTED = ("pbg_obs_stats_create", "pbg_obs_stats_destroy", "pbg_obs_stats_update", "pbg_obs_stats_finalize",
+                     "pbg_obs_stats_get_totals", "pbg_obs_stats_set_totals", "pbg_policy_set_obs_norm",
+                     "pbg_population_set_obs_norm", "pbg_policy_attach_obs_stats", "pbg_population_attach_obs_stats")
+EXPORTED = ("pbg_create", "pbg_create_debug", "pbg_create_ex", "pbg_create_v2", "pbg_precision",
+            "pbg_default_sim_params", "pbg_get_sim_params",
+            "pbg_destroy", "pbg_info", "pbg_reset", "pbg_step", "pbg_step_ex",
+            "pbg_get_state", "pbg_set_state", "pbg_pack_record_sizes", "pbg_pack", "pbg_sample_actions",
+            "pbg_debug_poison", "pbg_last_error") + POLICY_EXPORTED + POPULATION_EXPORTED + OBS_NORM_EXPORTED
 
 
 def check(rc: int, what: str):

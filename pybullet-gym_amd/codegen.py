@@ -323,10 +323,10 @@ def _arr2(name, ctype, rows, w):
 
 
 def emit_struct(t: Dict) -> str:
-    cls = STRUCTS[t["key"]]
+    spec = robots.SPECS[t["key"]]
     L = [f"// {t['env_id']}: generated by pybulletgym_amd.codegen from the reference MJCF asset",
-         f"struct {cls} {{",
-         f"  static constexpr int robot_id = {ROBOT_IDS[t['key']]};",
+         f"struct {spec.struct} {{",
+         f"  static constexpr int robot_id = {spec.robot_id};",
          f"  static constexpr int kind = {t['kind']};",
          f"  static constexpr bool floating = {'true' if t['floating'] else 'false'};"]
     for k in ("NL", "NJ", "NDOF", "NA", "NO", "NR", "NF", "NP", "NS", "NPAIR", "NG", "OBS", "alive", "substeps",
@@ -386,28 +386,21 @@ def emit_struct(t: Dict) -> str:
     return "\n".join(L)
 
 
-ROBOT_IDS = {"pendulum": 0, "hopper": 1, "halfcheetah": 2, "ant": 3, "humanoid": 4, "walker2d": 5,
-             "pendulum_swingup": 6, "double_pendulum": 7, "humanoid_flagrun": 8, "hopper_mujoco": 9,
-             "walker2d_mujoco": 10, "halfcheetah_mujoco": 11, "ant_mujoco": 12, "humanoid_mujoco": 13,
-             "double_pendulum_mujoco": 14, "humanoid_flagrun_harder": 15, "atlas": 16}
-STRUCTS = {"pendulum": "Pendulum", "hopper": "Hopper", "halfcheetah": "HalfCheetah", "ant": "Ant",
-           "humanoid": "Humanoid", "walker2d": "Walker2D", "pendulum_swingup": "PendulumSwingup",
-           "double_pendulum": "DoublePendulum", "humanoid_flagrun": "HumanoidFlagrun",
-           "hopper_mujoco": "HopperMuJoCo", "walker2d_mujoco": "Walker2DMuJoCo",
-           "halfcheetah_mujoco": "HalfCheetahMuJoCo", "ant_mujoco": "AntMuJoCo", "humanoid_mujoco": "HumanoidMuJoCo",
-           "double_pendulum_mujoco": "DoublePendulumMuJoCo", "humanoid_flagrun_harder": "HumanoidFlagrunHarder",
-           "atlas": "Atlas"}
-
-
 def emit_header(tables: Dict[str, Dict]) -> str:
     out = ["// GENERATED FILE - do not edit.  python -m pybulletgym_amd.codegen",
            "// Per-robot static tables compiled from the reference's MJCF assets",
            "// (pybulletgym/envs/assets/mjcf/*.xml) under the import rules in mjcf.py.",
            "#pragma once", "", "namespace pbg_models {", ""]
-    for key in ROBOT_IDS:
-        out.append(emit_struct(tables[key]))
+    for spec in robots.BY_ID:
+        out.append(emit_struct(tables[spec.key]))
         out.append("")
     out.append("}  // namespace pbg_models")
+    # the robot registry for every per-robot table of the host code and the oracle (robots.BY_ID)
+    out += ["", "// X(struct, robot_id, env id, key) for every robot, in robot_id order",
+            "#define PBG_ROBOTS(X) \\"]
+    out += [f'  X({s.struct}, {s.robot_id}, "{s.env_id}", "{s.key}") \\' for s in robots.BY_ID]
+    out[-1] = out[-1][:-2]
+    out.append(f"#define PBG_N_ROBOTS {len(robots.BY_ID)}")
     return "\n".join(out) + "\n"
 
 

@@ -28,39 +28,17 @@ int fail(int code, const char* fmt, const char* a = "", long b = 0) {
 
 int env_robot_id(const char* env_id) {
   if (!env_id) return -1;
-  static const char* ids[17][2] = {{"InvertedPendulumPyBulletEnv-v0", "pendulum"},
-                                  {"HopperPyBulletEnv-v0", "hopper"},
-                                  {"HalfCheetahPyBulletEnv-v0", "halfcheetah"},
-                                  {"AntPyBulletEnv-v0", "ant"},
-                                  {"HumanoidPyBulletEnv-v0", "humanoid"},
-                                  {"Walker2DPyBulletEnv-v0", "walker2d"},
-                                  {"InvertedPendulumSwingupPyBulletEnv-v0", "pendulum_swingup"},
-                                  {"InvertedDoublePendulumPyBulletEnv-v0", "double_pendulum"},
-                                  {"HumanoidFlagrunPyBulletEnv-v0", "humanoid_flagrun"},
-                                  {"HopperMuJoCoEnv-v0", "hopper_mujoco"},
-                                  {"Walker2DMuJoCoEnv-v0", "walker2d_mujoco"},
-                                  {"HalfCheetahMuJoCoEnv-v0", "halfcheetah_mujoco"},
-                                  {"AntMuJoCoEnv-v0", "ant_mujoco"},
-                                  {"HumanoidMuJoCoEnv-v0", "humanoid_mujoco"},
-                                  {"InvertedDoublePendulumMuJoCoEnv-v0", "double_pendulum_mujoco"},
-                                  {"HumanoidFlagrunHarderPyBulletEnv-v0", "humanoid_flagrun_harder"},
-                                  {"AtlasPyBulletEnv-v0", "atlas"}};
-  for (int i = 0; i < 17; i++)
+#define PBG_IDS(NAME, ID, ENV, KEY) {ENV, KEY},
+  static const char* ids[PBG_N_ROBOTS][2] = {PBG_ROBOTS(PBG_IDS)};  // models_gen.h: in robot_id order
+#undef PBG_IDS
+  for (int i = 0; i < PBG_N_ROBOTS; i++)
     if (!strcmp(env_id, ids[i][0]) || !strcmp(env_id, ids[i][1])) return i;
   return -1;
 }
 
-// The per-robot kernels of one precision (pbg_robot.hip)
-struct Kern {
-  int (*plan)(int, int, int, pbg::Geometry*);
-  int (*step)(const pbg::Buffers&, const pbg::StepIO&, float*, const pbg::Geometry&, hipStream_t);
-  int (*reset)(const pbg::Buffers&, const pbg::ResetIO&, hipStream_t);
-  int (*get_state)(const pbg::Buffers&, double*, double*, hipStream_t);
-  int (*set_state)(const pbg::Buffers&, const double*, const double*, hipStream_t);
-};
+using pbg::Kern;  // pbg_launch.h: a robot's launchers of one precision
 struct Ops {
-  Kern k32, k64;  // float32 kernels; the float64 (reference-precision) kernels
-  int (*pack)(int, const double*, double*, hipStream_t);
+  const pbg::RobotOps* r;  // the robot unit's launchers (pbg_robot.hip)
   pbg_info_t info;
   int pack_in, pack_out;
   pbg_sim_params_t defaults;
@@ -104,28 +82,22 @@ int check_sim_params(const pbg_sim_params_t& p) {
   return PBG_OK;
 }
 
-#define PBG_OPS(NAME, RID)                                                                                   \
-  Ops{Kern{pbg::plan_##NAME, pbg::launch_step_##NAME, pbg::launch_reset_##NAME, pbg::launch_get_state_##NAME,  \
-           pbg::launch_set_state_##NAME},                                                                    \
-      Kern{pbg::plan64_##NAME, pbg::launch_step64_##NAME, pbg::launch_reset64_##NAME,                        \
-           pbg::launch_get_state64_##NAME, pbg::launch_set_state64_##NAME},                                  \
-      pbg::launch_pack_##NAME, info_of<pbg_models::NAME>(RID), pbg::PackRec<pbg_models::NAME>::IN,          \
-      pbg::PackRec<pbg_models::NAME>::OUT, defaults_of<pbg_models::NAME>()}
-
 const Ops* ops(int rid) {
-  static const Ops table[17] = {PBG_OPS(Pendulum, 0), PBG_OPS(Hopper, 1), PBG_OPS(HalfCheetah, 2), PBG_OPS(Ant, 3),
-                                PBG_OPS(Humanoid, 4), PBG_OPS(Walker2D, 5), PBG_OPS(PendulumSwingup, 6),
-                                PBG_OPS(DoublePendulum, 7), PBG_OPS(HumanoidFlagrun, 8), PBG_OPS(HopperMuJoCo, 9),
-                                PBG_OPS(Walker2DMuJoCo, 10), PBG_OPS(HalfCheetahMuJoCo, 11), PBG_OPS(AntMuJoCo, 12),
-                                PBG_OPS(HumanoidMuJoCo, 13), PBG_OPS(DoublePendulumMuJoCo, 14),
-                                PBG_OPS(HumanoidFlagrunHarder, 15), PBG_OPS(Atlas, 16)};
-  return (rid >= 0 && rid < 17) ? &table[rid] : nullptr;
+#define PBG_OPS(NAME, ID, ENV, KEY)                                                                     \
+  Ops{&pbg::robot_ops_##NAME(), info_of<pbg_models::NAME>(ID), pbg::PackRec<pbg_models::NAME>::IN,      \
+      pbg::PackRec<pbg_models::NAME>::OUT, defaults_of<pbg_models::NAME>()},
+  static const Ops table[PBG_N_ROBOTS] = {PBG_ROBOTS(PBG_OPS)};
+#undef PBG_OPS
+  return (rid >= 0 && rid < PBG_N_ROBOTS) ? &table[rid] : nullptr;
 }
 
 using pbg::DeviceGuard;  // pbg_internal.h
 
 int hip_check(int e, const char* what) {
   if (e == (int)hipSuccess) return PBG_OK;
+  // the error is reported here: do not leave it in the runtime's sticky last-error too, where the caller's
+  // next launch check (torch's) would find it (a refused float64 lane plan of the Humanoid family did)
+  (void)hipGetLastError();
   return fail(PBG_E_HIP, "%s: HIP error %ld", what, (long)e);
 }
 
@@ -153,6 +125,33 @@ struct pbg_handle {
   pbg_info_t info;
   pbg_sim_params_t params;
 };
+
+namespace {
+// The handle's ten per-env device buffers: pbg_create_v2 allocates and zeroes them, pbg_destroy frees them
+struct DevBuf {
+  void** p;
+  size_t bytes;
+  const char* what;
+};
+struct DevBufs {
+  DevBuf b[10];
+};
+DevBufs dev_bufs(pbg_handle* h) {
+  pbg::Buffers& B = h->B;
+  const size_t n = (size_t)h->n;
+  const size_t wb = h->precision == 64 ? sizeof(double) : sizeof(float);  // state / z0 / workspace word
+  return DevBufs{{{&B.st, wb * n * h->info.state_words, "hipMalloc state"},
+                   {(void**)&B.pot, sizeof(double) * n, "hipMalloc potential"},
+                   {&B.z0, wb * n, "hipMalloc z0"},
+                   {(void**)&B.elapsed, sizeof(int) * n, "hipMalloc elapsed"},
+                   {(void**)&B.flags, sizeof(uint32_t) * n, "hipMalloc flags"},
+                   {(void**)&B.episode, sizeof(uint32_t) * n, "hipMalloc episode"},
+                   {(void**)&B.tgt, sizeof(double) * 2 * n, "hipMalloc walk target"},
+                   {(void**)&B.ftm, sizeof(int32_t) * 2 * n, "hipMalloc flag counters"},
+                   {(void**)&B.hkd, sizeof(double) * 2 * n, "hipMalloc crawl potentials"},
+                   {(void**)&B.hki, sizeof(int32_t) * 3 * n, "hipMalloc cube counters"}}};
+}
+}  // namespace
 
 // pbg_internal.h: the policy translation unit's access to the error message and the handle
 namespace pbg {
@@ -231,7 +230,7 @@ int pbg_create_v2(const char* env_id, int n_envs, int device, uint64_t seed, int
   h->n = n_envs;
   h->precision = co.precision;
   h->ops = o;
-  h->k = co.precision == 64 ? &o->k64 : &o->k32;
+  h->k = co.precision == 64 ? &o->r->k64 : &o->r->k32;
   h->info = o->info;
   h->info.n_envs = n_envs;
   h->info.substeps = sp.frame_skip;
@@ -244,15 +243,14 @@ int pbg_create_v2(const char* env_id, int n_envs, int device, uint64_t seed, int
                                         sp.joint_limit_erp, PBG_ANGULAR_MOTION_THRESHOLD);
   B.sp64 = pbg::resolve_sim_params<double>(sp.timestep, sp.frame_skip, sp.solver_iterations, sp.gravity,
                                            sp.contact_erp, sp.joint_limit_erp, PBG_ANGULAR_MOTION_THRESHOLD);
-  const size_t n = (size_t)n_envs;
   int cus = 256;
   (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
   // kernel variant: 1 = default (quad for Ant, gang for the other walkers), 0 = the
   // one-lane-per-env kernel for every robot, 2 = the gang kernel for every walker
   const int mode = (opts && (opts->kernel == 0 || opts->kernel == 2)) ? opts->kernel : 1;
-  h->geo.force_dist = opts ? opts->gang_dist : -1;
-  h->geo.gang_lanes = (opts && (opts->gang_lanes == 16 || opts->gang_lanes == 32)) ? opts->gang_lanes : -1;
-  int e = hip_check(h->k->plan(n_envs, cus, mode, &h->geo), "kernel attributes");
+  const pbg::PlanRequest rq = {mode, opts->gang_dist,
+                               (opts->gang_lanes == 16 || opts->gang_lanes == 32) ? opts->gang_lanes : -1};
+  int e = hip_check(h->k->plan(n_envs, cus, rq, &h->geo), "kernel attributes");
   // diagnostic options that the chosen kernel cannot honour are refused, not ignored: an A/B
   // run must never measure another kernel than the one it asked for.  Checked before any plan failure is
   // reported, so an option's refusal is PBG_E_ARG in both precisions.
@@ -282,29 +280,11 @@ int pbg_create_v2(const char* env_id, int n_envs, int device, uint64_t seed, int
   }
   // cap on the LDS-resident contact rows (tests of the device-workspace path)
   if (opts && opts->lds_rows >= 0 && opts->lds_rows < h->geo.lds_rows) h->geo.lds_rows = opts->lds_rows;
-  const size_t wb = co.precision == 64 ? sizeof(double) : sizeof(float);  // state / z0 / workspace word
-  e |= hip_check(hipMalloc(&B.st, wb * n * h->info.state_words), "hipMalloc state");
-  e |= hip_check(hipMalloc(&B.pot, sizeof(double) * n), "hipMalloc potential");
-  e |= hip_check(hipMalloc(&B.z0, wb * n), "hipMalloc z0");
-  e |= hip_check(hipMalloc(&B.elapsed, sizeof(int) * n), "hipMalloc elapsed");
-  e |= hip_check(hipMalloc(&B.flags, sizeof(uint32_t) * n), "hipMalloc flags");
-  e |= hip_check(hipMalloc(&B.episode, sizeof(uint32_t) * n), "hipMalloc episode");
-  e |= hip_check(hipMalloc(&B.tgt, sizeof(double) * 2 * n), "hipMalloc walk target");
-  e |= hip_check(hipMalloc(&B.ftm, sizeof(int32_t) * 2 * n), "hipMalloc flag counters");
-  e |= hip_check(hipMalloc(&B.hkd, sizeof(double) * 2 * n), "hipMalloc crawl potentials");
-  e |= hip_check(hipMalloc(&B.hki, sizeof(int32_t) * 3 * n), "hipMalloc cube counters");
-  e |= hip_check(hipMalloc(&h->scratch, (size_t)h->geo.word_bytes * n * h->geo.scratch_words_per_env), "hipMalloc scratch");
+  const DevBufs bufs = dev_bufs(h);
+  for (const DevBuf& b : bufs.b) e |= hip_check(hipMalloc(b.p, b.bytes), b.what);
+  e |= hip_check(hipMalloc(&h->scratch, (size_t)h->geo.word_bytes * h->n * h->geo.scratch_words_per_env), "hipMalloc scratch");
   if (!e) {
-    e |= hip_check(hipMemset(B.st, 0, wb * n * h->info.state_words), "hipMemset");
-    e |= hip_check(hipMemset(B.pot, 0, sizeof(double) * n), "hipMemset");
-    e |= hip_check(hipMemset(B.z0, 0, wb * n), "hipMemset");
-    e |= hip_check(hipMemset(B.elapsed, 0, sizeof(int) * n), "hipMemset");
-    e |= hip_check(hipMemset(B.flags, 0, sizeof(uint32_t) * n), "hipMemset");
-    e |= hip_check(hipMemset(B.episode, 0, sizeof(uint32_t) * n), "hipMemset");
-    e |= hip_check(hipMemset(B.tgt, 0, sizeof(double) * 2 * n), "hipMemset");
-    e |= hip_check(hipMemset(B.ftm, 0, sizeof(int32_t) * 2 * n), "hipMemset");
-    e |= hip_check(hipMemset(B.hkd, 0, sizeof(double) * 2 * n), "hipMemset");
-    e |= hip_check(hipMemset(B.hki, 0, sizeof(int32_t) * 3 * n), "hipMemset");
+    for (const DevBuf& b : bufs.b) e |= hip_check(hipMemset(*b.p, 0, b.bytes), "hipMemset");
     e |= hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
   }
   if (e) {
@@ -318,10 +298,9 @@ int pbg_create_v2(const char* env_id, int n_envs, int device, uint64_t seed, int
 void pbg_destroy(pbg_handle* h) {
   if (!h) return;
   DeviceGuard dg(h->device);
-  void* bufs[] = {h->B.st, h->B.pot, h->B.z0, h->B.elapsed, h->B.flags, h->B.episode, h->B.tgt, h->B.ftm,
-                  h->B.hkd, h->B.hki, h->scratch};
-  for (void* p : bufs)
-    if (p) (void)hipFree(p);
+  for (const DevBuf& b : dev_bufs(h).b)
+    if (*b.p) (void)hipFree(*b.p);
+  if (h->scratch) (void)hipFree(h->scratch);
   delete h;
 }
 
@@ -394,16 +373,7 @@ int pbg_pack_record_sizes(const char* env_id, int* in_words, int* out_words) {
 #ifdef PBG_STAMPS
 // diagnostic build only: read and clear the per-phase wave-cycle sums of one robot's kernel
 int pbg_debug_stamps(int rid, unsigned long long* host_out) {
-  using F = int (*)(unsigned long long*);
-  static const F table[17] = {pbg::debug_stamps_Pendulum, pbg::debug_stamps_Hopper, pbg::debug_stamps_HalfCheetah,
-                              pbg::debug_stamps_Ant, pbg::debug_stamps_Humanoid, pbg::debug_stamps_Walker2D,
-                              pbg::debug_stamps_PendulumSwingup, pbg::debug_stamps_DoublePendulum,
-                              pbg::debug_stamps_HumanoidFlagrun, pbg::debug_stamps_HopperMuJoCo,
-                              pbg::debug_stamps_Walker2DMuJoCo, pbg::debug_stamps_HalfCheetahMuJoCo,
-                              pbg::debug_stamps_AntMuJoCo, pbg::debug_stamps_HumanoidMuJoCo,
-                              pbg::debug_stamps_DoublePendulumMuJoCo, pbg::debug_stamps_HumanoidFlagrunHarder,
-                              pbg::debug_stamps_Atlas};
-  return (rid >= 0 && rid < 17) ? table[rid](host_out) : PBG_E_ENV;
+  return ops(rid) ? ops(rid)->r->stamps(host_out) : PBG_E_ENV;
 }
 #endif
 
@@ -443,7 +413,7 @@ int pbg_sample_actions(int action_dim, int n_envs, int n_steps, uint64_t seed, u
 // workgroups on that CU start on it instead of on whatever an earlier kernel left there
 __global__ __launch_bounds__(256) void poison_lds_kernel(uint32_t pattern) {
   extern __shared__ uint32_t lds_poison[];
-  for (int i = threadIdx.x; i < 163840 / 4; i += 256) lds_poison[i] = pattern;
+  for (int i = threadIdx.x; i < pbg::CU_LDS_BYTES / 4; i += 256) lds_poison[i] = pattern;
   __syncthreads();
 }
 
@@ -456,10 +426,10 @@ int pbg_debug_poison(pbg_handle* h, uint32_t pattern, void* stream) {
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
     return fail(PBG_E_HIP, "pbg_debug_poison: no CU count%s%ld");
   int e = hip_check((int)hipFuncSetAttribute((const void*)poison_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             163840), "poison attribute");
+                                             pbg::CU_LDS_BYTES), "poison attribute");
   if (e) return e;
   // one 160 KB workgroup fills a CU; 8 per CU reach every CU of every XCD whatever the dispatch order
-  hipLaunchKernelGGL(poison_lds_kernel, dim3((unsigned)(8 * cus)), dim3(256), 163840, (hipStream_t)stream, pattern);
+  hipLaunchKernelGGL(poison_lds_kernel, dim3((unsigned)(8 * cus)), dim3(256), pbg::CU_LDS_BYTES, (hipStream_t)stream, pattern);
   e = hip_check((int)hipGetLastError(), "poison launch");
   if (e || !h) return e;
   const size_t words = (size_t)h->geo.word_bytes * (size_t)h->B.n * (size_t)h->geo.scratch_words_per_env / 4;
@@ -476,7 +446,7 @@ int pbg_pack(const char* env_id, int n, const double* in_rec, double* out_rec, v
   if (dev < 0 || device_of(in_rec) != dev)
     return fail(PBG_E_ARG, "pbg_pack: in_rec / out_rec are not device memory of one GPU%s%ld");
   DeviceGuard dg(dev);
-  return hip_check(ops(rid)->pack(n, in_rec, out_rec, (hipStream_t)stream), "pack_kernel launch");
+  return hip_check(ops(rid)->r->pack(n, in_rec, out_rec, (hipStream_t)stream), "pack_kernel launch");
 }
 
 }  // extern "C"

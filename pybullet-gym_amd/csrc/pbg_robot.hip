@@ -1,5 +1,7 @@
-// pbg_robot.hip -- per-robot kernel instantiations + launchers.  Compiled once per robot
-// with -DPBG_ROBOT=<Pendulum|Hopper|HalfCheetah|Ant|Humanoid>.
+// pbg_robot.hip -- per-robot kernel instantiations + launchers.  Compiled once per robot with
+// -DPBG_ROBOT=<a struct of models_gen.h> (Makefile ROBOTS), and once more with -DPBG_TEAM64_TU for the
+// float64 quad kernel's own unit.  The launchers are written once, as templates over the robot type RR and
+// the lane kernel's robot type RL: <R, R> for float32, <F64<R>, F64L<R>> for float64.
 #include <hip/hip_runtime.h>
 
 #include "pbg_launch.h"
@@ -30,6 +32,21 @@ static int kernel_attrs(const void* fn, Geometry* g) {
   return (int)e;
 }
 
+// The capacity arithmetic the three planners share.  Workgroups of `epw` envs a CU holds when n_envs are
+// spread over `cus` CUs: they share its LDS.
+static inline int wgs_per_cu(int n_envs, int epw, int cus) {
+  const int wgs = (n_envs + epw - 1) / epw;
+  const int wpc = (wgs + cus - 1) / cus;
+  return wpc > 0 ? wpc : 1;
+}
+// Rows (gang: contacts) of `row_words` words per env that fit a workgroup's LDS share of `budget` bytes: `epw`
+// envs of `wb`-byte words, `fixed_words` per env taken first; at most `max_rows`
+static inline int row_capacity(long budget, int epw, long wb, long fixed_words, int row_words, int max_rows) {
+  const long words = budget / ((long)epw * wb) - fixed_words;
+  const int cap = (int)(words / row_words);
+  return cap > max_rows ? max_rows : (cap < 0 ? 0 : cap);
+}
+
 // Geometry: one env per lane, one wave per workgroup.  With fewer than 64 envs per CU
 // the workgroup shrinks to 32 or 16 active lanes so every CU gets a wave (the step is
 // issue/latency bound: a wave's time barely depends on its active lanes).  All resident
@@ -43,13 +60,7 @@ static int plan_team(int n_envs, int cus, Geometry* g) {
     using RW = TRows<RR, 16>;
     constexpr int ES = 16;
     constexpr size_t WB = sizeof(real_t<RR>);  // row word: float, or double on the float64 path
-    const int wgs = (n_envs + ES - 1) / ES;
-    const int wpc = (wgs + cus - 1) / cus;
-    const size_t budget = (size_t)163840 / (size_t)(wpc > 0 ? wpc : 1);
-    long words = (long)(budget / ((size_t)ES * WB)) - RW::HEAD;
-    int cap = (int)(words / RW::W);
-    if (cap > RW::MR) cap = RW::MR;
-    if (cap < 0) cap = 0;
+    const int cap = row_capacity(CU_LDS_BYTES / wgs_per_cu(n_envs, ES, cus), ES, (long)WB, RW::HEAD, RW::W, RW::MR);
     size_t per_env = (size_t)RW::HEAD + (size_t)cap * RW::W;
     if (per_env < (size_t)(2 * RR::NL + 2 * RR::NJ)) per_env = 2 * RR::NL + 2 * RR::NJ;  // pack staging
     g->team = 4;
@@ -100,14 +111,15 @@ template <class RR, int T>
 constexpr bool gang_repl() {
   return T == 16 && !RR::harder && (sizeof(real_t<RR>) == 4 || RR::NDOF < 8);
 }
+// force_dist: PlanRequest::gang_dist
 template <class RR, int T>
-static int plan_gang_t(int n_envs, int cus, Geometry* g) {
+static int plan_gang_t(int n_envs, int cus, int force_dist, Geometry* g) {
   if constexpr (gang_ok<RR, T>()) {
     using G = Gang<RR, T>;
     constexpr long WB = (long)sizeof(real_t<RR>);  // env-region word: 4 bytes, or 8 on the float64 path
     constexpr int EPB = gang_block<RR, T>() / T;  // envs per workgroup
     // the layout's floor (fixed words + the kinematic area, no LDS contact) must fit one CU's LDS
-    static_assert(4L * GangTabs<RR>::WORDS + WB * EPB * ((G::FIXED + G::MIN_CONTACT_WORDS + 3L) & ~3L) <= 163840L,
+    static_assert(4L * GangTabs<RR>::WORDS + WB * EPB * ((G::FIXED + G::MIN_CONTACT_WORDS + 3L) & ~3L) <= CU_LDS_BYTES,
                   "gang env regions exceed the CU's LDS");
     // every env region 16-byte (front path: b128 LDS loads) or 8-byte (b64 row loads) aligned:
     // round the region up, and give back a contact when the rounding crosses the budget
@@ -115,27 +127,23 @@ static int plan_gang_t(int n_envs, int cus, Geometry* g) {
       const int w = G::FIXED + (c * G::PERC > G::MIN_CONTACT_WORDS ? c * G::PERC : G::MIN_CONTACT_WORDS);
       return (w + G::REGION_ALIGN - 1) & ~(G::REGION_ALIGN - 1);
     };
-    const int wgs = (n_envs + EPB - 1) / EPB;
-    int wpc = (wgs + cus - 1) / cus;
+    int wpc = wgs_per_cu(n_envs, EPB, cus);
     // the workgroups a CU can hold at all (no LDS contact): planning the contact capacity for more
     // resident workgroups than fit would shrink it for nothing (round 5: float64 HalfCheetah and
     // Humanoid, Atlas -- one workgroup per CU, planned for two, had no LDS contact)
-    const long fit0 = 163840L / (4L * (long)GangTabs<RR>::WORDS + WB * EPB * (long)region(0));
+    const long fit0 = (long)CU_LDS_BYTES / (4L * (long)GangTabs<RR>::WORDS + WB * EPB * (long)region(0));
     if (wpc > fit0) wpc = fit0 > 0 ? (int)fit0 : 1;
     // signed: with many workgroups per CU the share can be smaller than the model tables
-    long budget = 163840L / (long)(wpc > 0 ? wpc : 1) - 4L * (long)GangTabs<RR>::WORDS;
+    long budget = (long)CU_LDS_BYTES / wpc - 4L * (long)GangTabs<RR>::WORDS;
     if (budget < 0) budget = 0;
-    long words = budget / (long)(EPB * WB) - G::FIXED;
-    int cap = (int)(words / G::PERC);
-    if (cap > G::MAXC) cap = G::MAXC;
-    if (cap < 0) cap = 0;
+    int cap = row_capacity(budget, EPB, WB, G::FIXED, G::PERC, G::MAXC);
     while (cap > 0 && (long)region(cap) * EPB * WB > budget) cap--;
     // distributed dynamics from 8 dofs (Walker2D, HalfCheetah, Humanoid: round-2 A/B) or more than one wave per SIMD (its
     // smaller register footprint lets two waves share a SIMD); replicated otherwise
     constexpr bool REPL = gang_repl<RR, T>();  // has a replicated variant
     g->gang_dist = !REPL || RR::NDOF >= 8 || (size_t)n_envs * T > (size_t)64 * 4 * cus;
     // pbg_create_debug (32-lane gangs, the cube robot and float64 from 8 dofs have no replicated-dynamics variant)
-    if ((g->force_dist == 0 || g->force_dist == 1) && REPL) g->gang_dist = g->force_dist;
+    if ((force_dist == 0 || force_dist == 1) && REPL) g->gang_dist = force_dist;
     g->team = T;
     g->block = gang_block<RR, T>();
     g->lds_rows = cap;
@@ -143,7 +151,7 @@ static int plan_gang_t(int n_envs, int cus, Geometry* g) {
     g->lds_bytes = 4 * (size_t)GangTabs<RR>::WORDS + (size_t)WB * (size_t)EPB * (size_t)g->env_words;
     // the workgroup's regions must fit the CU's LDS (the contact floor MIN_CONTACT_WORDS is the only
     // term the budget does not bound: a model whose tables + floor exceed it is not launchable)
-    if (g->lds_bytes > (size_t)163840) return (int)hipErrorInvalidConfiguration;
+    if (g->lds_bytes > (size_t)CU_LDS_BYTES) return (int)hipErrorInvalidConfiguration;
     g->scratch_words_per_env = G::GWORDS;
     g->word_bytes = (int)WB;
     const void* fn;
@@ -154,16 +162,9 @@ static int plan_gang_t(int n_envs, int cus, Geometry* g) {
     const int e = (int)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g->lds_bytes);
     return e ? e : kernel_attrs(fn, g);
   } else {
-    (void)n_envs; (void)cus; (void)g;
+    (void)n_envs; (void)cus; (void)force_dist; (void)g;
     return (int)hipErrorInvalidValue;
   }
-}
-// lanes: 16 or 32 (pbg_create_debug gang_lanes), -1: the plan's choice
-template <class RR>
-static int plan_gang(int n_envs, int cus, Geometry* g, int lanes) {
-  if (lanes < 0) lanes = 16;
-  if (lanes == 32) return plan_gang_t<RR, 32>(n_envs, cus, g);
-  return plan_gang_t<RR, 16>(n_envs, cus, g);
 }
 template <class RR, int T>
 static bool launch_gang_t(const Buffers& B, const StepIO& io, float* scratch, const Geometry& g, hipStream_t s) {
@@ -209,15 +210,9 @@ static int plan_lane(int n_envs, int cus, Geometry* g) {
     const int per_cu = (n_envs + cus - 1) / cus;
     int b = 16;
     while (b < per_cu && b < 64) b *= 2;
-    const int wgs = (n_envs + b - 1) / b;
-    const int wpc = (wgs + cus - 1) / cus;
-    const size_t budget = (size_t)163840 / (size_t)(wpc > 0 ? wpc : 1);
     using RW = Rows<RR, 64>;
     constexpr size_t WB = sizeof(real_t<RR>);  // LDS word: float, or double on the float64 path
-    long words = (long)(budget / ((size_t)b * WB)) - RW::NC - RW::LIMW;
-    int cap = (int)(words / RW::W);
-    if (cap > RW::MR) cap = RW::MR;
-    if (cap < 0) cap = 0;
+    const int cap = row_capacity(CU_LDS_BYTES / wgs_per_cu(n_envs, b, cus), b, (long)WB, RW::NC + RW::LIMW, RW::W, RW::MR);
     g->block = b;
     g->lds_rows = cap;
     g->lds_bytes = (size_t)b * WB * ((size_t)RW::LIMW + (size_t)cap * RW::W + RW::NC);
@@ -286,81 +281,78 @@ bool PBG_FN(launch_team64_)(const Buffers& B, const StepIO& io, float* scratch, 
 }
 #else
 
-// mode: 0 = lane kernel; 1 = default (quad for Ant, gang for the other walkers -- HumanoidFlagrunHarder
-// and Atlas included: the cube robot runs the gang kernel's front path, distributed dynamics only);
-// 2 = gang for every walker (parity tests of the gang kernel on Ant).
-int PBG_FN(plan_)(int n_envs, int cus, int mode, Geometry* g) {
-  if (Team<R>::ok && mode == 1) return plan_team<R>(n_envs, cus, g);
-  if (R::kind != 1 && (mode >= 1 || !lane_ok<R>())) return plan_gang<R>(n_envs, cus, g, g->gang_lanes);
-  return plan_lane<R>(n_envs, cus, g);
+// ---- one launcher set, instantiated per precision: <RR, RL> = <R, R> and <R64, R64L>.  Two rules are all
+// that depends on the precision.
+// The quad kernel of a float64 robot is the PBG_TEAM64_TU unit's (above), never instantiated here
+template <class RR>
+constexpr bool quad_in_t64_unit() { return sizeof(real_t<RR>) == 8; }
+// The gang width a plan picks by itself.  The Humanoid family's float64 default is 32 lanes: its float64
+// regions let a CU hold 8 envs, which 32-lane gangs spread over all four SIMDs (0.493 -> 0.471 ms at 4,096
+// Humanoid envs)
+template <class RR>
+constexpr int default_gang_lanes() { return sizeof(real_t<RR>) == 8 && gang_ok<RR, 32>() ? 32 : 16; }
+
+template <class RR>
+static int plan_quad(int n_envs, int cus, Geometry* g) {
+  if constexpr (quad_in_t64_unit<RR>()) return PBG_FN(plan_team64_)(n_envs, cus, g);
+  else return plan_team<RR>(n_envs, cus, g);
+}
+template <class RR>
+static bool launch_quad(const Buffers& B, const StepIO& io, float* scratch, const Geometry& g, hipStream_t s) {
+  if constexpr (quad_in_t64_unit<RR>()) return PBG_FN(launch_team64_)(B, io, scratch, g, s);
+  else return launch_team<RR>(B, io, scratch, g, s);
 }
 
-int PBG_FN(launch_step_)(const Buffers& B, const StepIO& io, float* scratch, const Geometry& g, hipStream_t s) {
-  if (launch_team<R>(B, io, scratch, g, s)) return (int)hipGetLastError();
-  if (launch_gang<R>(B, io, scratch, g, s)) return (int)hipGetLastError();
-  return launch_lane<R>(B, io, scratch, g, s);
-}
-
-int PBG_FN(launch_reset_)(const Buffers& B, const ResetIO& io, hipStream_t s) {
-  hipLaunchKernelGGL(reset_kernel<R>, dim3(blocks(B.n, 64)), dim3(64), 0, s, B, io);
-  return (int)hipGetLastError();
-}
-
-int PBG_FN(launch_get_state_)(const Buffers& B, double* phys, double* aux, hipStream_t s) {
-  hipLaunchKernelGGL(get_state_kernel<R>, dim3(blocks(B.n, 64)), dim3(64), 0, s, B, phys, aux);
-  return (int)hipGetLastError();
-}
-
-int PBG_FN(launch_set_state_)(const Buffers& B, const double* phys, const double* aux, hipStream_t s) {
-  hipLaunchKernelGGL(set_state_kernel<R>, dim3(blocks(B.n, 64)), dim3(64), 0, s, B, phys, aux);
-  return (int)hipGetLastError();
-}
-
-int PBG_FN(launch_pack_)(int n, const double* in, double* out, hipStream_t s) {
-  hipLaunchKernelGGL(pack_kernel<R>, dim3(blocks(n, 64)), dim3(64), 0, s, n, in, out);
-  return (int)hipGetLastError();
-}
-
-// ---- the reference-precision path (pbg_create_v2 precision 64): float64 physics state and
-// arithmetic (pybullet's btScalar, scene_bases.py:75-76) for every robot with at most 128
-// floor-contact slots (Atlas: PBG_E_HIP at create).  mode 0: the lane-per-env
-// kernel (the float64 gang and quad kernels' parity cross-check); 1 (default): the quad kernel for Ant
-// (team64_ok), the 16-lane gang kernel for the other walkers and the lane kernel for the pendulums;
-// 2: the gang kernel for every walker (Ant included).
-int PBG_FN(plan64_)(int n_envs, int cus, int mode, Geometry* g) {
-  if (team64_ok<R64>() && mode == 1) return PBG_FN(plan_team64_)(n_envs, cus, g);
-  if constexpr (gang_ok<R64, 16>()) {
-    if (mode != 0) {
-      // the Humanoid family's default is 32 lanes: its float64 regions let a CU hold 8 envs, which
-      // 32-lane gangs spread over all four SIMDs (0.493 -> 0.471 ms at 4,096 Humanoid envs)
-      if (g->gang_lanes == 32 || (g->gang_lanes < 0 && gang_ok<R64, 32>())) {
-        if constexpr (gang_ok<R64, 32>()) return plan_gang_t<R64, 32>(n_envs, cus, g);
-        else return (int)hipErrorInvalidValue;
-      }
-      return plan_gang_t<R64, 16>(n_envs, cus, g);
-    }
+// rq.mode: 0 = lane kernel (the gang and quad kernels' parity cross-check); 1 = default: quad for Ant and
+// AntMuJoCo (Team<RR>::ok), gang for the other walkers -- HumanoidFlagrunHarder and Atlas included: the cube
+// robot runs the gang kernel's front path, distributed dynamics only -- and the lane kernel for the pendulums;
+// 2 = gang for every walker (parity tests of the gang kernel on Ant).  Both precisions plan every robot:
+// float64 (pbg_create_v2 precision 64: float64 physics state and arithmetic, pybullet's btScalar,
+// scene_bases.py:75-76) runs Atlas on the 16-lane gang kernel.  A robot without a lane kernel (Atlas) gets
+// the gang plan under mode 0 too, which pbg_create_v2 refuses with PBG_E_ARG.
+template <class RR, class RL>
+static int plan(int n_envs, int cus, const PlanRequest& rq, Geometry* g) {
+  if (Team<RR>::ok && rq.mode == 1) return plan_quad<RR>(n_envs, cus, g);
+  if (gang_ok<RR, 16>() && (rq.mode != 0 || !lane_ok<RL>())) {
+    const int lanes = rq.gang_lanes < 0 ? default_gang_lanes<RR>() : rq.gang_lanes;
+    if (lanes == 32) return plan_gang_t<RR, 32>(n_envs, cus, rq.gang_dist, g);
+    return plan_gang_t<RR, 16>(n_envs, cus, rq.gang_dist, g);
   }
-  return plan_lane<R64L>(n_envs, cus, g);
+  return plan_lane<RL>(n_envs, cus, g);
 }
-int PBG_FN(launch_step64_)(const Buffers& B, const StepIO& io, float* scratch, const Geometry& g, hipStream_t s) {
-  if (PBG_FN(launch_team64_)(B, io, scratch, g, s)) return (int)hipGetLastError();
-  if (launch_gang<R64>(B, io, scratch, g, s)) return (int)hipGetLastError();
-  return launch_lane<R64L>(B, io, scratch, g, s);
+
+template <class RR, class RL>
+static int launch_step(const Buffers& B, const StepIO& io, float* scratch, const Geometry& g, hipStream_t s) {
+  if (launch_quad<RR>(B, io, scratch, g, s)) return (int)hipGetLastError();
+  if (launch_gang<RR>(B, io, scratch, g, s)) return (int)hipGetLastError();
+  return launch_lane<RL>(B, io, scratch, g, s);
 }
-int PBG_FN(launch_reset64_)(const Buffers& B, const ResetIO& io, hipStream_t s) {
-  hipLaunchKernelGGL(reset_kernel<R64>, dim3(blocks(B.n, 64)), dim3(64), 0, s, B, io);
-  return (int)hipGetLastError();
-}
-int PBG_FN(launch_get_state64_)(const Buffers& B, double* phys, double* aux, hipStream_t s) {
-  hipLaunchKernelGGL(get_state_kernel<R64>, dim3(blocks(B.n, 64)), dim3(64), 0, s, B, phys, aux);
-  return (int)hipGetLastError();
-}
-int PBG_FN(launch_set_state64_)(const Buffers& B, const double* phys, const double* aux, hipStream_t s) {
-  hipLaunchKernelGGL(set_state_kernel<R64>, dim3(blocks(B.n, 64)), dim3(64), 0, s, B, phys, aux);
+
+template <class RR>
+static int launch_reset(const Buffers& B, const ResetIO& io, hipStream_t s) {
+  hipLaunchKernelGGL(reset_kernel<RR>, dim3(blocks(B.n, 64)), dim3(64), 0, s, B, io);
   return (int)hipGetLastError();
 }
 
-int PBG_FN(debug_stamps_)(unsigned long long* host_out) {
+template <class RR>
+static int launch_get_state(const Buffers& B, double* phys, double* aux, hipStream_t s) {
+  hipLaunchKernelGGL(get_state_kernel<RR>, dim3(blocks(B.n, 64)), dim3(64), 0, s, B, phys, aux);
+  return (int)hipGetLastError();
+}
+
+template <class RR>
+static int launch_set_state(const Buffers& B, const double* phys, const double* aux, hipStream_t s) {
+  hipLaunchKernelGGL(set_state_kernel<RR>, dim3(blocks(B.n, 64)), dim3(64), 0, s, B, phys, aux);
+  return (int)hipGetLastError();
+}
+
+template <class RR>
+static int launch_pack(int n, const double* in, double* out, hipStream_t s) {
+  hipLaunchKernelGGL(pack_kernel<RR>, dim3(blocks(n, 64)), dim3(64), 0, s, n, in, out);
+  return (int)hipGetLastError();
+}
+
+static int debug_stamps(unsigned long long* host_out) {
 #ifdef PBG_STAMPS
   if (hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_stamps), sizeof(unsigned long long) * 16) != hipSuccess) return -3;
   unsigned long long z[16] = {0};
@@ -374,6 +366,15 @@ int PBG_FN(debug_stamps_)(unsigned long long* host_out) {
   (void)host_out;
   return -1;
 #endif
+}
+
+// this unit's whole host interface (pbg_launch.h).  The kernels are instantiated, and so laid out in the
+// code object, in the order this initializer names their launchers: keep it, the ISA comparison of DESIGN.md
+// section 6 is byte for byte
+#define PBG_KERN(RR, RL) {plan<RR, RL>, launch_step<RR, RL>, launch_reset<RR>, launch_get_state<RR>, launch_set_state<RR>}
+const RobotOps& PBG_FN(robot_ops_)() {
+  static const RobotOps ops = {PBG_KERN(R, R), launch_pack<R>, PBG_KERN(R64, R64L), debug_stamps};
+  return ops;
 }
 #endif  // PBG_TEAM64_TU
 }  // namespace pbg

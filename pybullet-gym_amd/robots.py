@@ -34,6 +34,8 @@ ALIVE_ATLAS = 13        # robot_locomotors.py:313-324 (+4 - knees at limit if he
 
 @dataclass
 class RobotSpec:
+    robot_id: int                                                # pbg_info_t.robot_id: never renumbered
+    struct: str                                                  # the C++ model struct (csrc/models_gen.h)
     env_id: str
     key: str
     mjcf: str
@@ -79,45 +81,54 @@ def _add(s: RobotSpec):
 
 
 # InvertedPendulum: robot_pendula.py:5-51, gym_pendulum_envs.py:7-42, envs/__init__.py:4-9
-_add(RobotSpec("InvertedPendulumPyBulletEnv-v0", "pendulum", "inverted_pendulum.xml", "cart",
+_add(RobotSpec(0, "Pendulum",
+               "InvertedPendulumPyBulletEnv-v0", "pendulum", "inverted_pendulum.xml", "cart",
                action_dim=1, obs_dim=5, kind=KIND_PENDULUM, power=1.0, alive=ALIVE_PENDULUM,
                timestep=0.0165, frame_skip=1, floor=False))
 # InvertedPendulumSwingup: robot_pendula.py:11-18,54-55 (hinge reset 3.1415 + u),
 # gym_pendulum_envs.py:26-34 (reward cos(theta), done False), envs/__init__.py:18-23
-_add(RobotSpec("InvertedPendulumSwingupPyBulletEnv-v0", "pendulum_swingup", "inverted_pendulum.xml", "cart",
+_add(RobotSpec(6, "PendulumSwingup",
+               "InvertedPendulumSwingupPyBulletEnv-v0", "pendulum_swingup", "inverted_pendulum.xml", "cart",
                action_dim=1, obs_dim=5, kind=KIND_PENDULUM, power=1.0, alive=ALIVE_SWINGUP,
                timestep=0.0165, frame_skip=1, floor=False, reset_offset=3.1415))
 # InvertedDoublePendulum: robot_pendula.py:58-88, gym_pendulum_envs.py:45-86, envs/__init__.py:11-16
-_add(RobotSpec("InvertedDoublePendulumPyBulletEnv-v0", "double_pendulum", "inverted_double_pendulum.xml", "cart",
+_add(RobotSpec(7, "DoublePendulum",
+               "InvertedDoublePendulumPyBulletEnv-v0", "double_pendulum", "inverted_double_pendulum.xml", "cart",
                action_dim=1, obs_dim=9, kind=KIND_PENDULUM, power=2.0, alive=ALIVE_DOUBLE,
                timestep=0.0165, frame_skip=1, floor=False))
 # InvertedDoublePendulumMuJoCoEnv: mujoco/robot_pendula.py:51-89, mujoco/gym_pendulum_envs.py:44-75,
 # envs/__init__.py:113-118 (InvertedPendulumMuJoCoEnv-v0 is not built: its reset reads
 # `self.swingup`, which the mujoco InvertedPendulum never defines -> AttributeError)
-_add(RobotSpec("InvertedDoublePendulumMuJoCoEnv-v0", "double_pendulum_mujoco", "inverted_double_pendulum.xml",
+_add(RobotSpec(14, "DoublePendulumMuJoCo",
+               "InvertedDoublePendulumMuJoCoEnv-v0", "double_pendulum_mujoco", "inverted_double_pendulum.xml",
                "cart", action_dim=1, obs_dim=11, kind=KIND_PENDULUM, power=2.0, alive=ALIVE_DOUBLE_MJ,
                timestep=0.0165, frame_skip=1, floor=False))
 # Hopper: robot_locomotors.py:82-90, envs/__init__.py:73-78
-_add(RobotSpec("HopperPyBulletEnv-v0", "hopper", "hopper.xml", "torso", action_dim=3, obs_dim=15,
+_add(RobotSpec(1, "Hopper",
+               "HopperPyBulletEnv-v0", "hopper", "hopper.xml", "torso", action_dim=3, obs_dim=15,
                kind=KIND_WALKER, power=0.75, foot_list=["foot"], alive=ALIVE_HOPPER))
 # HalfCheetah: robot_locomotors.py:109-127, envs/__init__.py:59-64
-_add(RobotSpec("HalfCheetahPyBulletEnv-v0", "halfcheetah", "half_cheetah.xml", "torso", action_dim=6,
+_add(RobotSpec(2, "HalfCheetah",
+               "HalfCheetahPyBulletEnv-v0", "halfcheetah", "half_cheetah.xml", "torso", action_dim=6,
                obs_dim=26, kind=KIND_WALKER, power=0.90,
                foot_list=["ffoot", "fshin", "fthigh", "bfoot", "bshin", "bthigh"], alive=ALIVE_HALFCHEETAH,
                power_coef={"bthigh": 120.0, "bshin": 90.0, "bfoot": 60.0, "fthigh": 140.0,
                            "fshin": 60.0, "ffoot": 30.0}))
 # Ant: robot_locomotors.py:130-138, envs/__init__.py:66-71
-_add(RobotSpec("AntPyBulletEnv-v0", "ant", "ant.xml", "torso", action_dim=8, obs_dim=28,
+_add(RobotSpec(3, "Ant",
+               "AntPyBulletEnv-v0", "ant", "ant.xml", "torso", action_dim=8, obs_dim=28,
                kind=KIND_WALKER, power=2.5,
                foot_list=["front_left_foot", "front_right_foot", "left_back_foot", "right_back_foot"],
                alive=ALIVE_ANT))
 # Walker2D: robot_locomotors.py:93-106 (foot power_coef 30 set in robot_specific_reset),
 # gym_locomotion_envs.py:128-131, envs/__init__.py:53-58
-_add(RobotSpec("Walker2DPyBulletEnv-v0", "walker2d", "walker2d.xml", "torso", action_dim=6, obs_dim=22,
+_add(RobotSpec(5, "Walker2D",
+               "Walker2DPyBulletEnv-v0", "walker2d", "walker2d.xml", "torso", action_dim=6, obs_dim=22,
                kind=KIND_WALKER, power=0.40, foot_list=["foot", "foot_left"], alive=ALIVE_HOPPER,
                power_coef={"foot_joint": 30.0, "foot_left_joint": 30.0}))
 # Humanoid: robot_locomotors.py:141-192, gym_locomotion_envs.py:146-151, envs/__init__.py:80-84
-_add(RobotSpec("HumanoidPyBulletEnv-v0", "humanoid", "humanoid_symmetric.xml", "torso", action_dim=17,
+_add(RobotSpec(4, "Humanoid",
+               "HumanoidPyBulletEnv-v0", "humanoid", "humanoid_symmetric.xml", "torso", action_dim=17,
                obs_dim=44, kind=KIND_WALKER, power=0.41, foot_list=["right_foot", "left_foot"],
                alive=ALIVE_HUMANOID,
                motor_order=["abdomen_z", "abdomen_y", "abdomen_x",
@@ -134,7 +145,8 @@ _add(RobotSpec("HumanoidPyBulletEnv-v0", "humanoid", "humanoid_symmetric.xml", "
 
 # HumanoidFlagrun: robot_locomotors.py:195-226 (flag_reposition / calc_state), the Humanoid
 # physics and rewards (gym_locomotion_envs.py:146-163), envs/__init__.py:86-91
-_add(RobotSpec("HumanoidFlagrunPyBulletEnv-v0", "humanoid_flagrun", "humanoid_symmetric.xml", "torso",
+_add(RobotSpec(8, "HumanoidFlagrun",
+               "HumanoidFlagrunPyBulletEnv-v0", "humanoid_flagrun", "humanoid_symmetric.xml", "torso",
                action_dim=17, obs_dim=44, kind=KIND_WALKER, power=0.41, foot_list=["right_foot", "left_foot"],
                alive=ALIVE_HUMANOID, motor_order=SPECS["humanoid"].motor_order,
                power_coef=dict(SPECS["humanoid"].power_coef), initial_z=0.8,
@@ -144,12 +156,15 @@ _add(RobotSpec("HumanoidFlagrunPyBulletEnv-v0", "humanoid_flagrun", "humanoid_sy
 # qpos[1:] + qvel of every ordered joint incl. the ignored root joints, reward
 # x-progress (+1 alive) + power cost; robot_locomotors.py (mujoco) :82-196,
 # gym_locomotion_envs.py (mujoco) :121-252, envs/__init__.py:121-146
-_add(RobotSpec("HopperMuJoCoEnv-v0", "hopper_mujoco", "hopper.xml", "torso", action_dim=3, obs_dim=11,
+_add(RobotSpec(9, "HopperMuJoCo",
+               "HopperMuJoCoEnv-v0", "hopper_mujoco", "hopper.xml", "torso", action_dim=3, obs_dim=11,
                kind=KIND_MUJOCO_PLANAR, power=0.75, alive=ALIVE_MJ_HOPPER, power_cost=-1e-3, qvel_clip=10.0))
-_add(RobotSpec("Walker2DMuJoCoEnv-v0", "walker2d_mujoco", "walker2d.xml", "torso", action_dim=6, obs_dim=17,
+_add(RobotSpec(10, "Walker2DMuJoCo",
+               "Walker2DMuJoCoEnv-v0", "walker2d_mujoco", "walker2d.xml", "torso", action_dim=6, obs_dim=17,
                kind=KIND_MUJOCO_PLANAR, power=0.40, alive=ALIVE_MJ_WALKER,
                power_coef={"foot_joint": 30.0, "foot_left_joint": 30.0}, power_cost=-1e-3, qvel_clip=10.0))
-_add(RobotSpec("HalfCheetahMuJoCoEnv-v0", "halfcheetah_mujoco", "half_cheetah.xml", "torso", action_dim=6,
+_add(RobotSpec(11, "HalfCheetahMuJoCo",
+               "HalfCheetahMuJoCoEnv-v0", "halfcheetah_mujoco", "half_cheetah.xml", "torso", action_dim=6,
                obs_dim=17, kind=KIND_MUJOCO_PLANAR, power=1.0, alive=ALIVE_MJ_CHEETAH,
                power_coef={"bthigh": 120.0, "bshin": 90.0, "bfoot": 60.0, "fthigh": 140.0,
                            "fshin": 60.0, "ffoot": 30.0}, power_cost=-0.1, qvel_clip=0.0,
@@ -160,11 +175,13 @@ _add(RobotSpec("HalfCheetahMuJoCoEnv-v0", "halfcheetah_mujoco", "half_cheetah.xm
 # MuJoCo-observation floating-base walkers: obs [qpos[2:], qvel, zeros] (float64 in the
 # reference), reward alive(state[0] + initial_z) + progress + joints_at_limit (no electricity);
 # mujoco robot_locomotors.py:210-319, gym_locomotion_envs.py:39-118,243-260, envs/__init__.py:134-152
-_add(RobotSpec("AntMuJoCoEnv-v0", "ant_mujoco", "ant.xml", "torso", action_dim=8, obs_dim=111,
+_add(RobotSpec(12, "AntMuJoCo",
+               "AntMuJoCoEnv-v0", "ant_mujoco", "ant.xml", "torso", action_dim=8, obs_dim=111,
                kind=KIND_MUJOCO_3D, power=2.5,
                foot_list=["front_left_foot", "front_right_foot", "left_back_foot", "right_back_foot"],
                alive=ALIVE_ANT))
-_add(RobotSpec("HumanoidMuJoCoEnv-v0", "humanoid_mujoco", "humanoid_symmetric.xml", "torso", action_dim=17,
+_add(RobotSpec(13, "HumanoidMuJoCo",
+               "HumanoidMuJoCoEnv-v0", "humanoid_mujoco", "humanoid_symmetric.xml", "torso", action_dim=17,
                obs_dim=376, kind=KIND_MUJOCO_3D, power=0.41, foot_list=["right_foot", "left_foot"],
                alive=ALIVE_HUMANOID, motor_order=SPECS["humanoid"].motor_order,
                power_coef=dict(SPECS["humanoid"].power_coef), initial_z=0.8))
@@ -174,7 +191,8 @@ _add(RobotSpec("HumanoidMuJoCoEnv-v0", "humanoid_mujoco", "humanoid_symmetric.xm
 # envs/__init__.py:93-97.  The env's `self.electricity_cost /= 4` (:172) runs before
 # HumanoidBulletEnv.__init__ sets electricity_cost = 4.25 * -2.0 (:150), which overwrites it: the
 # Humanoid's costs stand (pinned by tests/golden/pack_humanoid_flagrun_harder.npz).
-_add(RobotSpec("HumanoidFlagrunHarderPyBulletEnv-v0", "humanoid_flagrun_harder", "humanoid_symmetric.xml", "torso",
+_add(RobotSpec(15, "HumanoidFlagrunHarder",
+               "HumanoidFlagrunHarderPyBulletEnv-v0", "humanoid_flagrun_harder", "humanoid_symmetric.xml", "torso",
                action_dim=17, obs_dim=44, kind=KIND_WALKER, power=0.41, foot_list=["right_foot", "left_foot"],
                alive=ALIVE_HUMANOID, motor_order=SPECS["humanoid"].motor_order,
                power_coef=dict(SPECS["humanoid"].power_coef), initial_z=0.8,
@@ -184,13 +202,19 @@ _add(RobotSpec("HumanoidFlagrunHarderPyBulletEnv-v0", "humanoid_flagrun_harder",
 # power 2.9, robot_specific_reset -> reset_pose([0, 0, 0 + 1.0], yaw 0: random_yaw False),
 # initial_z 1.5, alive_bonus from the head height and the knees), gym_locomotion_envs.py:181-191
 # (StadiumScene timestep 0.0165/8, frame_skip 8), envs/__init__.py:99-103
-_add(RobotSpec("AtlasPyBulletEnv-v0", "atlas", "", "pelvis", action_dim=30, obs_dim=70, kind=KIND_WALKER,
+_add(RobotSpec(16, "Atlas",
+               "AtlasPyBulletEnv-v0", "atlas", "", "pelvis", action_dim=30, obs_dim=70, kind=KIND_WALKER,
                power=2.9, foot_list=["r_foot", "l_foot"], alive=ALIVE_ATLAS, initial_z=1.5,
                timestep=0.0165 / 8, frame_skip=8, self_collision=False,
                urdf="atlas/atlas_description/atlas_v4_with_multisense.urdf", base_pos=[0.0, 0.0, 1.0],
                head="head", knees=["l_leg_kny", "r_leg_kny"]))
 
 ENV_IDS = {s.env_id: s for s in SPECS.values()}
+# The one robot registry: the specs in robot_id order.  The generated header's robot table, the
+# bindings' id maps and the package's ENV_IDS all derive from it; SPECS keeps its insertion order (the
+# flagrun variants copy the Humanoid's spec), so iterate BY_ID wherever the order must be the id order.
+BY_ID: List[RobotSpec] = sorted(SPECS.values(), key=lambda s: s.robot_id)
+assert [s.robot_id for s in BY_ID] == list(range(len(BY_ID))), "robot ids must be 0..N-1 without gaps"
 
 
 def spec_for(name: str) -> RobotSpec:
