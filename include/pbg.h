@@ -455,6 +455,73 @@ int pbg_population_set_obs_norm(pbg_population* p, const float* mean, const floa
 int pbg_policy_attach_obs_stats(pbg_policy* p, pbg_obs_stats* s);
 int pbg_population_attach_obs_stats(pbg_population* p, pbg_obs_stats* s);
 
+/* ---- Stochastic Gaussian actions and advantage estimation (appended; nothing above changes) ----
+ * A policy-gradient learner needs a = mu(obs) + std eps inside the rollout, the noise's squared norm for the
+ * log-probability, and advantages from the reward / done trajectories.  A pbg_action_noise lives on one
+ * device and holds act_dim, a uint64 seed, a DEVICE float32 std[act_dim] (initially zero), a DEVICE uint32
+ * step counter (initially zero) and a nullable DEVICE pointer eps2_traj, float64 [T, n].
+ *
+ * Contract.  While one is attached to an actor (below), step s = 0 .. T - 1 of a pbg_rollout /
+ * pbg_rollout_population call computes, for env e (row of the handle, whose global index is the handle's
+ * env_offset + e) and component j,
+ *   eps[e][j] : component j % 4 of the Noise contract's block (Philox4x32-10, key = seed, two Box-Muller
+ *               pairs) at counter = (j / 4, env_offset + e, counter + s, 0xAC)
+ *   a[e][j]   = (float)((double)mu[e][j] + (double)std[j] * (double)eps[e][j])
+ *   eps2[e]   = sum over j ascending, sequential float64 adds, of (double)eps[e][j] * (double)eps[e][j]
+ * mu is the third layer's output, exactly what the actor computes with nothing attached; a is what goes to
+ * act, to act_traj and into the step; eps2[e] goes to eps2_traj[s][e] when that pointer is set.  The product
+ * of two float32 values is exact in float64, so a and every partial sum are one rounding each (the same bits
+ * contracted into an fma or not).  A NaN mu gives a NaN action, which the step turns into done.  std is not
+ * validated (it lives on the device).  The fourth counter word 0xAC keeps the stream apart from the
+ * evolution strategy's 0xE5; the device function is the one the populations' noise uses.
+ * The step counter is read on the device by every actor launch, which adds its own s (a launch argument);
+ * the call's closing bookkeeping launch adds T to it.  A rollout therefore stays 2 T + 1 launches with no
+ * host work, and a captured graph draws fresh noise on every replay.  The noise depends on (seed, global
+ * env index, step count, component) only: not on the batch or shard the env sits in, on the tile geometry,
+ * or on whether the actor is a policy or a population.  obs_traj and attached statistics are unaffected;
+ * the plain *_act calls never sample. */
+typedef struct pbg_action_noise pbg_action_noise;
+
+/* PBG_E_ARG (before any HIP call) for act_dim outside pbg_policy_create's 1..64, device < 0 or out NULL;
+ * PBG_E_HIP for a device that does not exist.  *out is NULL after every failure. */
+int pbg_action_noise_create(int device, int act_dim, uint64_t seed, pbg_action_noise** out);
+/* Detach it from every actor first (pbg_*_attach_action_noise with NULL): the actors keep only the pointer. */
+void pbg_action_noise_destroy(pbg_action_noise* z);
+/* std: DEVICE float32 [act_dim], copied on `stream` (no host work: a training loop sets it every iteration). */
+int pbg_action_noise_set_std(pbg_action_noise* z, const float* std, void* stream);
+/* The step counter: set on `stream`; get copies it into a DEVICE uint32 on `stream`. */
+int pbg_action_noise_set_counter(pbg_action_noise* z, uint32_t counter, void* stream);
+int pbg_action_noise_get_counter(const pbg_action_noise* z, uint32_t* counter_out, void* stream);
+/* Host-side: where the next rollouts write eps2 (DEVICE float64 [T, n] of that rollout; NULL: nowhere). */
+int pbg_action_noise_set_eps2_traj(pbg_action_noise* z, double* eps2_traj);
+/* eps_out (DEVICE [n, act_dim] float32) = the eps of envs env_offset .. env_offset + n at the absolute step
+ * count `step` (the counter plus s of the rollout step it mirrors): one launch of the same device function. */
+int pbg_action_noise_fill(const pbg_action_noise* z, int n, int env_offset, uint32_t step, float* eps_out, void* stream);
+/* The host counterpart (float64, rounded once; HOST eps_out [n, act_dim]); needs no GPU.  Host and device
+ * agree within the Noise contract's 1e-5 absolute, not bitwise. */
+int pbg_action_noise_host(int act_dim, uint64_t seed, int n, int env_offset, uint32_t step, float* eps_out);
+/* Attach the noise to an actor (NULL detaches).  The rollout returns PBG_E_ARG for an attached object on
+ * another device or with another act_dim. */
+int pbg_policy_attach_action_noise(pbg_policy* p, pbg_action_noise* z);
+int pbg_population_attach_action_noise(pbg_population* p, pbg_action_noise* z);
+
+/* Generalised advantage estimation (Schulman et al. 2016) as one launch, a lane per env, t descending from
+ * T - 1, all DEVICE arrays: rew_traj float32 [T, n], done_traj uint8 [T, n], value float32 [T + 1, n] (row T:
+ * the value of the observation after the last step), adv_out, ret_out float32 [T, n].  All arithmetic is
+ * float64, nothing contracted, in this order (A = 0 before t = T - 1; gl = gamma * lambda, computed once on
+ * the host):
+ *   nd    = done[t][e] ? 0.0 : 1.0
+ *   delta = (r + (gamma * v[t+1]) * nd) - v[t]
+ *   A     = delta + (gl * nd) * A
+ *   adv[t][e] = (float)A;  ret[t][e] = (float)(A + v[t])
+ * done includes the TimeLimit truncation (the trajectories carry no separate flag): a truncated episode is
+ * treated as terminal, nothing bootstraps through it.  PBG_E_ARG (before any HIP call) for T < 1, n < 1 or
+ * a NULL array.  pbg_gae_host: the same loop on HOST pointers, the same bits; needs no GPU. */
+int pbg_gae(int T, int n, const float* rew_traj, const uint8_t* done_traj, const float* value, double gamma,
+            double lambda, float* adv_out, float* ret_out, void* stream);
+int pbg_gae_host(int T, int n, const float* rew_traj, const uint8_t* done_traj, const float* value, double gamma,
+                 double lambda, float* adv_out, float* ret_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,6 +26,12 @@ def __getattr__(name):
     if name == "EvolutionStrategy":
         from .es import EvolutionStrategy
         return EvolutionStrategy
+    if name == "ActionNoise":
+        from .policy import ActionNoise
+        return ActionNoise
+    if name == "PPO":
+        from .ppo import PPO
+        return PPO
     if name in ("make", "register_with_gym"):
         from . import envs
         return getattr(envs, name)

@@ -157,6 +157,24 @@ def lib():
         for f in OBS_NORM_EXPORTED:
             if f != "pbg_obs_stats_destroy":
                 getattr(L, f).restype = I
+    if hasattr(L, "pbg_action_noise_create"):  # stochastic actions and advantage estimation
+        U64, U32, D = ctypes.c_uint64, ctypes.c_uint32, ctypes.c_double
+        L.pbg_action_noise_create.argtypes = [I, I, U64, ctypes.POINTER(H)]
+        L.pbg_action_noise_destroy.argtypes = [H]
+        L.pbg_action_noise_destroy.restype = None
+        L.pbg_action_noise_set_std.argtypes = [H, P, P]
+        L.pbg_action_noise_set_counter.argtypes = [H, U32, P]
+        L.pbg_action_noise_get_counter.argtypes = [H, P, P]
+        L.pbg_action_noise_set_eps2_traj.argtypes = [H, P]
+        L.pbg_action_noise_fill.argtypes = [H, I, I, U32, P, P]
+        L.pbg_action_noise_host.argtypes = [I, U64, I, I, U32, P]
+        L.pbg_policy_attach_action_noise.argtypes = [H, H]
+        L.pbg_population_attach_action_noise.argtypes = [H, H]
+        L.pbg_gae.argtypes = [I, I, P, P, P, D, D, P, P, P]
+        L.pbg_gae_host.argtypes = [I, I, P, P, P, D, D, P, P]
+        for f in ACTION_NOISE_EXPORTED:
+            if f != "pbg_action_noise_destroy":
+                getattr(L, f).restype = I
     for f in ("pbg_info", "pbg_reset", "pbg_step", "pbg_step_ex", "pbg_get_state", "pbg_set_state",
               "pbg_pack_record_sizes", "pbg_pack", "pbg_create_debug", "pbg_sample_actions", "pbg_create_ex",
               "pbg_default_sim_params", "pbg_get_sim_params", "pbg_create_v2", "pbg_precision"):
@@ -173,11 +191,16 @@ POPULATION_EXPORTED = ("pbg_population_create", "pbg_population_destroy", "pbg_p
 OBS_NORM_EXPORTED = ("pbg_obs_stats_create", "pbg_obs_stats_destroy", "pbg_obs_stats_update", "pbg_obs_stats_finalize",
                      "pbg_obs_stats_get_totals", "pbg_obs_stats_set_totals", "pbg_policy_set_obs_norm",
                      "pbg_population_set_obs_norm", "pbg_policy_attach_obs_stats", "pbg_population_attach_obs_stats")
+ACTION_NOISE_EXPORTED = ("pbg_action_noise_create", "pbg_action_noise_destroy", "pbg_action_noise_set_std",
+                         "pbg_action_noise_set_counter", "pbg_action_noise_get_counter", "pbg_action_noise_set_eps2_traj",
+                         "pbg_action_noise_fill", "pbg_action_noise_host", "pbg_policy_attach_action_noise",
+                         "pbg_population_attach_action_noise", "pbg_gae", "pbg_gae_host")
 EXPORTED = ("pbg_create", "pbg_create_debug", "pbg_create_ex", "pbg_create_v2", "pbg_precision",
             "pbg_default_sim_params", "pbg_get_sim_params",
             "pbg_destroy", "pbg_info", "pbg_reset", "pbg_step", "pbg_step_ex",
             "pbg_get_state", "pbg_set_state", "pbg_pack_record_sizes", "pbg_pack", "pbg_sample_actions",
-            "pbg_debug_poison", "pbg_last_error") + POLICY_EXPORTED + POPULATION_EXPORTED + OBS_NORM_EXPORTED
+            "pbg_debug_poison", "pbg_last_error") + POLICY_EXPORTED + POPULATION_EXPORTED + OBS_NORM_EXPORTED + \
+    ACTION_NOISE_EXPORTED
 
 
 def check(rc: int, what: str):

@@ -157,6 +157,7 @@ DevBufs dev_bufs(pbg_handle* h) {
 namespace pbg {
 int capi_fail(int code, const char* msg) { return fail(code, "%s", msg); }
 int handle_device(const pbg_handle* h) { return h->device; }
+int handle_env_offset(const pbg_handle* h) { return h->B.env_offset; }
 }  // namespace pbg
 
 extern "C" {

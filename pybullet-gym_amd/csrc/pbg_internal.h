@@ -11,6 +11,8 @@ namespace pbg {
 int capi_fail(int code, const char* msg);
 // The GPU a handle lives on.
 int handle_device(const pbg_handle* h);
+// The global index of its env 0 (pbg_create's env_offset).
+int handle_env_offset(const pbg_handle* h);
 
 // Make `dev` the current device for a scope and put the caller's back afterwards.
 struct DeviceGuard {

@@ -21,9 +21,12 @@ using pbg::DeviceGuard;
 
 namespace {
 
-__global__ __launch_bounds__(256) void book_kernel(Book b, int n) {
+// the call's closing launch; BUMP: lane 0 also adds the call's T steps to the attached noise's step counter
+template <bool BUMP>
+__global__ __launch_bounds__(256) void book_kernel(Book b, int n, uint32_t* counter, uint32_t steps) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e < n) book_env(b, e);
+  if (BUMP && e == 0) *counter += steps;
 }
 
 // act[n, act_dim] = pi_m(obs[n, obs_dim]), n = n_members G rows: grid = n_members * tpm workgroups, workgroup
@@ -32,16 +35,18 @@ __global__ __launch_bounds__(256) void book_kernel(Book b, int n) {
 // trajectories; the bookkeeping of the previous env step (bk.rew64 != NULL) for the tile's envs comes first.
 // nm: the actor's normaliser (mean NULL: none); st: slot 0 of the statistics to collect into (sum NULL:
 // none), workgroup b adds to slot b; MODE (pbg_policy_dev.h) says which of the two the instantiation looks at.
-template <int MODE>
+// nz: the launch's action noise, which only a SAMPLE instantiation looks at (the last argument, so that the
+// others read theirs where they did before it existed).
+template <int MODE, bool SAMPLE>
 __global__ __launch_bounds__(PB) void actor_kernel(const float* __restrict__ params, int obs_dim, int h1, int h2, int act_dim,
                                                    int D, int G, int tpm, Norm nm, Slot st, const float* __restrict__ obs,
                                                    float* __restrict__ act, float* __restrict__ obs_traj,
-                                                   float* __restrict__ act_traj, Book bk) {
+                                                   float* __restrict__ act_traj, Book bk, Noise nz) {
   __shared__ __attribute__((aligned(16))) float bufA[PD * PT];
   __shared__ __attribute__((aligned(16))) float bufB[PD * PT];
   const Tile t = tile_of(blockIdx.x, G, tpm);
-  act_tile<MODE>(weights_at(params + (size_t)t.m * D, obs_dim, h1, h2, act_dim), nm, slot_at(st, obs_dim, blockIdx.x), t.row0,
-                 t.rows, obs, act, obs_traj, act_traj, bk, bufA, bufB);
+  act_tile<MODE, SAMPLE>(weights_at(params + (size_t)t.m * D, obs_dim, h1, h2, act_dim), nm, slot_at(st, obs_dim, blockIdx.x), nz,
+                         t.row0, t.rows, obs, act, obs_traj, act_traj, bk, bufA, bufB);
 }
 
 // the actor's normaliser with its arrays at `base` (the device's, or a policy's host copy)
@@ -72,23 +77,27 @@ struct pbg_policy {
 };
 
 int pbg::policy::launch_actor(const Actor& a, int n, const float* obs, float* act, float* obs_traj, float* act_traj,
-                              const Book& bk, bool collect, hipStream_t stream) {
+                              const Book& bk, bool collect, const Noise& nz, hipStream_t stream) {
   const int G = n / a.n_members;  // the callers have checked n % n_members == 0 and n > 0
   const Norm nm = norm_of(a, a.norm);
   const Slot st = collect && a.stats ? a.stats->slot0() : Slot{nullptr, nullptr, nullptr};
-  decltype(&actor_kernel<PLAIN>) kernel = nullptr;
-  switch (mode_of(nm, st)) {
-    case PLAIN: kernel = actor_kernel<PLAIN>; break;
-    case NORM: kernel = actor_kernel<NORM>; break;
-    case COLLECT: kernel = actor_kernel<COLLECT>; break;
+  decltype(&actor_kernel<PLAIN, false>) kernel = nullptr;
+  switch (2 * mode_of(nm, st) + (nz.std ? 1 : 0)) {
+    case 2 * PLAIN: kernel = actor_kernel<PLAIN, false>; break;
+    case 2 * NORM: kernel = actor_kernel<NORM, false>; break;
+    case 2 * COLLECT: kernel = actor_kernel<COLLECT, false>; break;
+    case 2 * PLAIN + 1: kernel = actor_kernel<PLAIN, true>; break;
+    case 2 * NORM + 1: kernel = actor_kernel<NORM, true>; break;
+    case 2 * COLLECT + 1: kernel = actor_kernel<COLLECT, true>; break;
   }
   hipLaunchKernelGGL(kernel, dim3((unsigned)tiles_of(n, G)), dim3(PB), 0, stream, a.params, a.obs_dim, a.h1, a.h2, a.act_dim, a.D,
-                     G, (G + PT - 1) / PT, nm, st, obs, act, obs_traj, act_traj, bk);
+                     G, (G + PT - 1) / PT, nm, st, obs, act, obs_traj, act_traj, bk, nz);
   return (int)hipGetLastError();
 }
 
 int pbg::policy::actor_init(const char* who, Actor& a, int device, int obs_dim, int h1, int h2, int act_dim, int n_members) {
-  a = Actor{device, obs_dim, h1, h2, act_dim, n_members, param_count(obs_dim, h1, h2, act_dim), nullptr, nullptr, 0.f, 0, nullptr};
+  a = Actor{device, obs_dim, h1, h2, act_dim, n_members, param_count(obs_dim, h1, h2, act_dim), nullptr, nullptr, 0.f, 0, nullptr,
+            nullptr};
   if (device < 0) return PBG_OK;
   if (const int rc = check_device(who, device)) return rc;
   DeviceGuard dg(device);
@@ -202,6 +211,12 @@ int pbg_policy_attach_obs_stats(pbg_policy* p, pbg_obs_stats* s) {
   return PBG_OK;
 }
 
+int pbg_policy_attach_action_noise(pbg_policy* p, pbg_action_noise* z) {
+  if (!p) return pbg::capi_fail(PBG_E_ARG, "pbg_policy_attach_action_noise: policy is NULL");
+  p->a.noise = z;
+  return PBG_OK;
+}
+
 int pbg_policy_act_host(const pbg_policy* p, int n, const float* obs, float* act) {
   if (!p || n < 0 || (n > 0 && (!obs || !act))) return pbg::capi_fail(PBG_E_ARG, "pbg_policy_act_host: bad arguments");
   const Weights P = weights_at(p->host, p->a.obs_dim, p->a.h1, p->a.h2, p->a.act_dim);
@@ -229,7 +244,7 @@ int pbg_policy_act(const pbg_policy* p, int n, const float* obs, float* act, voi
   DeviceGuard dg(p->a.device);
   Book none;
   memset(&none, 0, sizeof(none));
-  const int e = launch_actor(p->a, n, obs, act, nullptr, nullptr, none, false, (hipStream_t)stream);
+  const int e = launch_actor(p->a, n, obs, act, nullptr, nullptr, none, false, Noise{}, (hipStream_t)stream);
   return e ? hip_fail(e, "actor_kernel launch") : PBG_OK;
 }
 
@@ -280,6 +295,11 @@ int pbg::policy::rollout_loop(const char* who, pbg_handle* h, const pbg_rollout_
       return pbg::capi_fail(PBG_E_ARG, msg);
     }
   }
+  if (a.noise && (a.noise->device != dev || a.noise->act_dim != a.act_dim)) {
+    snprintf(msg, sizeof(msg), "%s: the attached action noise (device %d, act_dim %d) does not fit device %d and act_dim %d", who,
+             a.noise->device, a.noise->act_dim, dev, a.act_dim);
+    return pbg::capi_fail(PBG_E_ARG, msg);
+  }
   if (io->n_steps < 1) {
     snprintf(msg, sizeof(msg), "%s: n_steps must be >= 1", who);
     return pbg::capi_fail(PBG_E_ARG, msg);
@@ -301,10 +321,18 @@ int pbg::policy::rollout_loop(const char* who, pbg_handle* h, const pbg_rollout_
   st.obs = io->obs;
   st.rew64 = io->rew64;
   st.autoreset = io->autoreset ? 1 : 0;
+  Noise nz{};
+  if (a.noise)
+    nz = Noise{a.noise->std, a.noise->counter, nullptr, (uint32_t)a.noise->seed, (uint32_t)(a.noise->seed >> 32),
+               (uint32_t)pbg::handle_env_offset(h), 0u};
   for (int t = 0; t < io->n_steps; t++) {
+    if (a.noise) {
+      nz.step = (uint32_t)t;
+      nz.eps2 = a.noise->eps2_traj ? a.noise->eps2_traj + (size_t)t * n : nullptr;
+    }
     // actor: the bookkeeping of step t - 1, then act = pi(obs)
     int e = launch_actor(a, n, io->obs, io->act, io->obs_traj ? io->obs_traj + (size_t)t * no : nullptr,
-                         io->act_traj ? io->act_traj + (size_t)t * na : nullptr, bk, a.stats != nullptr, s);
+                         io->act_traj ? io->act_traj + (size_t)t * na : nullptr, bk, a.stats != nullptr, nz, s);
     if (e) return hip_fail(e, "actor kernel launch");
     // the step writes reward and done straight into the trajectory rows when there are any
     st.rew = io->rew_traj ? io->rew_traj + (size_t)t * n : io->rew;
@@ -314,7 +342,11 @@ int pbg::policy::rollout_loop(const char* who, pbg_handle* h, const pbg_rollout_
     bk.rew64 = io->rew64;
     bk.done = st.done;
   }
-  hipLaunchKernelGGL(book_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, bk, n);
+  const dim3 bgrid((unsigned)((n + 255) / 256));
+  if (a.noise)
+    hipLaunchKernelGGL(book_kernel<true>, bgrid, dim3(256), 0, s, bk, n, a.noise->counter, (uint32_t)io->n_steps);
+  else
+    hipLaunchKernelGGL(book_kernel<false>, bgrid, dim3(256), 0, s, bk, n, (uint32_t*)nullptr, 0u);
   const int e = (int)hipGetLastError();
   return e ? hip_fail(e, "rollout bookkeeping launch") : PBG_OK;
 }

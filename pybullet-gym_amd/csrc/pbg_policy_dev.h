@@ -1,5 +1,5 @@
-// pbg_policy_dev.h -- what the actor translation units (pbg_policy.hip, pbg_population.hip, pbg_obsnorm.hip)
-// share: the description of an actor (Actor: a pbg_policy is one with a single member whose group is the
+// pbg_policy_dev.h -- what the actor translation units (pbg_policy.hip, pbg_population.hip, pbg_obsnorm.hip,
+// pbg_actnoise.hip) share: the description of an actor (Actor: a pbg_policy is one with a single member whose group is the
 // whole batch, a pbg_population one with 2 n_pairs), the MLP tile that pbg_policy.hip's actor_kernel
 // evaluates with the workgroup's member's weights, the rollout bookkeeping, the one actor launch and the
 // rollout loop (pbg_rollout and pbg_rollout_population are the same 2 T + 1 launches), and the host helpers
@@ -25,6 +25,7 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include "pbg_es_noise.h"
 #include "pbg_internal.h"
 
 namespace pbg {
@@ -125,6 +126,18 @@ struct Actor {
   float clip;
   int norm_on;
   pbg_obs_stats* stats;  // attached (pbg_*_attach_obs_stats), not owned
+  pbg_action_noise* noise;  // attached (pbg_*_attach_action_noise), not owned
+};
+
+// The action noise of one actor launch (pbg.h "Stochastic Gaussian actions"); std NULL = the launch does
+// not sample.  The lanes read the object's device step counter and add `step`, the launch's own.
+struct Noise {
+  const float* std;         // device [act_dim]
+  const uint32_t* counter;  // device: the steps sampled before this rollout call
+  double* eps2;             // device [n]: this step's row of eps2_traj, nullable
+  uint32_t k0, k1;          // the seed
+  uint32_t env_offset;      // global index of the launch's row 0
+  uint32_t step;            // s, the step inside the call
 };
 
 // slot b of the object whose slot 0 is `base` (K = obs_dim)
@@ -258,8 +271,21 @@ enum Mode { PLAIN = 0, NORM = 1, COLLECT = 2 };
 
 inline Mode mode_of(const Norm& nm, const Slot& st) { return st.sum ? COLLECT : (nm.mean ? NORM : PLAIN); }
 
-template <int MODE>
-__device__ __forceinline__ void act_tile(const Weights P, const Norm nm, const Slot st, int env0, int rows,
+// The four normals of action components 4 b .. 4 b + 3 of the global env `env` at step count `step`: the
+// one spelling the sampling actor and pbg_actnoise.hip's fill kernel share (pbg.h's same-bits rule).
+__device__ __forceinline__ void action_normals4(uint32_t k0, uint32_t k1, uint32_t b, uint32_t env, uint32_t step,
+                                                float z[4]) {
+  pbg::es::es_normals4(k0, k1, b, env, step, pbg::es::ACTION_TAG, z);
+}
+
+// SAMPLE (a rollout step with action noise attached, nz.std != NULL): after the third layer mu sits transposed
+// in bufB and bufA is idle.  Lane (e = tid % PT, b = tid / PT) draws the block of components 4 b .. 4 b + 3 of
+// row e into bufA [act_dim][PT]; after one more barrier lane e < rows sums its row's squares in ascending j and
+// the output loop adds std[j] eps to mu in float64.  PT rows x 16 blocks = PB lanes: one pass.
+static_assert((PB / PT) * 4 >= PBG_POLICY_MAX_ACT, "a lane per (row, block of 4 components)");
+
+template <int MODE, bool SAMPLE>
+__device__ __forceinline__ void act_tile(const Weights P, const Norm nm, const Slot st, const Noise nz, int env0, int rows,
                                          const float* __restrict__ obs, float* __restrict__ act,
                                          float* __restrict__ obs_traj, float* __restrict__ act_traj, const Book bk,
                                          float* bufA, float* bufB) {
@@ -289,9 +315,29 @@ __device__ __forceinline__ void act_tile(const Weights P, const Norm nm, const S
   layer(P.w3, P.b3, P.h2, P.act_dim, false, bufA, bufB);
   __syncthreads();
   const int NA = P.act_dim;
+  if (SAMPLE) {
+    const int e = tid & (PT - 1), b = tid / PT;
+    if (e < rows && 4 * b < NA) {
+      float z[4];
+      action_normals4(nz.k0, nz.k1, (uint32_t)b, nz.env_offset + (uint32_t)(env0 + e), *nz.counter + nz.step, z);
+#pragma unroll
+      for (int t = 0; t < 4; t++)
+        if (4 * b + t < NA) bufA[(4 * b + t) * PT + e] = z[t];
+    }
+    __syncthreads();
+    if (nz.eps2 && tid < rows) {
+      double q = 0.0;
+      for (int j = 0; j < NA; j++) {
+        const double x = (double)bufA[j * PT + tid];
+        q += x * x;  // exact product: the same bits contracted or not
+      }
+      nz.eps2[env0 + tid] = q;
+    }
+  }
   for (int i = tid; i < rows * NA; i += PB) {
     const int e = i / NA, j = i - e * NA;
-    const float v = bufB[j * PT + e];
+    float v = bufB[j * PT + e];
+    if (SAMPLE) v = (float)((double)v + (double)nz.std[j] * (double)bufA[j * PT + e]);  // exact product, one rounding
     const size_t at = (size_t)env0 * NA + i;
     act[at] = v;
     if (act_traj) act_traj[at] = v;
@@ -315,14 +361,16 @@ __device__ __forceinline__ Tile tile_of(unsigned b, int G, int tpm) {
 // The one actor launch (pbg_policy.hip): act = pi_m(obs) for n rows (n > 0, a multiple of a.n_members) after
 // the bookkeeping `bk`, enqueued on `stream`; returns the hipError_t of the launch.
 // `collect`: accumulate the actor's attached statistics (rollout steps only; the loop has validated them).
+// `nz`: the launch's action noise (rollout steps only; std NULL, a Noise{}: none).
 int launch_actor(const Actor& a, int n, const float* obs, float* act, float* obs_traj, float* act_traj, const Book& bk,
-                 bool collect, hipStream_t stream);
+                 bool collect, const Noise& nz, hipStream_t stream);
 
 // The closed loop of pbg_rollout / pbg_rollout_population (pbg_policy.hip): validates `io` against the
 // handle and the actor's device and dims (the handle's n_envs a multiple of the actor's members; attached
-// statistics on the actor's device, of its obs_dim and with a slot per workgroup), then enqueues per step the
-// actor and the handle's step, and one closing bookkeeping launch.  `who` names the entry point in error
-// messages.
+// statistics on the actor's device, of its obs_dim and with a slot per workgroup; attached action noise on the
+// actor's device and of its act_dim), then enqueues per step the actor and the handle's step, and one closing
+// bookkeeping launch, which also advances the attached noise's step counter.  `who` names the entry point in
+// error messages.
 int rollout_loop(const char* who, pbg_handle* h, const pbg_rollout_io_t* io, void* stream, const Actor& a);
 
 // ---------------------------------------------------------------- host helpers of the three objects
@@ -375,4 +423,14 @@ struct pbg_obs_stats {
   int64_t* slot_count;
 
   pbg::policy::Slot slot0() const { return pbg::policy::Slot{slot_count, slot_sum, slot_sumsq}; }
+};
+
+// pbg.h pbg_action_noise: one device allocation, std [act_dim] float32 then the uint32 step counter
+// (pbg_actnoise.hip owns it; the rollout loop reads the pointers)
+struct pbg_action_noise {
+  int device, act_dim;
+  uint64_t seed;
+  float* std;
+  uint32_t* counter;
+  double* eps2_traj;  // device [T, n] of the next rollouts, nullable; not owned
 };

@@ -43,7 +43,7 @@ __global__ __launch_bounds__(256) void noise_kernel(int D, uint32_t k0, uint32_t
   const int b = blockIdx.y * 256 + threadIdx.x;
   if (4 * b >= D) return;
   float e[4];
-  es_normals4(k0, k1, (uint32_t)b, pair0 + (uint32_t)i, generation, e);
+  es_normals4(k0, k1, (uint32_t)b, pair0 + (uint32_t)i, generation, ES_TAG, e);
   float* out = eps + (size_t)i * D;
 #pragma unroll
   for (int t = 0; t < 4; t++)
@@ -59,7 +59,7 @@ __global__ __launch_bounds__(256) void perturb_kernel(int D, const float* __rest
   const int b = blockIdx.y * 256 + threadIdx.x;
   if (4 * b >= D) return;
   float e[4];
-  es_normals4(k0, k1, (uint32_t)b, pair0 + (uint32_t)i, generation, e);
+  es_normals4(k0, k1, (uint32_t)b, pair0 + (uint32_t)i, generation, ES_TAG, e);
   float* plus = members + (size_t)(2 * i) * D;
   float* minus = plus + D;
   const double s = (double)sigma;
@@ -83,7 +83,7 @@ __global__ __launch_bounds__(256) void grad_kernel(int D, int n_pairs, const flo
   double acc[4] = {0.0, 0.0, 0.0, 0.0};
   for (int i = 0; i < n_pairs; i++) {
     float e[4];
-    es_normals4(k0, k1, (uint32_t)b, pair0 + (uint32_t)i, generation, e);
+    es_normals4(k0, k1, (uint32_t)b, pair0 + (uint32_t)i, generation, ES_TAG, e);
     const double wi = (double)w[i];
 #pragma unroll
     for (int t = 0; t < 4; t++) acc[t] = __builtin_fma(wi, (double)e[t], acc[t]);
@@ -121,27 +121,6 @@ int launched(const char* what) {
 
 // the largest population whose member count and whose global pair indices stay inside an int
 bool pairs_ok(int n_pairs, int pair0) { return n_pairs >= 1 && n_pairs <= INT_MAX / 2 && pair0 >= 0 && pair0 <= INT_MAX - n_pairs; }
-
-void host_philox(uint32_t c[4], uint32_t k0, uint32_t k1) {
-  for (int r = 0; r < 10; r++) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n1 = (uint32_t)p1;
-    const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1, n3 = (uint32_t)p0;
-    c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-}
-
-// the noise contract in float64, rounded once
-void host_box_muller(uint32_t a, uint32_t b, float* n0, float* n1) {
-  const double u1 = (double)(a >> 9) * 0x1p-23 + 0x1p-24;
-  const double u2 = (double)(b >> 8) * 0x1p-24;
-  const double r = sqrt(-2.0 * log(u1));
-  const double ang = 2.0 * M_PI * u2;
-  *n0 = (float)(r * cos(ang));
-  *n1 = (float)(r * sin(ang));
-}
 
 dim3 pair_grid(const pbg_population* p) { return dim3((unsigned)p->n_pairs, (unsigned)(((p->a.D + 3) / 4 + 255) / 256)); }
 
@@ -199,6 +178,12 @@ int pbg_population_attach_obs_stats(pbg_population* p, pbg_obs_stats* s) {
   return PBG_OK;
 }
 
+int pbg_population_attach_action_noise(pbg_population* p, pbg_action_noise* z) {
+  if (!p) return pbg::capi_fail(PBG_E_ARG, "pbg_population_attach_action_noise: population is NULL");
+  p->a.noise = z;
+  return PBG_OK;
+}
+
 int pbg_population_noise_host(int obs_dim, int h1, int h2, int act_dim, uint64_t seed, uint32_t generation, int pair0,
                               int n_pairs, float* eps_out) {
   if (const int rc = check_dims("pbg_population_noise_host", obs_dim, h1, h2, act_dim)) return rc;
@@ -209,11 +194,8 @@ int pbg_population_noise_host(int obs_dim, int h1, int h2, int act_dim, uint64_t
   for (int i = 0; i < n_pairs; i++) {
     float* row = eps_out + (size_t)i * D;
     for (int b = 0; 4 * b < D; b++) {
-      uint32_t c[4] = {(uint32_t)b, (uint32_t)pair0 + (uint32_t)i, generation, ES_TAG};
-      host_philox(c, k0, k1);
       float e[4];
-      host_box_muller(c[0], c[1], &e[0], &e[1]);
-      host_box_muller(c[2], c[3], &e[2], &e[3]);
+      host_normals4(k0, k1, (uint32_t)b, (uint32_t)pair0 + (uint32_t)i, generation, ES_TAG, e);
       for (int t = 0; t < 4 && 4 * b + t < D; t++) row[4 * b + t] = e[t];
     }
   }
@@ -279,7 +261,7 @@ int pbg_population_act(const pbg_population* p, int n, const float* obs, float* 
   DeviceGuard dg(p->a.device);
   Book none;
   memset(&none, 0, sizeof(none));
-  const int e = launch_actor(p->a, n, obs, act, nullptr, nullptr, none, false, (hipStream_t)stream);
+  const int e = launch_actor(p->a, n, obs, act, nullptr, nullptr, none, false, Noise{}, (hipStream_t)stream);
   return e ? hip_fail(e, "actor_kernel launch") : PBG_OK;
 }
 

@@ -150,6 +150,79 @@ class ObsStats(_NativeObject):
         self._totals_src = t  # alive until the stream has copied it
 
 
+class ActionNoise(_NativeObject):
+    """Per-env Gaussian action noise on one GPU (include/pbg.h pbg_action_noise_*).  Attached to an actor
+    (``attach_action_noise``), every step of ``VecEnv.rollout`` with that actor acts ``a = mu(obs) + std * eps``
+    (float64 arithmetic, rounded once) inside the actor launch; ``act`` never samples.  ``eps`` is counter-based
+    (Philox4x32-10 keyed by ``seed``, counter = block of 4 components, global env index, step count, 0xAC), so
+    it depends on neither the batch, the shard nor the actor's kind, and ``fill`` regenerates the bits of any
+    step.  ``std`` starts at zero, the step ``counter`` at zero; the counter lives on the device and every
+    rollout call advances it by its steps, a graph replay included.  Everything is asynchronous on the current
+    stream."""
+    _DESTROY, _NOUN = "pbg_action_noise_destroy", "action noise"
+
+    def __init__(self, act_dim: int, seed: int = 0, device="cuda:0"):
+        self.act_dim, self.seed = int(act_dim), int(seed) & 0xFFFFFFFFFFFFFFFF
+        idx = self._set_device(device)
+        h = ctypes.c_void_p()
+        _native.check(_need("pbg_action_noise_create")(idx, self.act_dim, self.seed, ctypes.byref(h)),
+                      "pbg_action_noise_create")
+        self._h = h
+        self._eps2 = None  # the bound eps2_traj tensor (kept alive while bound)
+
+    def set_std(self, std):
+        """``std``: contiguous float32 ``[act_dim]`` on the device, copied on the current stream (not validated)."""
+        z = self._open("set_std")
+        std = self._vec(std, "set_std", "std", (self.act_dim,))
+        _native.check(_native.lib().pbg_action_noise_set_std(z, std.data_ptr(), self._stream()), "pbg_action_noise_set_std")
+
+    @property
+    def counter(self) -> int:
+        """Steps sampled so far (synchronises to read it); assignable, to resume a run."""
+        import torch
+        z = self._open("counter")
+        out = torch.zeros(1, dtype=torch.int32, device=self.device)
+        _native.check(_native.lib().pbg_action_noise_get_counter(z, out.data_ptr(), self._stream()),
+                      "pbg_action_noise_get_counter")
+        return int(out.item()) & 0xFFFFFFFF
+
+    @counter.setter
+    def counter(self, value):
+        z = self._open("counter")
+        _native.check(_native.lib().pbg_action_noise_set_counter(z, int(value) & 0xFFFFFFFF, self._stream()),
+                      "pbg_action_noise_set_counter")
+
+    def bind_eps2_traj(self, eps2_traj):
+        """Where the next rollouts write each step's ``sum_j eps[e][j] ** 2``: a contiguous float64 ``[T, n]``
+        device tensor for rollouts of T steps over n envs (None: nowhere).  ``VecEnv.rollout`` calls this."""
+        import torch
+        z = self._open("bind_eps2_traj")
+        if eps2_traj is not None:
+            shape = tuple(eps2_traj.shape) if isinstance(eps2_traj, torch.Tensor) and eps2_traj.dim() == 2 else (-1, -1)
+            self._vec(eps2_traj, "bind_eps2_traj", "eps2_traj", shape, torch.float64)
+        _native.check(_native.lib().pbg_action_noise_set_eps2_traj(z, None if eps2_traj is None else eps2_traj.data_ptr()),
+                      "pbg_action_noise_set_eps2_traj")
+        self._eps2 = eps2_traj
+
+    def fill(self, n: int, env_offset: int, step: int, out=None):
+        """``[n, act_dim]`` float32: the eps of global envs ``env_offset .. env_offset + n`` at the absolute step
+        count ``step`` (the counter before a rollout call plus the step inside it), the bits the actor adds."""
+        import torch
+        z = self._open("fill")
+        shape = (int(n), self.act_dim)
+        out = torch.empty(shape, dtype=torch.float32, device=self.device) if out is None else out
+        out = self._vec(out, "fill", "out", shape)
+        _native.check(_native.lib().pbg_action_noise_fill(z, int(n), int(env_offset), int(step) & 0xFFFFFFFF,
+                                                          out.data_ptr(), self._stream()), "pbg_action_noise_fill")
+        return out
+
+
+def _attach_action_noise(actor, fname, noise):
+    p = actor._open("attach_action_noise")
+    _native.check(_need(fname)(p, None if noise is None else noise._open("attach")), fname)
+    actor.action_noise = noise
+
+
 class MLPPolicy(_NativeObject):
     """obs -> h1 -> h2 -> act, ReLU on the hidden layers, float32.
 
@@ -162,6 +235,7 @@ class MLPPolicy(_NativeObject):
     _DESTROY, _NOUN = "pbg_policy_destroy", "policy"
     _ROLLOUT = "pbg_rollout"   # VecEnv.rollout's entry point for this actor
     n_members = 1              # one weight set for the whole batch
+    action_noise = None        # the attached ActionNoise, or None
 
     def __init__(self, w1, b1, w2, b2, w3, b3, device=None, obs_norm=None):
         ws = [np.ascontiguousarray(np.asarray(a), dtype=np.float32) for a in (w1, b1, w2, b2, w3, b3)]
@@ -222,6 +296,11 @@ class MLPPolicy(_NativeObject):
         _native.check(_need("pbg_policy_attach_obs_stats")(p, None if stats is None else stats._open("attach")),
                       "pbg_policy_attach_obs_stats")
         self.obs_stats = stats
+
+    def attach_action_noise(self, noise):
+        """While an ``ActionNoise`` is attached, every step of ``VecEnv.rollout`` with this policy acts
+        ``mu + std * eps`` (``act`` never samples); None detaches."""
+        _attach_action_noise(self, "pbg_policy_attach_action_noise", noise)
 
     def act(self, obs, out=None):
         """``[n, obs_dim]`` float32 observations -> ``[n, act_dim]`` actions.  Device policy: torch
@@ -292,6 +371,7 @@ class MLPPopulation(_NativeObject):
     allocates only the results it is not handed (``out=``), so a generation captures into a HIP graph."""
     _DESTROY, _NOUN = "pbg_population_destroy", "population"
     _ROLLOUT = "pbg_rollout_population"   # VecEnv.rollout's entry point for this actor
+    action_noise = None                   # the attached ActionNoise, or None
 
     def __init__(self, dims, n_pairs: int, device, pair0: int = 0):
         self.dims = tuple(int(d) for d in dims)
@@ -348,6 +428,11 @@ class MLPPopulation(_NativeObject):
         _native.check(_need("pbg_population_attach_obs_stats")(p, None if stats is None else stats._open("attach")),
                       "pbg_population_attach_obs_stats")
         self.obs_stats = stats
+
+    def attach_action_noise(self, noise):
+        """While an ``ActionNoise`` is attached, every step of ``VecEnv.rollout`` with this population acts
+        ``mu + std * eps``, the noise of an env depending on its global index only; None detaches."""
+        _attach_action_noise(self, "pbg_population_attach_action_noise", noise)
 
     # ------------------------------------------------------------------ parameters
     def init_theta(self, seed: int = 0):

@@ -1,0 +1,227 @@
+"""Proximal policy optimisation on the device (Schulman et al. 2017) and generalised advantage estimation
+(Schulman et al. 2016).
+
+The per-step path is HIP: ``VecEnv.rollout`` with an ``ActionNoise`` attached acts ``a = mu(obs) + std eps``
+inside the actor launch and records ``sum eps^2`` for the log-probability (include/pbg.h "Stochastic Gaussian
+actions"), the critic's values are one ``MLPPopulation.act`` over the whole trajectory, and ``gae`` is one
+launch (pbg_gae).  The backward pass is torch autograd on purpose: it runs K M times per iteration, not
+T times, and is plumbing here.  The collection half of an iteration has no host work between its launches."""
+from __future__ import annotations
+
+import ctypes
+import math
+from dataclasses import dataclass
+
+import numpy as np
+import torch
+
+from . import _native
+from .policy import ActionNoise, MLPPopulation, ObsStats
+
+
+def gae(rew_traj, done_traj, value, gamma: float = 0.99, lam: float = 0.95, adv=None, ret=None):
+    """``(adv, ret)``, float32 ``[T, n]``: pbg_gae, one launch, a lane per env, float64 arithmetic in the order
+    include/pbg.h states.  ``rew_traj`` float32 ``[T, n]``, ``done_traj`` uint8 ``[T, n]``, ``value`` float32
+    ``[T + 1, n]`` (row T: the value of the observation after the last step), contiguous tensors on one GPU.
+    ``done`` includes the TimeLimit truncation: a truncated episode is treated as terminal, nothing bootstraps
+    through it.  numpy arrays instead of tensors run the same loop on the host (pbg_gae_host, the same bits)."""
+    if not hasattr(_native.lib(), "pbg_gae"):
+        raise _native.PbgError(f"{_native.LIB_PATH} has no pbg_gae: a build without advantage estimation")
+    host = isinstance(rew_traj, np.ndarray)
+    if rew_traj.ndim != 2:
+        raise _native.PbgError(f"gae: rew_traj must be [T, n], got shape {tuple(rew_traj.shape)}")
+    T, n = (int(d) for d in rew_traj.shape)
+    f32, u8 = (np.float32, np.uint8) if host else (torch.float32, torch.uint8)
+    new = (lambda: np.empty((T, n), np.float32)) if host else \
+        (lambda: torch.empty((T, n), dtype=torch.float32, device=rew_traj.device))
+    adv = new() if adv is None else adv
+    ret = new() if ret is None else ret
+    for name, t, shape, dt in (("rew_traj", rew_traj, (T, n), f32), ("done_traj", done_traj, (T, n), u8),
+                               ("value", value, (T + 1, n), f32), ("adv", adv, (T, n), f32), ("ret", ret, (T, n), f32)):
+        ok = isinstance(t, np.ndarray) and t.flags.c_contiguous if host else \
+            isinstance(t, torch.Tensor) and t.is_contiguous() and t.device == rew_traj.device and t.is_cuda
+        if not ok or tuple(t.shape) != shape or t.dtype != dt or T < 1 or n < 1:
+            raise _native.PbgError(f"gae: {name} must be a contiguous {dt} {'array' if host else 'GPU tensor'} of shape "
+                                   f"{shape} (T, n >= 1), all on one device")
+    if host:
+        _native.check(_native.lib().pbg_gae_host(T, n, rew_traj.ctypes.data, done_traj.ctypes.data, value.ctypes.data,
+                                                 float(gamma), float(lam), adv.ctypes.data, ret.ctypes.data), "pbg_gae_host")
+        return adv, ret
+    with torch.cuda.device(rew_traj.device):
+        stream = ctypes.c_void_p(torch.cuda.current_stream(rew_traj.device).cuda_stream)
+        _native.check(_native.lib().pbg_gae(T, n, rew_traj.data_ptr(), done_traj.data_ptr(), value.data_ptr(), float(gamma),
+                                            float(lam), adv.data_ptr(), ret.data_ptr(), stream), "pbg_gae")
+    return adv, ret
+
+
+def mlp_forward(theta, dims, x, obs_norm=None):
+    """The MLP of the flat parameter vector ``theta`` (include/pbg.h "Flat parameter layout", ``unpack_theta``'s
+    slicing as views, so autograd reaches ``theta``) on ``x [B, obs_dim]``; ``obs_norm = (mean, inv_std, clip)``:
+    the actor's normaliser expression first."""
+    o, h1, h2, a = dims
+    if obs_norm is not None:
+        mean, inv_std, clip = obs_norm
+        x = torch.clamp((x - mean) * inv_std, -clip, clip)
+    at = 0
+    for k, h, relu in ((o, h1, True), (h1, h2, True), (h2, a, False)):
+        w = theta[at:at + k * h].view(k, h)
+        b = theta[at + k * h:at + k * h + h]
+        at += k * h + h
+        x = x @ w + b
+        if relu:
+            x = torch.relu(x)
+    return x
+
+
+@dataclass
+class Batch:
+    """One iteration's data (views of the env's rollout buffers and this object's own): ``[T, n, ...]``."""
+    obs: torch.Tensor
+    act: torch.Tensor
+    rew: torch.Tensor
+    done: torch.Tensor
+    eps2: torch.Tensor      # float64
+    logp: torch.Tensor      # float64, under the policy that acted
+    value: torch.Tensor     # [T + 1, n]
+    adv: torch.Tensor
+    ret: torch.Tensor
+
+
+class PPO:
+    """``env``: a ``VecEnv`` (auto-reset on, an even ``num_envs``).  The actor (obs -> h1 -> h2 -> act) and the
+    critic (obs -> h1 -> h2 -> 1) are two ``MLPPopulation``s of one pair each, given their weights by
+    ``set_all(theta)`` on the stream; ``actor_theta``, ``critic_theta`` (flat float32, section 11's layout) and
+    ``log_std`` are the torch parameters Adam moves.  ``iterate()`` is one iteration: rollout of ``steps`` env
+    steps with Gaussian action noise, values, GAE, then ``epochs`` x ``minibatches`` clipped-surrogate updates.
+    ``obs_norm=True``: running observation normalisation on section 12's schedule: statistics are attached
+    during the rollout and finalized into both networks' normaliser after the update, which uses the normaliser
+    its data was collected under."""
+
+    def __init__(self, env, hidden=(64, 64), steps: int = 64, seed: int = 0, gamma: float = 0.99, lam: float = 0.95,
+                 clip: float = 0.2, lr: float = 3e-4, epochs: int = 4, minibatches: int = 4, vf_coef: float = 0.5,
+                 ent_coef: float = 0.0, log_std: float = -0.5, max_grad_norm: float = 0.5, norm_adv: bool = True,
+                 obs_norm: bool = False, obs_clip: float = 5.0):
+        n, dev = env.num_envs, env.device
+        if n % 2 != 0 or not env.autoreset:
+            raise _native.PbgError("PPO: the env must have an even number of envs (the actors are populations of one "
+                                   "pair) and autoreset=True")
+        if int(steps) < 1 or int(epochs) < 1 or int(minibatches) < 1 or (int(steps) * n) % int(minibatches) != 0:
+            raise _native.PbgError("PPO: steps, epochs, minibatches must be >= 1 and steps * num_envs a multiple of minibatches")
+        self.env, self.steps, self.seed = env, int(steps), int(seed)
+        self.gamma, self.lam, self.clip, self.epochs, self.minibatches = float(gamma), float(lam), float(clip), int(epochs), \
+            int(minibatches)
+        self.vf_coef, self.ent_coef, self.max_grad_norm, self.norm_adv = float(vf_coef), float(ent_coef), max_grad_norm, norm_adv
+        obs_dim, act_dim = env.info.obs_dim, env.info.action_dim
+        self.actor_dims = (obs_dim, int(hidden[0]), int(hidden[1]), act_dim)
+        self.critic_dims = (obs_dim, int(hidden[0]), int(hidden[1]), 1)
+        self.actor = MLPPopulation(self.actor_dims, 1, dev)
+        self.critic = MLPPopulation(self.critic_dims, 1, dev)
+        self.noise = ActionNoise(act_dim, self.seed, dev)
+        self.actor.attach_action_noise(self.noise)
+        ta, tc = self.actor.init_theta(self.seed), self.critic.init_theta(self.seed + 1)
+        ta[-(self.actor_dims[2] * act_dim + act_dim):] *= 0.01   # a near-zero mean at the start: the noise explores
+        self.actor_theta = torch.nn.Parameter(ta)
+        self.critic_theta = torch.nn.Parameter(tc)
+        self.log_std = torch.nn.Parameter(torch.full((act_dim,), float(log_std), dtype=torch.float32, device=dev))
+        self.opt = torch.optim.Adam([self.actor_theta, self.critic_theta, self.log_std], lr=float(lr), eps=1e-5)
+        self._gen = torch.Generator(device=dev)
+        self._gen.manual_seed(self.seed)
+        self.iteration = 0
+        self.obs_stats, self.obs_clip = None, float(obs_clip)
+        if obs_norm:
+            self.obs_stats = ObsStats(obs_dim, n, group=n // 2, device=dev)
+            self._set_norm()  # the initial totals' normaliser
+        T = self.steps
+        kw = dict(dtype=torch.float32, device=dev)
+        self._value = torch.zeros((T + 1, n), **kw)
+        self._adv, self._ret = torch.zeros((T, n), **kw), torch.zeros((T, n), **kw)
+        self._obs_all = torch.zeros(((T + 1) * n, obs_dim), **kw)
+        self._std = torch.zeros(act_dim, **kw)
+        env.reset()
+
+    def _set_norm(self):
+        mean, inv_std = self.obs_stats.finalize()
+        self.actor.set_obs_norm(mean, inv_std, clip=self.obs_clip)
+        self.critic.set_obs_norm(mean, inv_std, clip=self.obs_clip)
+
+    def collect(self) -> Batch:
+        """The collection half of an iteration: both networks take their weights, the env runs ``steps`` noisy
+        steps, the critic values every visited observation and the last one, and ``gae`` turns them into
+        advantages.  A function of the seed and the parameters alone: it repeats bit for bit."""
+        env, T, n = self.env, self.steps, self.env.num_envs
+        self.actor.set_all(self.actor_theta.data)
+        self.critic.set_all(self.critic_theta.data)
+        torch.exp(self.log_std.data, out=self._std)
+        self.noise.set_std(self._std)
+        if self.obs_stats is not None:
+            self.actor.attach_obs_stats(self.obs_stats)
+        res = env.rollout(self.actor, T, trajectory=True)
+        if self.obs_stats is not None:
+            self.actor.attach_obs_stats(None)
+        self._obs_all[:T * n].copy_(res.obs_traj.view(T * n, -1))
+        self._obs_all[T * n:].copy_(env.obs)
+        self.critic.act(self._obs_all, out=self._value.view((T + 1) * n, 1))
+        gae(res.rew_traj, res.done_traj, self._value, self.gamma, self.lam, adv=self._adv, ret=self._ret)
+        return Batch(obs=res.obs_traj, act=res.act_traj, rew=res.rew_traj, done=res.done_traj, eps2=res.eps2_traj,
+                     logp=res.logp_traj(self._std), value=self._value, adv=self._adv, ret=self._ret)
+
+    def update(self, b: Batch) -> dict:
+        """``epochs`` passes of ``minibatches`` clipped-surrogate steps over the batch (torch autograd, Adam)."""
+        T, n = self.steps, self.env.num_envs
+        B, A = T * n, self.actor_dims[3]
+        obs, act = b.obs.reshape(B, -1), b.act.reshape(B, A)
+        logp_old, ret, adv = b.logp.reshape(B).float(), b.ret.reshape(B), b.adv.reshape(B)
+        norm = self.actor.obs_norm
+        stats = {}
+        for _ in range(self.epochs):
+            perm = torch.randperm(B, device=obs.device, generator=self._gen).view(self.minibatches, -1)
+            for idx in perm:
+                a_mb = adv[idx]
+                if self.norm_adv:
+                    a_mb = (a_mb - a_mb.mean()) / (a_mb.std() + 1e-8)
+                mu = mlp_forward(self.actor_theta, self.actor_dims, obs[idx], norm)
+                v = mlp_forward(self.critic_theta, self.critic_dims, obs[idx], norm).squeeze(1)
+                z = (act[idx] - mu) * torch.exp(-self.log_std)
+                logp = -0.5 * (z * z).sum(1) - self.log_std.sum() - 0.5 * A * math.log(2.0 * math.pi)
+                ratio = torch.exp(logp - logp_old[idx])
+                pg = -torch.min(ratio * a_mb, torch.clamp(ratio, 1.0 - self.clip, 1.0 + self.clip) * a_mb).mean()
+                vf = 0.5 * ((v - ret[idx]) ** 2).mean()
+                entropy = self.log_std.sum() + 0.5 * A * (1.0 + math.log(2.0 * math.pi))
+                loss = pg + self.vf_coef * vf - self.ent_coef * entropy
+                self.opt.zero_grad(set_to_none=True)
+                loss.backward()
+                if self.max_grad_norm:
+                    torch.nn.utils.clip_grad_norm_([self.actor_theta, self.critic_theta, self.log_std], self.max_grad_norm)
+                self.opt.step()
+                stats = dict(pg=pg.detach(), vf=vf.detach())
+        return stats
+
+    def iterate(self) -> dict:
+        b = self.collect()
+        stats = self.update(b)
+        if self.obs_stats is not None:
+            self._set_norm()
+        self.iteration += 1
+        return stats
+
+    def evaluate(self, env, steps: int, init_q=None):
+        """The noise-free mean policy on ``env`` (another ``VecEnv`` of the same robot, an even ``num_envs``):
+        per-env ``(returns float64 [n], lengths int32 [n])`` of a fresh ``steps``-step rollout (of the first
+        episode with ``autoreset=False``).  Moves neither the statistics nor the noise's counter."""
+        self.actor.set_all(self.actor_theta.data)
+        self.actor.attach_action_noise(None)
+        env.reset(init_q=init_q)
+        res = env.rollout(self.actor, steps, fresh=True)
+        self.actor.attach_action_noise(self.noise)
+        return res.done_return + res.cur_return, res.done_length + res.cur_length
+
+    def save_npz(self, path):
+        """The mean policy (and the normaliser in force, if any) under the reference's key names:
+        ``MLPPolicy.from_npz`` and tools/enjoy.py load it."""
+        self.actor.save_npz(path, self.actor_theta.data)
+
+    def close(self):
+        self.actor.attach_action_noise(None)
+        for o in (self.actor, self.critic, self.noise, self.obs_stats):
+            if o is not None:
+                o.close()

@@ -79,17 +79,28 @@ def es_noise(dims, seed: int, generation: int, pair0: int, n_pairs: int) -> np.n
     contract": Philox4x32-10, key = seed, counter = (block of 4 params, pair0 + i, generation, 0xE5), two
     Box-Muller pairs per block), computed in float64 and rounded once like pbg_population_noise_host.
     The device computes the same formula in float32: it agrees within 1e-5 absolute, not bitwise."""
-    D = es_param_count(dims)
-    nb = (D + 3) // 4
+    return _normal_rows(es_param_count(dims), seed, pair0, n_pairs, generation, 0xE5)
+
+
+def _normal_rows(width: int, seed: int, row0: int, n_rows: int, third: int, tag: int) -> np.ndarray:
+    """float32 [n_rows, width]: row i's block b of four normals from counter (b, row0 + i, third, tag)."""
+    nb = (width + 3) // 4
     key = (seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF)
-    B, I = np.meshgrid(np.arange(nb, dtype=np.uint32), np.arange(pair0, pair0 + n_pairs, dtype=np.uint32))
-    ctr = np.stack([B, I, np.full_like(B, generation & 0xFFFFFFFF), np.full_like(B, 0xE5)], axis=-1)
+    B, I = np.meshgrid(np.arange(nb, dtype=np.uint32), np.arange(row0, row0 + n_rows, dtype=np.uint32))
+    ctr = np.stack([B, I, np.full_like(B, third & 0xFFFFFFFF), np.full_like(B, tag)], axis=-1)
     x = philox4x32_10(ctr, key)
-    out = np.empty((n_pairs, nb, 4), dtype=np.float32)
+    out = np.empty((n_rows, nb, 4), dtype=np.float32)
     for h in (0, 1):
         u1 = (x[..., 2 * h] >> np.uint32(9)).astype(np.float64) * 2.0 ** -23 + 2.0 ** -24
         u2 = (x[..., 2 * h + 1] >> np.uint32(8)).astype(np.float64) * 2.0 ** -24
         r = np.sqrt(-2.0 * np.log(u1))
         out[..., 2 * h] = r * np.cos(2.0 * np.pi * u2)
         out[..., 2 * h + 1] = r * np.sin(2.0 * np.pi * u2)
-    return np.ascontiguousarray(out.reshape(n_pairs, 4 * nb)[:, :D])
+    return np.ascontiguousarray(out.reshape(n_rows, 4 * nb)[:, :width])
+
+
+def action_noise(act_dim: int, seed: int, n: int, env_offset: int, step: int) -> np.ndarray:
+    """float32 [n, act_dim]: the action noise of pbg_action_noise_fill (include/pbg.h "Stochastic Gaussian
+    actions": the Noise contract's block at counter = (block of 4 components, env_offset + e, step, 0xAC)),
+    computed in float64 and rounded once like pbg_action_noise_host.  The device agrees within 1e-5 absolute."""
+    return _normal_rows(int(act_dim), seed, int(env_offset), int(n), int(step), 0xAC)

@@ -52,6 +52,17 @@ class RolloutResult:
     act_traj: torch.Tensor = None   # [steps, n, action_dim]
     rew_traj: torch.Tensor = None   # [steps, n] float32
     done_traj: torch.Tensor = None  # [steps, n] uint8
+    eps2_traj: torch.Tensor = None  # [steps, n] float64: sum_j eps[e][j] ** 2 of each step's action noise
+
+    def logp_traj(self, std) -> torch.Tensor:
+        """``[steps, n]`` float64 log-probability of each recorded action under the diagonal Gaussian it was
+        drawn from, ``-0.5 eps2 - sum(log std) - 0.5 A log(2 pi)``; ``std``: the ``[A]`` tensor the attached
+        ``ActionNoise`` held during the rollout."""
+        if self.eps2_traj is None:
+            raise _native.PbgError("RolloutResult.logp_traj: the rollout recorded no eps2_traj (trajectory=True with an "
+                                   "ActionNoise attached)")
+        s = std.detach().to(device=self.eps2_traj.device, dtype=torch.float64)
+        return -0.5 * self.eps2_traj - torch.log(s).sum() - 0.5 * s.numel() * float(np.log(2.0 * np.pi))
 
 
 class VecEnv:
@@ -217,7 +228,9 @@ class VecEnv:
         ``reset_rollout()`` zeroes them.  With ``autoreset=False`` an env that has finished an
         episode stops accumulating, so ``done_return`` / ``done_length`` hold its first episode.
         ``trajectory=True`` also records ``obs_traj`` (the observation each action was computed
-        from), ``act_traj``, ``rew_traj`` and ``done_traj``, ``[steps, n, ...]``.
+        from), ``act_traj``, ``rew_traj`` and ``done_traj``, ``[steps, n, ...]``.  With an ``ActionNoise``
+        attached to the policy every action is ``mu + std * eps`` (what ``act_traj`` then records), and
+        ``trajectory=True`` also records ``eps2_traj`` (``RolloutResult.logp_traj``).
 
         All buffers are allocated once per ``(steps, trajectory)`` and reused, and the returned
         tensors are views of them (``clone()`` what must survive the next call), so after one
@@ -256,11 +269,18 @@ class VecEnv:
             self._ro_io[key] = (io, traj)
         io, traj = self._ro_io[key]
         io.autoreset = 1 if self.autoreset else 0
+        noise, eps2 = policy.action_noise, None
+        if noise is not None:  # the noise object, not the io struct, carries where eps2 goes (pbg.h)
+            if trajectory:
+                if "eps2_traj" not in traj:
+                    traj["eps2_traj"] = torch.zeros((steps, n), dtype=torch.float64, **kw)
+                eps2 = traj["eps2_traj"]
+            noise.bind_eps2_traj(eps2)
         _native.check(getattr(_native.lib(), policy._ROLLOUT)(self._h, policy._h, ctypes.byref(io),
                                                               _stream(self.device)), policy._ROLLOUT)
         return RolloutResult(obs=self.obs, **self._ro_acc, obs_traj=traj.get("obs_traj"),
                              act_traj=traj.get("act_traj"), rew_traj=traj.get("rew_traj"),
-                             done_traj=traj.get("done_traj"))
+                             done_traj=traj.get("done_traj"), eps2_traj=eps2)
 
     def reset_rollout(self):
         """Zero the rollout accumulators (stream-ordered, no allocation)."""

@@ -23,8 +23,14 @@ to the actor), written to profiles/obs_norm_rollout.json.  The normaliser is the
 1, a clip no observation reaches): the same three float32 operations per loaded element as any other, and
 all six legs stay in the same state bit for bit (asserted on the final observations).
 
+With --action-noise the rollout legs are A and B, each of them again with an ActionNoise of std zero attached
+(`_noise`: the sampling actor's whole work, the same states), and pbg_gae at T = 200 is set against the torch
+loop it replaces; written to profiles/action_noise_rollout.json.  --lib runs the legs a library has against
+another build of libpbg_amd.so (the parent commit's, alternated with this tree's in one session).
+
   python tools/bench_population.py [--out profiles/population_rollout.json]
   python tools/bench_population.py --obs-norm [--out profiles/obs_norm_rollout.json]
+  python tools/bench_population.py --action-noise [--lib PATH] [--out profiles/action_noise_rollout.json]
   python tools/bench_population.py --actor-only [--members 1024]   # actor launches alone, for a kernel trace
 """
 from __future__ import annotations
@@ -185,6 +191,101 @@ def bench_obs_norm(args, dev):
     return out
 
 
+NOISE_LEGS = {"A": (None, False), "B": (1024, False), "A_noise": (None, True), "B_noise": (1024, True)}
+
+
+def bench_action_noise(args, dev):
+    """Legs A and B of bench_rollout, each plain and with an ActionNoise attached.  The noise's std is zero (a
+    fresh object's): every sampled action is mu + 0 eps = mu through the same Philox block, Box-Muller pair,
+    LDS round trip, barrier and float64 multiply-add as under any other std, and all four legs stay in the same
+    state bit for bit (asserted on the final observations).  A library without the action noise (--lib, a
+    build of the parent commit) runs the plain legs only."""
+    import torch
+    from pybulletgym_amd import _native
+    from pybulletgym_amd.policy import ActionNoise
+    from pybulletgym_amd.vec_env import VecEnv
+    has = hasattr(_native.lib(), "pbg_action_noise_create")
+    legs = {leg: v for leg, v in NOISE_LEGS.items() if has or not v[1]}
+    pis, dims, _ = actors(dev, {leg: m for leg, (m, _) in legs.items()})
+    noises = {}
+    for leg, (m, sample) in legs.items():
+        if sample:
+            noises[leg] = ActionNoise(dims[3], 0, dev)
+            pis[leg].attach_action_noise(noises[leg])
+    envs = {leg: VecEnv(ENV_ID, N, device=dev, seed=0, autoreset=True, precision=64) for leg in legs}
+    for e in envs.values():
+        e.reset()
+    pre = (args.preroll + args.warmup + K - 1) // K
+    for _ in range(pre):
+        for leg in legs:
+            envs[leg].rollout(pis[leg], K)
+    torch.cuda.synchronize(dev)
+    graphs = {leg: capture(lambda leg=leg: envs[leg].rollout(pis[leg], K), dev) for leg in legs}
+    for leg in legs:
+        graphs[leg].replay()
+    w = timed(args.windows, args.replays, list(legs), lambda leg: graphs[leg].replay(), dev, K)
+    out = summary(w)
+    med = out["median"]
+    out.update({"env_id": ENV_ID, "n_envs": N, "precision": 64, "steps_per_graph": K, "replays_per_window": args.replays,
+                "unit": "us per env-batch step", "library": os.path.relpath(_native.LIB_PATH, REPO),
+                "legs": {leg: {"members": m, "mode": "sampling" if s else "plain"} for leg, (m, s) in legs.items()},
+                "mlp_dims": dims, "std": "zero (mu + 0 eps: the same operations, the same states)",
+                "delta_us": {leg: med[leg] - med[leg[0]] for leg in legs if legs[leg][1]},
+                "plain_leg_spread_us": {leg: out["max"][leg] - out["min"][leg] for leg in ("A", "B")},
+                "steps_sampled": {leg: z.counter for leg, z in noises.items()},
+                "final_obs_equal": bool(all(torch.equal(envs["A"].obs, envs[leg].obs) for leg in legs))})
+    for e in envs.values():
+        e.close()
+    for leg, p in pis.items():
+        if leg in noises:
+            p.attach_action_noise(None)
+        p.close()
+    for z in noises.values():
+        z.close()
+    return out
+
+
+def gae_torch_loop(rew, done, value, gamma, lam):
+    """The chain of small torch kernels pbg_gae replaces: T steps of about six launches each."""
+    import torch
+    T = rew.shape[0]
+    adv, ret = torch.empty_like(rew), torch.empty_like(rew)
+    A = torch.zeros_like(value[0], dtype=torch.float64)
+    for t in range(T - 1, -1, -1):
+        nd = 1.0 - done[t].double()
+        v = value[t].double()
+        delta = rew[t].double() + gamma * value[t + 1].double() * nd - v
+        A = delta + gamma * lam * nd * A
+        adv[t] = A.float()
+        ret[t] = (A + v).float()
+    return adv, ret
+
+
+def bench_gae(args, dev, T=200):
+    """pbg_gae at T = 200, n = 16,384 beside the torch loop it replaces (eager launches, as a learner would run it)."""
+    import torch
+    from pybulletgym_amd.ppo import gae
+    g = torch.Generator(device=dev)
+    g.manual_seed(0)
+    rew = torch.randn((T, N), device=dev, generator=g)
+    value = torch.randn((T + 1, N), device=dev, generator=g)
+    done = (torch.rand((T, N), device=dev, generator=g) < 0.01).to(torch.uint8)
+    adv, ret = torch.empty_like(rew), torch.empty_like(rew)
+    runs = {"pbg_gae": lambda: gae(rew, done, value, 0.99, 0.95, adv=adv, ret=ret),
+            "torch_loop": lambda: gae_torch_loop(rew, done, value, 0.99, 0.95)}
+    for f in runs.values():
+        f()
+    ta, tr = runs["torch_loop"]()
+    runs["pbg_gae"]()
+    err = max(float((ta - adv).abs().max()), float((tr - ret).abs().max()))
+    w = timed(args.windows, 5, list(runs), lambda leg: runs[leg](), dev, 1)
+    out = summary(w)
+    out.update({"T": T, "n": N, "unit": "us per call", "max_abs_difference_from_the_torch_loop": err,
+                "bytes_touched": T * N * (4 + 1 + 4 + 4 + 4) + N * 4,
+                "speedup_median": out["median"]["torch_loop"] / out["median"]["pbg_gae"]})
+    return out
+
+
 def bench_copy(args, dev):
     """Device-to-device copy of 1 GiB: bytes read plus bytes written over the time."""
     import torch
@@ -247,6 +348,8 @@ def main():
     ap.add_argument("--out", default=None, help="default: profiles/population_rollout.json "
                     "(--obs-norm: profiles/obs_norm_rollout.json)")
     ap.add_argument("--obs-norm", action="store_true", help="the observation-normalisation legs only")
+    ap.add_argument("--action-noise", action="store_true", help="the action-noise legs and pbg_gae only")
+    ap.add_argument("--lib", default=None, help="another build of libpbg_amd.so (the parent commit's, to alternate with)")
     ap.add_argument("--preroll", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--windows", type=int, default=5)
@@ -257,10 +360,33 @@ def main():
     import torch
     import pybulletgym_amd  # noqa: F401
     dev = torch.device("cuda:0")
+    if args.lib:
+        from pybulletgym_amd import _native
+        _native.LIB_PATH = os.path.abspath(args.lib)
     if args.actor_only:
         return actor_only(args, dev)
     if args.out is None:
-        args.out = os.path.join(REPO, "profiles", "obs_norm_rollout.json" if args.obs_norm else "population_rollout.json")
+        name = "action_noise_rollout.json" if args.action_noise else \
+            "obs_norm_rollout.json" if args.obs_norm else "population_rollout.json"
+        args.out = os.path.join(REPO, "profiles", name)
+    if args.action_noise:
+        from pybulletgym_amd import _native
+        res = {"rollout": bench_action_noise(args, dev)}
+        if hasattr(_native.lib(), "pbg_gae"):
+            res["gae"] = bench_gae(args, dev)
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+        r = res["rollout"]
+        print("rollout us/step median [min, max]: " + "  ".join(
+            f"{leg} {r['median'][leg]:.1f} [{r['min'][leg]:.1f}, {r['max'][leg]:.1f}]" for leg in r["median"]) +
+            f"  same states: {r['final_obs_equal']}")
+        if "gae" in res:
+            g = res["gae"]
+            print("gae us/call median [min, max]: " + "  ".join(
+                f"{k} {g['median'][k]:.1f} [{g['min'][k]:.1f}, {g['max'][k]:.1f}]" for k in g["median"]))
+        print(json.dumps({"done": bool(r["final_obs_equal"]), "out": args.out}))
+        return
     if args.obs_norm:
         res = {"rollout": bench_obs_norm(args, dev)}
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)

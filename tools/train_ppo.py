@@ -1,0 +1,96 @@
+#!/usr/bin/env python3
+"""Train a SmallReactivePolicy-shaped MLP on the device with PPO (pybullet-gym_amd/ppo.py: Gaussian action noise
+inside the actor launch, one-launch GAE, clipped-surrogate updates by torch autograd) and write the mean policy
+as an npz that tools/enjoy.py and MLPPolicy.from_npz load.
+
+  python tools/train_ppo.py InvertedPendulumPyBulletEnv-v0 [--envs 256] [--steps 32] [--iterations 40]
+         [--lr 3e-3] [--epochs 4] [--minibatches 4] [--gamma 0.99] [--lam 0.95] [--clip 0.2] [--log-std -0.5]
+         [--ent-coef 0.0] [--vf-coef 0.5] [--seed 0] [--precision 64] [--hidden 64 64] [--out ppo_policy.npz]
+         [--obs-norm] [--obs-clip 5.0] [--eval-envs 256] [--eval-steps 200] [--eval-every 1] [--curve curve.json]
+
+--obs-norm trains under running observation normalisation (PPO(obs_norm=True)) and saves the final normaliser
+in the npz (obs_mean, obs_inv_std, obs_clip); --curve writes the per-iteration evaluation as JSON.
+
+Per evaluated iteration it prints the noise-free mean policy's mean first-episode return and length over
+--eval-envs envs of a separate batch without auto-reset."""
+from __future__ import annotations
+
+import argparse
+import os
+import sys
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("env_id")
+    ap.add_argument("--envs", type=int, default=256, help="training envs (even)")
+    ap.add_argument("--steps", type=int, default=32, help="env steps per iteration's rollout")
+    ap.add_argument("--iterations", type=int, default=40)
+    ap.add_argument("--lr", type=float, default=3e-3)
+    ap.add_argument("--epochs", type=int, default=4)
+    ap.add_argument("--minibatches", type=int, default=4)
+    ap.add_argument("--gamma", type=float, default=0.99)
+    ap.add_argument("--lam", type=float, default=0.95)
+    ap.add_argument("--clip", type=float, default=0.2)
+    ap.add_argument("--log-std", type=float, default=-0.5, help="initial log standard deviation of the actions")
+    ap.add_argument("--ent-coef", type=float, default=0.0)
+    ap.add_argument("--vf-coef", type=float, default=0.5)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--precision", type=int, choices=(32, 64), default=64)
+    ap.add_argument("--hidden", type=int, nargs=2, default=(64, 64), metavar=("H1", "H2"))
+    ap.add_argument("--eval-envs", type=int, default=256)
+    ap.add_argument("--eval-steps", type=int, default=200)
+    ap.add_argument("--eval-every", type=int, default=1)
+    ap.add_argument("--out", default="ppo_policy.npz")
+    ap.add_argument("--obs-norm", action="store_true", help="running observation normalisation")
+    ap.add_argument("--obs-clip", type=float, default=5.0)
+    ap.add_argument("--curve", default=None, help="write the per-iteration evaluation here (JSON)")
+    args = ap.parse_args()
+
+    import json
+
+    import torch
+    import pybulletgym_amd  # noqa: F401
+    from pybulletgym_amd.ppo import PPO
+    from pybulletgym_amd.vec_env import VecEnv
+
+    env = VecEnv(args.env_id, args.envs, device="cuda:0", seed=args.seed, autoreset=True, precision=args.precision)
+    test = VecEnv(args.env_id, args.eval_envs, device="cuda:0", seed=args.seed + 1, autoreset=False, precision=args.precision)
+    ppo = PPO(env, hidden=args.hidden, steps=args.steps, seed=args.seed, gamma=args.gamma, lam=args.lam, clip=args.clip,
+              lr=args.lr, epochs=args.epochs, minibatches=args.minibatches, vf_coef=args.vf_coef, ent_coef=args.ent_coef,
+              log_std=args.log_std, obs_norm=args.obs_norm, obs_clip=args.obs_clip)
+    print(f"{args.env_id} (float{args.precision}): {args.envs} envs x {args.steps} steps per iteration, actor MLP "
+          f"{ppo.actor_dims}, lr {args.lr}, {args.epochs} epochs x {args.minibatches} minibatches, observation "
+          f"normalisation {'on' if args.obs_norm else 'off'}")
+    curve = []
+
+    def report(it):
+        ret, length = ppo.evaluate(test, args.eval_steps)
+        curve.append(dict(iteration=it, return_mean=ret.mean().item(), return_min=ret.min().item(),
+                          length_mean=length.double().mean().item(), std_mean=ppo.log_std.data.exp().mean().item()))
+        print(f"iteration {it:4d}: mean policy return mean {ret.mean().item():9.2f} min {ret.min().item():9.2f}  "
+              f"first-episode length mean {length.double().mean().item():6.1f} of {args.eval_steps}  "
+              f"action std {curve[-1]['std_mean']:.3f}", flush=True)
+
+    report(0)
+    for it in range(1, args.iterations + 1):
+        ppo.iterate()
+        if it % args.eval_every == 0 or it == args.iterations:
+            report(it)
+    torch.cuda.synchronize()
+    ppo.save_npz(args.out)
+    print(f"wrote {args.out}")
+    if args.curve:
+        with open(args.curve, "w") as f:
+            json.dump(dict(vars(args), curve=curve), f, indent=1)
+        print(f"wrote {args.curve}")
+    ppo.close()
+    test.close()
+    env.close()
+
+
+if __name__ == "__main__":
+    main()
