@@ -522,6 +522,104 @@ int pbg_gae(int T, int n, const float* rew_traj, const uint8_t* done_traj, const
 int pbg_gae_host(int T, int n, const float* rew_traj, const uint8_t* done_traj, const float* value, double gamma,
                  double lambda, float* adv_out, float* ret_out);
 
+/* ---- PPO gradient (appended; nothing above changes) ----
+ * The gradient of the clipped-surrogate loss (Schulman et al. 2017) of one minibatch with respect to the actor's
+ * and the critic's flat parameters and log_std, as at most two launches: the tiles, then the reduction.  Actor
+ * (obs_dim -> h1 -> h2 -> act_dim) and critic (obs_dim -> h1 -> h2 -> 1) share obs_dim, h1, h2; A = act_dim,
+ * Da, Dc = the two networks' D (Flat parameter layout), B = batch_rows, Bm = mb_rows.
+ *
+ * The function.  Row i of the minibatch is row r = idx[i] of the batch (idx NULL: r = i).  With c = clip_eps:
+ *   mu = actor(obs_r), v = critic(obs_r)                  through the normaliser when mean / inv_std are set
+ *   z_j = (act_rj - mu_j) exp(-log_std_j)
+ *   logp = -1/2 sum_j z_j^2 - sum_j log_std_j - 1/2 A log 2 pi
+ *   a^ = adv_norm ? (adv_r - adv_norm[0]) * adv_norm[1] : adv_r
+ *   ratio = exp(logp - logp_old_r);  s1 = ratio a^;  s2 = clamp(ratio, 1 - c, 1 + c) a^
+ *   L = mean_i(-min(s1, s2)) + vf_coef 1/2 mean_i((v - ret_r)^2) - ent_coef (sum_j log_std_j + const)
+ * and the derivatives are
+ *   dL/dlogp_i = -(s1 <= s2 ? a^ ratio : 0) / Bm     (inside the clip range s1 == s2: the gradient flows)
+ *   dlogp/dmu_j = z_j exp(-log_std_j);  dlogp/dlog_std_j = z_j^2 - 1;  dL/dlog_std_j gets a further -ent_coef
+ *   dL/dv_i = vf_coef (v - ret_r) / Bm
+ *   ReLU passes the gradient where the stored activation is > 0.
+ *
+ * Forward numerics are the actor's: mu and v are the Numeric contract's k-ascending fmaf chains, after
+ * pbg_policy_set_obs_norm's transform when a normaliser is given, so v_out equals pbg_population_act of the
+ * critic's weights on the same rows bit for bit and the ReLU masks are the ones the rollout's network had.
+ * Everything from z to the two derivatives dL/dmu_ij and dL/dv_i is float64 per row (one function, host and
+ * device), rounded once to float32.  logp_out is that logp, the one the gradient used.
+ *
+ * The surrogate, the clipped fraction and mean(logp_old - logp) of `stats` come from a second, float64 evaluation
+ * of the actor on the same rows (the same transform and the same k-ascending chain from the bias, as fma in
+ * float64 on the float32 parameters; the same per-row expressions).  mean(logp_old - logp) is a mean of cancelling
+ * terms, of which the float32 chain's rounding of mu would leave three digits at 64 action components.  The value
+ * loss is taken from the float32 v.  A row whose ratio lies within the float32 forward's error of a clip edge can
+ * count as clipped in `stats` and not in the gradient, or the reverse.
+ *
+ * Backward numerics and the order of every sum.  The minibatch is cut into tiles of 16 consecutive rows;
+ * the launch has G = min(number of tiles, the object's workgroup count) workgroups, and workgroup b owns the
+ * tiles b, b + G, b + 2 G, ...  Per tile every weight-gradient element is one float32 fmaf chain over the tile's
+ * rows in ascending order started from zero (a bias or log_std element: the same chain with a factor 1), every
+ * back-propagated activation one float32 fmaf chain over the layer's outputs j in ascending order started from
+ * zero.  A workgroup adds its tiles' values in ascending tile order in float32 into a partial it alone owns;
+ * the reduction adds the G partials in ascending b in float64 and rounds once (grad_log_std: after subtracting
+ * ent_coef in float64).  The four stats are float64 throughout: per row-in-tile slot summed over the
+ * workgroup's tiles ascending, then over the 16 slots ascending, then over b ascending, then divided by Bm.
+ * The workgroup count is fixed at creation: min(ceil(max_rows / 16), 512, as many partials as fit 128 MiB),
+ * at least 1.  There are no atomics: the result is a function of the inputs and of max_rows alone, the same
+ * bits on every call, on every stream and inside a replayed graph.
+ *
+ * pbg_ppo_grad_host is the same function on HOST pointers with no GPU: the same forward chains and the same
+ * per-row functions; its backward sums in float64 over rows ascending and rounds once, and its exp is the
+ * host's, so it agrees with the device to rounding, not bitwise.  Its v_out is bitwise the device's. */
+typedef struct pbg_ppo_grad pbg_ppo_grad;
+
+/* All pointers DEVICE memory of the object's GPU (pbg_ppo_grad_run) or HOST memory (pbg_ppo_grad_host); nothing
+ * is copied or kept, the parameters are read where they lie.  Versioned by struct_size like pbg_rollout_io_t:
+ * PBG_E_ARG for a size below the first version's (which ends with v_out), above the library's, or not a
+ * multiple of 4. */
+typedef struct {
+  uint32_t struct_size;
+  int batch_rows;            /* B >= 1 */
+  int mb_rows;               /* Bm: 1 <= Bm <= max_rows; with idx NULL also Bm <= B */
+  int reserved;              /* 0 */
+  const float* theta_actor;  /* [Da] */
+  const float* theta_critic; /* [Dc] */
+  const float* log_std;      /* [A] */
+  const float* mean;         /* [obs_dim], nullable with inv_std: no normaliser */
+  const float* inv_std;      /* [obs_dim] */
+  float clip;                /* the normaliser's, > 0 when it is set */
+  float clip_eps;            /* c >= 0 */
+  float vf_coef;
+  float ent_coef;
+  const float* obs;          /* [B, obs_dim] */
+  const float* act;          /* [B, A] */
+  const float* logp_old;     /* [B] */
+  const float* adv;          /* [B] */
+  const float* ret;          /* [B] */
+  const int64_t* idx;        /* [Bm] rows of the batch, nullable: rows 0 .. Bm - 1.  pbg_ppo_grad_run does NOT
+                                validate the indices (they live on the device): every one must be in 0 .. B - 1.
+                                pbg_ppo_grad_host does (PBG_E_ARG) */
+  const float* adv_norm;     /* [2] (shift, scale), nullable */
+  float* grad_actor;         /* [Da] out */
+  float* grad_critic;        /* [Dc] out */
+  float* grad_log_std;       /* [A] out */
+  double* stats;             /* [4] out: mean_i(-min(s1, s2)), 1/2 mean_i((v - ret)^2), the fraction of rows with
+                                |ratio - 1| > c, mean_i(logp_old - logp) */
+  float* logp_out;           /* [Bm] out, nullable: logp in minibatch order */
+  float* v_out;              /* [Bm] out, nullable: v in minibatch order */
+} pbg_ppo_grad_io_t;
+
+/* The object owns the reduction's device workspace for up to max_rows minibatch rows.  PBG_E_ARG (before any HIP
+ * call) for dims out of pbg_policy_create's ranges, max_rows < 1, device < 0 or out NULL; PBG_E_HIP for a device
+ * that does not exist.  *out is NULL after every failure. */
+int pbg_ppo_grad_create(int device, int obs_dim, int h1, int h2, int act_dim, int max_rows, pbg_ppo_grad** out);
+void pbg_ppo_grad_destroy(pbg_ppo_grad* g);
+/* Two launches on `stream`, no host work, no synchronisation: captures as a plain chain.  PBG_E_ARG (before any
+ * HIP call) for a NULL argument or required pointer, a bad struct_size, mb_rows outside 1 .. max_rows, batch_rows
+ * < 1 (< mb_rows with idx NULL), one of mean / inv_std NULL, a normaliser clip that is not > 0 or a clip_eps that
+ * is not >= 0.  Two calls with one object must not overlap on the device (they share the workspace). */
+int pbg_ppo_grad_run(pbg_ppo_grad* g, const pbg_ppo_grad_io_t* io, void* stream);
+int pbg_ppo_grad_host(int obs_dim, int h1, int h2, int act_dim, const pbg_ppo_grad_io_t* io);
+
 #ifdef __cplusplus
 }
 #endif

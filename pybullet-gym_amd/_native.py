@@ -72,6 +72,22 @@ class RolloutIO(ctypes.Structure):
         super().__init__(struct_size=ctypes.sizeof(RolloutIO), **kw)
 
 
+class PPOGradIO(ctypes.Structure):
+    """pbg_ppo_grad_io_t (pbg_ppo_grad_run, pbg_ppo_grad_host): versioned by struct_size."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("batch_rows", ctypes.c_int), ("mb_rows", ctypes.c_int),
+                ("reserved", ctypes.c_int), ("theta_actor", ctypes.c_void_p), ("theta_critic", ctypes.c_void_p),
+                ("log_std", ctypes.c_void_p), ("mean", ctypes.c_void_p), ("inv_std", ctypes.c_void_p),
+                ("clip", ctypes.c_float), ("clip_eps", ctypes.c_float), ("vf_coef", ctypes.c_float),
+                ("ent_coef", ctypes.c_float), ("obs", ctypes.c_void_p), ("act", ctypes.c_void_p),
+                ("logp_old", ctypes.c_void_p), ("adv", ctypes.c_void_p), ("ret", ctypes.c_void_p),
+                ("idx", ctypes.c_void_p), ("adv_norm", ctypes.c_void_p), ("grad_actor", ctypes.c_void_p),
+                ("grad_critic", ctypes.c_void_p), ("grad_log_std", ctypes.c_void_p), ("stats", ctypes.c_void_p),
+                ("logp_out", ctypes.c_void_p), ("v_out", ctypes.c_void_p)]
+
+    def __init__(self, **kw):
+        super().__init__(struct_size=ctypes.sizeof(PPOGradIO), **kw)
+
+
 POLICY_MAX_DIM = 256  # PBG_POLICY_MAX_DIM: obs_dim, h1, h2
 POLICY_MAX_ACT = 64   # PBG_POLICY_MAX_ACT
 
@@ -175,6 +191,15 @@ def lib():
         for f in ACTION_NOISE_EXPORTED:
             if f != "pbg_action_noise_destroy":
                 getattr(L, f).restype = I
+    if hasattr(L, "pbg_ppo_grad_create"):  # the PPO update's backward pass
+        L.pbg_ppo_grad_create.argtypes = [I, I, I, I, I, I, ctypes.POINTER(H)]
+        L.pbg_ppo_grad_destroy.argtypes = [H]
+        L.pbg_ppo_grad_destroy.restype = None
+        L.pbg_ppo_grad_run.argtypes = [H, ctypes.POINTER(PPOGradIO), P]
+        L.pbg_ppo_grad_host.argtypes = [I, I, I, I, ctypes.POINTER(PPOGradIO)]
+        for f in PPO_GRAD_EXPORTED:
+            if f != "pbg_ppo_grad_destroy":
+                getattr(L, f).restype = I
     for f in ("pbg_info", "pbg_reset", "pbg_step", "pbg_step_ex", "pbg_get_state", "pbg_set_state",
               "pbg_pack_record_sizes", "pbg_pack", "pbg_create_debug", "pbg_sample_actions", "pbg_create_ex",
               "pbg_default_sim_params", "pbg_get_sim_params", "pbg_create_v2", "pbg_precision"):
@@ -195,12 +220,13 @@ ACTION_NOISE_EXPORTED = ("pbg_action_noise_create", "pbg_action_noise_destroy", 
                          "pbg_action_noise_set_counter", "pbg_action_noise_get_counter", "pbg_action_noise_set_eps2_traj",
                          "pbg_action_noise_fill", "pbg_action_noise_host", "pbg_policy_attach_action_noise",
                          "pbg_population_attach_action_noise", "pbg_gae", "pbg_gae_host")
+PPO_GRAD_EXPORTED = ("pbg_ppo_grad_create", "pbg_ppo_grad_destroy", "pbg_ppo_grad_run", "pbg_ppo_grad_host")
 EXPORTED = ("pbg_create", "pbg_create_debug", "pbg_create_ex", "pbg_create_v2", "pbg_precision",
             "pbg_default_sim_params", "pbg_get_sim_params",
             "pbg_destroy", "pbg_info", "pbg_reset", "pbg_step", "pbg_step_ex",
             "pbg_get_state", "pbg_set_state", "pbg_pack_record_sizes", "pbg_pack", "pbg_sample_actions",
             "pbg_debug_poison", "pbg_last_error") + POLICY_EXPORTED + POPULATION_EXPORTED + OBS_NORM_EXPORTED + \
-    ACTION_NOISE_EXPORTED
+    ACTION_NOISE_EXPORTED + PPO_GRAD_EXPORTED
 
 
 def check(rc: int, what: str):

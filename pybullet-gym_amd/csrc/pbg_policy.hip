@@ -55,18 +55,6 @@ Norm norm_of(const Actor& a, const float* base) {
   return Norm{base, base + a.obs_dim, a.clip};
 }
 
-// the contract's chain on the CPU: y[j] = fmaf chain over k ascending from the bias
-void host_layer(const float* W, const float* b, int K, int H, bool relu, const float* x, float* y) {
-  for (int j = 0; j < H; j++) y[j] = b[j];
-  for (int k = 0; k < K; k++) {
-    const float xk = x[k];
-    const float* w = W + (size_t)k * H;
-    for (int j = 0; j < H; j++) y[j] = __builtin_fmaf(xk, w[j], y[j]);
-  }
-  if (relu)
-    for (int j = 0; j < H; j++) y[j] = y[j] < 0.f ? 0.f : y[j];
-}
-
 }  // namespace
 
 // an Actor with one member, plus the host's copies: pbg_policy_act_host and host-only policies run on them

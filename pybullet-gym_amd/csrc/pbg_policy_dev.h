@@ -1,6 +1,8 @@
 // pbg_policy_dev.h -- what the actor translation units (pbg_policy.hip, pbg_population.hip, pbg_obsnorm.hip,
-// pbg_actnoise.hip) share: the description of an actor (Actor: a pbg_policy is one with a single member whose group is the
-// whole batch, a pbg_population one with 2 n_pairs), the MLP tile that pbg_policy.hip's actor_kernel
+// pbg_actnoise.hip) and the PPO gradient (pbg_ppograd.hip: `layer`, `normalise`, host_layer and the per-row loss
+// derivative and statistics ppo_actor_row / ppo_critic_row / ppo_stats_row) share: the description of an actor (Actor: a pbg_policy is one with
+// a single member whose group is the whole batch, a pbg_population one with 2 n_pairs), the MLP tile that
+// pbg_policy.hip's actor_kernel
 // evaluates with the workgroup's member's weights, the rollout bookkeeping, the one actor launch and the
 // rollout loop (pbg_rollout and pbg_rollout_population are the same 2 T + 1 launches), and the host helpers
 // of the three objects.
@@ -342,6 +344,91 @@ __device__ __forceinline__ void act_tile(const Weights P, const Norm nm, const S
     act[at] = v;
     if (act_traj) act_traj[at] = v;
   }
+}
+
+// the contract's chain on the CPU (pbg_policy_act_host, pbg_ppo_grad_host): y[j] = fmaf chain over k ascending
+// from the bias
+inline void host_layer(const float* W, const float* b, int K, int H, bool relu, const float* x, float* y) {
+  for (int j = 0; j < H; j++) y[j] = b[j];
+  for (int k = 0; k < K; k++) {
+    const float xk = x[k];
+    const float* w = W + (size_t)k * H;
+    for (int j = 0; j < H; j++) y[j] = __builtin_fmaf(xk, w[j], y[j]);
+  }
+  if (relu)
+    for (int j = 0; j < H; j++) y[j] = y[j] < 0.f ? 0.f : y[j];
+}
+
+// pbg.h "PPO gradient": the per-row loss derivative and the row's terms of `stats`, host and device, float64.
+// logp of a row from its means mu[j * stride] (float: the contract's forward; double: the statistics' forward):
+// inv_sig[j] = exp(-log_std_j), sum_ls = sum_j log_std_j (j ascending)
+template <typename T>
+__host__ __device__ __forceinline__ double ppo_logp_row(int A, const T* mu, int stride, const float* __restrict__ act_row,
+                                                        const double* inv_sig, double sum_ls) {
+  double q = 0.0;
+  for (int j = 0; j < A; j++) {
+    const double z = ((double)act_row[j] - (double)mu[j * stride]) * inv_sig[j];
+    q += z * z;
+  }
+  return -0.5 * q - sum_ls - 0.5 * (double)A * 1.8378770664093453;  // log 2 pi
+}
+
+// The actor's row: mu[j * stride] (j < A) holds the row's float32 means and takes dL/dmu_j in their place,
+// dls[j * stride] takes the row's term of dL/dlog_std_j; ahat the (normalised) advantage, c = clip_eps,
+// inv_bm = 1 / Bm.  Returns logp.
+__host__ __device__ __forceinline__ double ppo_actor_row(int A, float* mu, float* dls, int stride,
+                                                         const float* __restrict__ act_row, const double* inv_sig,
+                                                         double sum_ls, double logp_old, double ahat, double c, double inv_bm) {
+  const double logp = ppo_logp_row(A, mu, stride, act_row, inv_sig, sum_ls);
+  const double ratio = exp(logp - logp_old);
+  const double lo = 1.0 - c, hi = 1.0 + c;
+  const double s1 = ratio * ahat, s2 = (ratio < lo ? lo : (ratio > hi ? hi : ratio)) * ahat;
+  const double dlogp = s1 <= s2 ? -(ahat * ratio) * inv_bm : 0.0;
+  for (int j = 0; j < A; j++) {
+    const double z = ((double)act_row[j] - (double)mu[j * stride]) * inv_sig[j];
+    mu[j * stride] = (float)(dlogp * z * inv_sig[j]);
+    dls[j * stride] = (float)(dlogp * (z * z - 1.0));
+  }
+  return logp;
+}
+
+// The row's terms of (pg loss, clipped, logp_old - logp) from the float64 means mu64[j * stride]: the last is a
+// mean of cancelling terms, which the float32 forward's rounding would leave with three digits.
+__host__ __device__ __forceinline__ void ppo_stats_row(int A, const double* mu64, int stride, const float* __restrict__ act_row,
+                                                       const double* inv_sig, double sum_ls, double logp_old, double ahat,
+                                                       double c, double st[3]) {
+  const double logp = ppo_logp_row(A, mu64, stride, act_row, inv_sig, sum_ls);
+  const double ratio = exp(logp - logp_old);
+  const double lo = 1.0 - c, hi = 1.0 + c;
+  const double s1 = ratio * ahat, s2 = (ratio < lo ? lo : (ratio > hi ? hi : ratio)) * ahat;
+  st[0] = -(s1 < s2 ? s1 : s2);
+  st[1] = (ratio - 1.0 > c || 1.0 - ratio > c) ? 1.0 : 0.0;
+  st[2] = logp_old - logp;
+}
+
+// The statistics' forward (pbg.h "PPO gradient"): the contract's transform and chain in float64, host and device.
+__host__ __device__ __forceinline__ double normalise64(float x, float mean, float inv_std, float clip) {
+  const double v = ((double)x - (double)mean) * (double)inv_std, c = (double)clip;
+  return v < -c ? -c : (v > c ? c : v);
+}
+
+// y[j] = fma chain over k ascending from the bias, float64 from the float32 parameters
+inline void host_layer64(const float* W, const float* b, int K, int H, bool relu, const double* x, double* y) {
+  for (int j = 0; j < H; j++) y[j] = (double)b[j];
+  for (int k = 0; k < K; k++) {
+    const double xk = x[k];
+    const float* w = W + (size_t)k * H;
+    for (int j = 0; j < H; j++) y[j] = __builtin_fma(xk, (double)w[j], y[j]);
+  }
+  if (relu)
+    for (int j = 0; j < H; j++) y[j] = y[j] < 0.0 ? 0.0 : y[j];
+}
+
+// The critic's row: dL/dv; *vf takes the row's term of the value loss.
+__host__ __device__ __forceinline__ float ppo_critic_row(float v, float ret, double vf_coef, double inv_bm, double* vf) {
+  const double d = (double)v - (double)ret;
+  *vf = 0.5 * d * d;
+  return (float)(vf_coef * d * inv_bm);
 }
 
 // workgroups (= slots) of an actor launch over n rows in groups of G (n a multiple of G > 0)

@@ -4,8 +4,9 @@
 The per-step path is HIP: ``VecEnv.rollout`` with an ``ActionNoise`` attached acts ``a = mu(obs) + std eps``
 inside the actor launch and records ``sum eps^2`` for the log-probability (include/pbg.h "Stochastic Gaussian
 actions"), the critic's values are one ``MLPPopulation.act`` over the whole trajectory, and ``gae`` is one
-launch (pbg_gae).  The backward pass is torch autograd on purpose: it runs K M times per iteration, not
-T times, and is plumbing here.  The collection half of an iteration has no host work between its launches."""
+launch (pbg_gae).  The backward pass is torch autograd by default (``PPO(backward="torch")``); with
+``backward="hip"`` each minibatch's gradient is ``PPOGrad.run``: two launches (pbg_ppo_grad, include/pbg.h "PPO
+gradient").  The collection half of an iteration has no host work between its launches."""
 from __future__ import annotations
 
 import ctypes
@@ -73,6 +74,111 @@ def mlp_forward(theta, dims, x, obs_norm=None):
     return x
 
 
+class PPOGrad:
+    """The gradient of the clipped-surrogate loss of one minibatch as two HIP launches (include/pbg.h "PPO
+    gradient", pbg_ppo_grad).  ``dims = (obs_dim, h1, h2, act_dim)``: the actor's; the critic is obs_dim -> h1 -> h2
+    -> 1.  ``device``: a GPU, or ``None`` / ``"cpu"`` for the host twin (pbg_ppo_grad_host, numpy arrays, no GPU).
+    ``max_rows``: the largest minibatch ``run`` will see (it sizes the reduction's workspace)."""
+
+    def __init__(self, dims, max_rows: int, device=None):
+        if not hasattr(_native.lib(), "pbg_ppo_grad_create"):
+            raise _native.PbgError(f"{_native.LIB_PATH} has no pbg_ppo_grad_create: a build without the PPO gradient")
+        self.dims = tuple(int(d) for d in dims)
+        if len(self.dims) != 4:
+            raise _native.PbgError(f"PPOGrad: dims must be (obs_dim, h1, h2, act_dim), got {dims!r}")
+        o, h1, h2, a = self.dims
+        self.Da = o * h1 + h1 + h1 * h2 + h2 + h2 * a + a
+        self.Dc = o * h1 + h1 + h1 * h2 + h2 + h2 + 1
+        self.max_rows = int(max_rows)
+        self.host = device is None or str(device) == "cpu"
+        self.device = None if self.host else torch.device(device)
+        self._h = ctypes.c_void_p()
+        if self.host:
+            if self.max_rows < 1 or not (1 <= o <= _native.POLICY_MAX_DIM and 1 <= h1 <= _native.POLICY_MAX_DIM and
+                                         1 <= h2 <= _native.POLICY_MAX_DIM and 1 <= a <= _native.POLICY_MAX_ACT):
+                raise _native.PbgError(f"PPOGrad: dims {self.dims} or max_rows {max_rows} out of range")
+            return
+        if self.device.type != "cuda":
+            raise _native.PbgError(f"PPOGrad: device must be a GPU or None, got {device!r}")
+        index = self.device.index if self.device.index is not None else torch.cuda.current_device()
+        self.device = torch.device("cuda", index)
+        _native.check(_native.lib().pbg_ppo_grad_create(index, o, h1, h2, a, self.max_rows, ctypes.byref(self._h)),
+                      "pbg_ppo_grad_create")
+
+    def _ok(self, t, shape, dt):
+        if self.host:
+            return isinstance(t, np.ndarray) and t.flags.c_contiguous and tuple(t.shape) == shape and t.dtype == dt
+        return isinstance(t, torch.Tensor) and t.is_contiguous() and t.device == self.device and \
+            tuple(t.shape) == shape and t.dtype == dt
+
+    def run(self, theta_actor, theta_critic, log_std, obs, act, logp_old, adv, ret, idx=None, rows=None, adv_norm=None,
+            obs_norm=None, clip_eps: float = 0.2, vf_coef: float = 0.5, ent_coef: float = 0.0, grad_actor=None,
+            grad_critic=None, grad_log_std=None, stats=None, logp_out=None, v_out=None):
+        """``(grad_actor [Da], grad_critic [Dc], grad_log_std [A], stats float64 [4])`` of the minibatch ``idx`` (int64
+        ``[Bm]`` rows of the batch; ``None``: the first ``rows`` rows, default all) of the batch ``obs [B, obs_dim]``,
+        ``act [B, A]``, ``logp_old``, ``adv``, ``ret`` ``[B]``: contiguous float32 tensors on the object's GPU (numpy
+        arrays on the host).  ``adv_norm``: float32 ``[2]`` (shift, scale) or ``None``; ``obs_norm``: ``(mean, inv_std,
+        clip)`` or ``None``.  The outputs are written into the given tensors, or into new ones.  ``stats``: pg loss, vf
+        loss, clipped fraction, mean(logp_old - logp).  ``logp_out``, ``v_out``: optional float32 ``[Bm]``.  The indices
+        are not validated on a GPU."""
+        o, h1, h2, A = self.dims
+        f32, f64, i64 = (np.float32, np.float64, np.int64) if self.host else (torch.float32, torch.float64, torch.int64)
+        if getattr(obs, "ndim", 0) != 2:
+            raise _native.PbgError("PPOGrad.run: obs must be [B, obs_dim]")
+        B = int(obs.shape[0])
+        Bm = int(idx.shape[0]) if idx is not None and getattr(idx, "ndim", 0) == 1 else (B if rows is None else int(rows))
+        new = (lambda n, dt: np.empty(n, dt)) if self.host else (lambda n, dt: torch.empty(n, dtype=dt, device=self.device))
+        grad_actor = new(self.Da, f32) if grad_actor is None else grad_actor
+        grad_critic = new(self.Dc, f32) if grad_critic is None else grad_critic
+        grad_log_std = new(A, f32) if grad_log_std is None else grad_log_std
+        stats = new(4, f64) if stats is None else stats
+        mean, inv_std, clip = obs_norm if obs_norm is not None else (None, None, 0.0)
+        checks = [("theta_actor", theta_actor, (self.Da,), f32), ("theta_critic", theta_critic, (self.Dc,), f32),
+                  ("log_std", log_std, (A,), f32), ("obs", obs, (B, o), f32), ("act", act, (B, A), f32),
+                  ("logp_old", logp_old, (B,), f32), ("adv", adv, (B,), f32), ("ret", ret, (B,), f32),
+                  ("grad_actor", grad_actor, (self.Da,), f32), ("grad_critic", grad_critic, (self.Dc,), f32),
+                  ("grad_log_std", grad_log_std, (A,), f32), ("stats", stats, (4,), f64)]
+        checks += [(n, t, s, d) for n, t, s, d in (("idx", idx, (Bm,), i64), ("adv_norm", adv_norm, (2,), f32),
+                                                   ("mean", mean, (o,), f32), ("inv_std", inv_std, (o,), f32),
+                                                   ("logp_out", logp_out, (Bm,), f32), ("v_out", v_out, (Bm,), f32))
+                   if t is not None]
+        for name, t, shape, dt in checks:
+            if not self._ok(t, shape, dt):
+                raise _native.PbgError(f"PPOGrad.run: {name} must be a contiguous {dt} "
+                                       f"{'array' if self.host else f'tensor on {self.device}'} of shape {shape}")
+        if Bm < 1 or Bm > self.max_rows or (idx is None and Bm > B):
+            raise _native.PbgError(f"PPOGrad.run: {Bm} minibatch rows outside 1 .. max_rows = {self.max_rows} (or the batch's {B})")
+        if (mean is None) != (inv_std is None):
+            raise _native.PbgError("PPOGrad.run: obs_norm needs both mean and inv_std")
+        ptr = (lambda t: None if t is None else t.ctypes.data) if self.host else (lambda t: None if t is None else t.data_ptr())
+        io = _native.PPOGradIO(batch_rows=B, mb_rows=Bm, theta_actor=ptr(theta_actor), theta_critic=ptr(theta_critic),
+                               log_std=ptr(log_std), mean=ptr(mean), inv_std=ptr(inv_std), clip=float(clip),
+                               clip_eps=float(clip_eps), vf_coef=float(vf_coef), ent_coef=float(ent_coef), obs=ptr(obs),
+                               act=ptr(act), logp_old=ptr(logp_old), adv=ptr(adv), ret=ptr(ret), idx=ptr(idx),
+                               adv_norm=ptr(adv_norm), grad_actor=ptr(grad_actor), grad_critic=ptr(grad_critic),
+                               grad_log_std=ptr(grad_log_std), stats=ptr(stats), logp_out=ptr(logp_out), v_out=ptr(v_out))
+        if self.host:
+            _native.check(_native.lib().pbg_ppo_grad_host(o, h1, h2, A, ctypes.byref(io)), "pbg_ppo_grad_host")
+        else:
+            if not self._h:
+                raise _native.PbgError("PPOGrad.run: the object is closed")
+            with torch.cuda.device(self.device):
+                stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+                _native.check(_native.lib().pbg_ppo_grad_run(self._h, ctypes.byref(io), stream), "pbg_ppo_grad_run")
+        return grad_actor, grad_critic, grad_log_std, stats
+
+    def close(self):
+        if self._h:
+            _native.lib().pbg_ppo_grad_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 @dataclass
 class Batch:
     """One iteration's data (views of the env's rollout buffers and this object's own): ``[T, n, ...]``."""
@@ -95,13 +201,18 @@ class PPO:
     steps with Gaussian action noise, values, GAE, then ``epochs`` x ``minibatches`` clipped-surrogate updates.
     ``obs_norm=True``: running observation normalisation on section 12's schedule: statistics are attached
     during the rollout and finalized into both networks' normaliser after the update, which uses the normaliser
-    its data was collected under."""
+    its data was collected under.  ``backward="hip"``: every minibatch's gradient comes from ``PPOGrad.run`` (two
+    launches, written straight into the parameters' ``.grad``) instead of torch autograd; the permutation, the
+    gradient clipping and Adam are the same, and ``update``'s stats gain ``clipfrac`` and ``kl``."""
 
     def __init__(self, env, hidden=(64, 64), steps: int = 64, seed: int = 0, gamma: float = 0.99, lam: float = 0.95,
                  clip: float = 0.2, lr: float = 3e-4, epochs: int = 4, minibatches: int = 4, vf_coef: float = 0.5,
                  ent_coef: float = 0.0, log_std: float = -0.5, max_grad_norm: float = 0.5, norm_adv: bool = True,
-                 obs_norm: bool = False, obs_clip: float = 5.0):
+                 obs_norm: bool = False, obs_clip: float = 5.0, backward: str = "torch"):
         n, dev = env.num_envs, env.device
+        if backward not in ("torch", "hip"):
+            raise _native.PbgError(f"PPO: backward must be 'torch' or 'hip', got {backward!r}")
+        self.backward = backward
         if n % 2 != 0 or not env.autoreset:
             raise _native.PbgError("PPO: the env must have an even number of envs (the actors are populations of one "
                                    "pair) and autoreset=True")
@@ -137,6 +248,13 @@ class PPO:
         self._adv, self._ret = torch.zeros((T, n), **kw), torch.zeros((T, n), **kw)
         self._obs_all = torch.zeros(((T + 1) * n, obs_dim), **kw)
         self._std = torch.zeros(act_dim, **kw)
+        self.grad = None
+        if backward == "hip":
+            # the gradient tensors pbg_ppo_grad writes, bound once to the parameters' .grad
+            self.grad = PPOGrad(self.actor_dims, (T * n) // self.minibatches, dev)
+            for p in (self.actor_theta, self.critic_theta, self.log_std):
+                p.grad = torch.zeros_like(p.data)
+            self._grad_stats = torch.zeros(4, dtype=torch.float64, device=dev)
         env.reset()
 
     def _set_norm(self):
@@ -166,7 +284,10 @@ class PPO:
                      logp=res.logp_traj(self._std), value=self._value, adv=self._adv, ret=self._ret)
 
     def update(self, b: Batch) -> dict:
-        """``epochs`` passes of ``minibatches`` clipped-surrogate steps over the batch (torch autograd, Adam)."""
+        """``epochs`` passes of ``minibatches`` clipped-surrogate steps over the batch (Adam; the gradient by torch
+        autograd, or by pbg_ppo_grad with ``backward="hip"``)."""
+        if self.grad is not None:
+            return self._update_hip(b)
         T, n = self.steps, self.env.num_envs
         B, A = T * n, self.actor_dims[3]
         obs, act = b.obs.reshape(B, -1), b.act.reshape(B, A)
@@ -196,6 +317,31 @@ class PPO:
                 stats = dict(pg=pg.detach(), vf=vf.detach())
         return stats
 
+    def _update_hip(self, b: Batch) -> dict:
+        """``update`` with the gradient from ``PPOGrad.run``: the same permutation, clipping and optimiser step; the
+        parameters' storage is read where it lies and the three ``.grad`` tensors are overwritten in place."""
+        T, n = self.steps, self.env.num_envs
+        B, A = T * n, self.actor_dims[3]
+        obs, act = b.obs.reshape(B, -1), b.act.reshape(B, A)
+        logp_old, ret, adv = b.logp.reshape(B).float(), b.ret.reshape(B), b.adv.reshape(B)
+        params = [self.actor_theta, self.critic_theta, self.log_std]
+        for _ in range(self.epochs):
+            perm = torch.randperm(B, device=obs.device, generator=self._gen).view(self.minibatches, -1)
+            for idx in perm:
+                adv_norm = None
+                if self.norm_adv:
+                    a_mb = adv[idx]
+                    adv_norm = torch.stack((a_mb.mean(), 1.0 / (a_mb.std() + 1e-8)))
+                self.grad.run(self.actor_theta.data, self.critic_theta.data, self.log_std.data, obs, act, logp_old, adv, ret,
+                              idx=idx, adv_norm=adv_norm, obs_norm=self.actor.obs_norm, clip_eps=self.clip,
+                              vf_coef=self.vf_coef, ent_coef=self.ent_coef, grad_actor=self.actor_theta.grad,
+                              grad_critic=self.critic_theta.grad, grad_log_std=self.log_std.grad, stats=self._grad_stats)
+                if self.max_grad_norm:
+                    torch.nn.utils.clip_grad_norm_(params, self.max_grad_norm)
+                self.opt.step()
+        st = self._grad_stats.clone()   # the last minibatch's
+        return dict(pg=st[0], vf=st[1], clipfrac=st[2], kl=st[3])
+
     def iterate(self) -> dict:
         b = self.collect()
         stats = self.update(b)
@@ -222,6 +368,6 @@ class PPO:
 
     def close(self):
         self.actor.attach_action_noise(None)
-        for o in (self.actor, self.critic, self.noise, self.obs_stats):
+        for o in (self.actor, self.critic, self.noise, self.obs_stats, self.grad):
             if o is not None:
                 o.close()

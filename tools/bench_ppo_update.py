@@ -1,0 +1,186 @@
+#!/usr/bin/env python3
+"""The PPO update's gradient: torch autograd beside pbg_ppo_grad.
+
+Two legs compute one minibatch's gradient from the same data, eager launches as the trainer issues them:
+
+  torch  the body of PPO.update from the gather to loss.backward() (ppo.py's torch path)
+  hip    PPOGrad.run: the tile kernel and the reduction (plus the two torch reductions that form adv_norm)
+
+at three shapes: the pendulum trainer's (5, 64, 64, 1) with 2,048 rows of 8,192, Ant's (28, 64, 64, 8) with
+131,072 rows of 524,288, and (44, 256, 256, 17) with 16,384 rows of 65,536.  Then one whole PPO.iterate() of the
+pendulum trainer (256 envs x 32 steps, 4 epochs x 4 minibatches) in both modes.  Section 11's protocol: warm-up,
+five windows bracketed by device events (iterate: a host clock around a synchronise), the legs alternated per
+window, medians with [min, max].  The FLOP count is the algorithm's: per row and network 2 K H for each layer's
+forward, 2 K H for its weight gradient and 2 K H for the input gradient of layers two and three.
+
+  python tools/bench_ppo_update.py [--out profiles/ppo_grad.json]
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import math
+import os
+import statistics
+import sys
+import time
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+
+SHAPES = {"pendulum": ((5, 64, 64, 1), 8192, 2048), "ant": ((28, 64, 64, 8), 524288, 131072),
+          "wide": ((44, 256, 256, 17), 65536, 16384)}
+PEAK_FP32_TF = 157.0
+CLIP, VF_COEF, ENT_COEF = 0.2, 0.5, 0.0
+
+
+def flops_per_row(dims):
+    o, h1, h2, a = dims
+    total = 0
+    for out in (a, 1):
+        layers = (o * h1, h1 * h2, h2 * out)
+        total += 2 * sum(layers) * 2 + 2 * (layers[1] + layers[2])
+    return total
+
+
+def torch_gradient(theta_a, theta_c, log_std, dims, obs, act, logp_old, adv, ret, idx):
+    """ppo.py's torch path for one minibatch."""
+    import torch
+    from pybulletgym_amd.ppo import mlp_forward
+    A = dims[3]
+    a_mb = adv[idx]
+    a_mb = (a_mb - a_mb.mean()) / (a_mb.std() + 1e-8)
+    mu = mlp_forward(theta_a, dims, obs[idx], None)
+    v = mlp_forward(theta_c, dims[:3] + (1,), obs[idx], None).squeeze(1)
+    z = (act[idx] - mu) * torch.exp(-log_std)
+    logp = -0.5 * (z * z).sum(1) - log_std.sum() - 0.5 * A * math.log(2.0 * math.pi)
+    ratio = torch.exp(logp - logp_old[idx])
+    pg = -torch.min(ratio * a_mb, torch.clamp(ratio, 1.0 - CLIP, 1.0 + CLIP) * a_mb).mean()
+    vf = 0.5 * ((v - ret[idx]) ** 2).mean()
+    entropy = log_std.sum() + 0.5 * A * (1.0 + math.log(2.0 * math.pi))
+    loss = pg + VF_COEF * vf - ENT_COEF * entropy
+    for p in (theta_a, theta_c, log_std):
+        p.grad = None
+    loss.backward()
+
+
+def bench_shape(name, dims, B, Bm, args, dev):
+    import torch
+    from pybulletgym_amd.policy import MLPPopulation
+    from pybulletgym_amd.ppo import PPOGrad, mlp_forward
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(0)
+    rnd = lambda *s: torch.randn(s, device=dev, generator=gen)  # noqa: E731
+    cd = dims[:3] + (1,)
+    pa, pc = MLPPopulation(dims, 1, dev), MLPPopulation(cd, 1, dev)
+    theta_a, theta_c = torch.nn.Parameter(pa.init_theta(0)), torch.nn.Parameter(pc.init_theta(1))
+    pa.close()
+    pc.close()
+    log_std = torch.nn.Parameter(torch.full((dims[3],), -0.5, device=dev))
+    obs = rnd(B, dims[0])
+    with torch.no_grad():
+        mu = mlp_forward(theta_a, dims, obs)
+        eps = rnd(B, dims[3])
+        act = (mu + math.exp(-0.5) * eps).contiguous()
+        logp_old = (-0.5 * (eps * eps).sum(1) + 0.5 * dims[3] - 0.5 * dims[3] * math.log(2.0 * math.pi) + 0.15 * rnd(B)).contiguous()
+        ret = (mlp_forward(theta_c, cd, obs).squeeze(1) + rnd(B)).contiguous()
+    adv = rnd(B)
+    idx = torch.randperm(B, device=dev, generator=gen)[:Bm].contiguous()
+    g = PPOGrad(dims, Bm, dev)
+    ga, gc, gl = torch.zeros_like(theta_a.data), torch.zeros_like(theta_c.data), torch.zeros_like(log_std.data)
+    stats = torch.zeros(4, dtype=torch.float64, device=dev)
+
+    def hip():
+        a_mb = adv[idx]
+        adv_norm = torch.stack((a_mb.mean(), 1.0 / (a_mb.std() + 1e-8)))
+        g.run(theta_a.data, theta_c.data, log_std.data, obs, act, logp_old, adv, ret, idx=idx, adv_norm=adv_norm, clip_eps=CLIP,
+              vf_coef=VF_COEF, ent_coef=ENT_COEF, grad_actor=ga, grad_critic=gc, grad_log_std=gl, stats=stats)
+
+    legs = {"torch": lambda: torch_gradient(theta_a, theta_c, log_std, dims, obs, act, logp_old, adv, ret, idx), "hip": hip}
+    for _ in range(args.warmup):
+        for f in legs.values():
+            f()
+    torch.cuda.synchronize(dev)
+    diff = max(float((x - p.grad).abs().max() / p.grad.abs().max()) for x, p in ((ga, theta_a), (gc, theta_c), (gl, log_std)))
+    stream = torch.cuda.current_stream(dev)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    w = {leg: [] for leg in legs}
+    for _ in range(args.windows):
+        for leg, f in legs.items():
+            torch.cuda.synchronize(dev)
+            e0.record(stream)
+            for _ in range(args.calls):
+                f()
+            e1.record(stream)
+            torch.cuda.synchronize(dev)
+            w[leg].append(e0.elapsed_time(e1) * 1e3 / args.calls)
+    g.close()
+    med = {k: statistics.median(v) for k, v in w.items()}
+    fl = flops_per_row(dims) * Bm
+    return {"dims": dims, "batch_rows": B, "minibatch_rows": Bm, "unit": "us per minibatch gradient", "windows": w, "median": med,
+            "min": {k: min(v) for k, v in w.items()}, "max": {k: max(v) for k, v in w.items()},
+            "torch_over_hip": med["torch"] / med["hip"], "flops_per_minibatch": fl,
+            "achieved_TFLOPs": {k: fl / (us * 1e-6) / 1e12 for k, us in med.items()},
+            "share_of_fp32_peak": {k: fl / (us * 1e-6) / 1e12 / PEAK_FP32_TF for k, us in med.items()},
+            "max_relative_difference_of_the_gradients": diff, "calls_per_window": args.calls}
+
+
+def bench_iterate(args, dev):
+    import torch
+    from pybulletgym_amd.ppo import PPO
+    from pybulletgym_amd.vec_env import VecEnv
+    hp = dict(hidden=(64, 64), steps=32, lr=3e-3, epochs=4, minibatches=4, log_std=-0.5)
+    tr = {}
+    for mode in ("torch", "hip"):
+        env = VecEnv("InvertedPendulumPyBulletEnv-v0", 256, device=dev, seed=0, autoreset=True, precision=64)
+        tr[mode] = (env, PPO(env, seed=0, backward=mode, **hp))
+        for _ in range(3):
+            tr[mode][1].iterate()
+    w = {mode: [] for mode in tr}
+    for _ in range(args.windows):
+        for mode, (_, ppo) in tr.items():
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+            for _ in range(args.iterations):
+                ppo.iterate()
+            torch.cuda.synchronize(dev)
+            w[mode].append((time.perf_counter() - t0) * 1e3 / args.iterations)
+    for env, ppo in tr.values():
+        ppo.close()
+        env.close()
+    med = {k: statistics.median(v) for k, v in w.items()}
+    return {"trainer": dict(hp, env_id="InvertedPendulumPyBulletEnv-v0", envs=256), "unit": "ms per PPO.iterate()", "windows": w,
+            "median": med, "min": {k: min(v) for k, v in w.items()}, "max": {k: max(v) for k, v in w.items()},
+            "torch_over_hip": med["torch"] / med["hip"], "iterations_per_window": args.iterations}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "ppo_grad.json"))
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--windows", type=int, default=5)
+    ap.add_argument("--calls", type=int, default=20, help="gradient calls per timed window")
+    ap.add_argument("--iterations", type=int, default=5, help="PPO.iterate() calls per timed window")
+    ap.add_argument("--shapes", nargs="*", default=list(SHAPES))
+    args = ap.parse_args()
+    import torch
+    import pybulletgym_amd  # noqa: F401
+    dev = torch.device("cuda:0")
+    res = {"peak_fp32_TFLOPs": PEAK_FP32_TF, "shapes": {}}
+    for name in args.shapes:
+        res["shapes"][name] = r = bench_shape(name, *SHAPES[name], args, dev)
+        print(f"{name} {r['dims']} x {r['minibatch_rows']}: us median [min, max]  " + "  ".join(
+            f"{k} {r['median'][k]:.1f} [{r['min'][k]:.1f}, {r['max'][k]:.1f}] ({r['achieved_TFLOPs'][k]:.2f} TF)"
+            for k in r["median"]) + f"  torch / hip {r['torch_over_hip']:.2f}  grad diff {r['max_relative_difference_of_the_gradients']:.1e}")
+    res["iterate"] = r = bench_iterate(args, dev)
+    print("PPO.iterate() ms median [min, max]  " + "  ".join(
+        f"{k} {r['median'][k]:.2f} [{r['min'][k]:.2f}, {r['max'][k]:.2f}]" for k in r["median"]) +
+        f"  torch / hip {r['torch_over_hip']:.2f}")
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps({"done": True, "out": args.out}))
+
+
+if __name__ == "__main__":
+    main()

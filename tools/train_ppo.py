@@ -47,6 +47,8 @@ def main():
     ap.add_argument("--out", default="ppo_policy.npz")
     ap.add_argument("--obs-norm", action="store_true", help="running observation normalisation")
     ap.add_argument("--obs-clip", type=float, default=5.0)
+    ap.add_argument("--backward", choices=("torch", "hip"), default="torch",
+                    help="the update's gradient: torch autograd, or the HIP backward pass (pbg_ppo_grad)")
     ap.add_argument("--curve", default=None, help="write the per-iteration evaluation here (JSON)")
     args = ap.parse_args()
 
@@ -61,10 +63,10 @@ def main():
     test = VecEnv(args.env_id, args.eval_envs, device="cuda:0", seed=args.seed + 1, autoreset=False, precision=args.precision)
     ppo = PPO(env, hidden=args.hidden, steps=args.steps, seed=args.seed, gamma=args.gamma, lam=args.lam, clip=args.clip,
               lr=args.lr, epochs=args.epochs, minibatches=args.minibatches, vf_coef=args.vf_coef, ent_coef=args.ent_coef,
-              log_std=args.log_std, obs_norm=args.obs_norm, obs_clip=args.obs_clip)
+              log_std=args.log_std, obs_norm=args.obs_norm, obs_clip=args.obs_clip, backward=args.backward)
     print(f"{args.env_id} (float{args.precision}): {args.envs} envs x {args.steps} steps per iteration, actor MLP "
           f"{ppo.actor_dims}, lr {args.lr}, {args.epochs} epochs x {args.minibatches} minibatches, observation "
-          f"normalisation {'on' if args.obs_norm else 'off'}")
+          f"normalisation {'on' if args.obs_norm else 'off'}, backward pass {args.backward}")
     curve = []
 
     def report(it):
