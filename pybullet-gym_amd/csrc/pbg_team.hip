@@ -1371,12 +1371,22 @@ PBG_DEV void team_gather(const TState<R>& s, const Lane& L, const TRows<R, ES>& 
   }
 }
 
+// team_reset writes the bare noise into the reset dofs: right only while every robot it is built for has
+// zero reset offsets (pbg_step.hip reset_env_epi adds R::reset_offset, as a robot like the swingup needs)
+template <class R>
+constexpr bool reset_offsets_zero() {
+  for (int r = 0; r < R::NR; r++)
+    if (R::reset_offset[r] != 0.0) return false;
+  return true;
+}
+
 // snapshot + Philox reset noise (pbg_step.hip reset_env); returns the reset pack
 template <class R, int ES>
 PBG_DEV void team_reset(const Buffers& B, int e, const Lane& L, TState<R>& s, const TRows<R, ES>& rw, float* obs,
                         bool& has_floor, double& pot, real_t<R>& z0) {
   using T = Team<R>;
   using Sc = real_t<R>;
+  static_assert(reset_offsets_zero<R>(), "team_reset drops R::reset_offset: add it before a quad robot has one");
 #pragma unroll
   for (int i = 0; i < 3; i++) s.bp[i] = (Sc)R::base_pos[i];
 #pragma unroll
