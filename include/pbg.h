@@ -620,6 +620,110 @@ void pbg_ppo_grad_destroy(pbg_ppo_grad* g);
 int pbg_ppo_grad_run(pbg_ppo_grad* g, const pbg_ppo_grad_io_t* io, void* stream);
 int pbg_ppo_grad_host(int obs_dim, int h1, int h2, int act_dim, const pbg_ppo_grad_io_t* io);
 
+/* ---- PPO optimiser step (appended; nothing above changes) ----
+ * What a PPO minibatch step does besides the gradient: the advantage normaliser's (shift, scale) pair, and Adam
+ * (Kingma & Ba 2015) with global-norm gradient clipping.  All arithmetic below is IEEE float64 add, multiply,
+ * divide and square root in the stated order, nothing contracted, so each host twin gives its device function's
+ * bits.  No atomics and no cooperative launch anywhere: every call is a function of its inputs and of the object's
+ * state alone, the same bits on every stream and inside a replayed graph.
+ *
+ * pbg_adv_norm: out (DEVICE float32 [2]) = (shift, scale), the pair pbg_ppo_grad_io_t.adv_norm consumes, of the
+ * Bm = n_rows advantages a_i = adv[idx[i]] (adv DEVICE float32 [B], B = n_batch; idx DEVICE int64 [Bm], nullable:
+ * rows 0 .. Bm - 1; NOT validated on the device, every index must lie in 0 .. B - 1).  One launch of one workgroup
+ * of 1,024 lanes, no workspace:
+ *   c0 = a_0, the minibatch's first advantage;  d_i = a_i - c0   (both widened to float64 first; one subtraction)
+ *   lane l:   s1_l = sum of d_i, s2_l = sum of d_i * d_i over i = l, l + 1024, l + 2048, ... ascending from 0.0
+ *             (the product rounded, then the add: never fused)
+ *   the tree: for s = 512, 256, ..., 1:  x_l += x_(l + s) for every l < s;  S1, S2 = lane 0's s1, s2
+ *   ms   = S1 / Bm;  mean = c0 + ms
+ *   var  = (S2 - S1 * ms) / (Bm - 1);  var < 0 becomes 0 (Bessel's correction, Tensor.std(); a NaN stays NaN)
+ *   out  = ((float)mean, (float)(1 / (sqrt(var) + 1e-8)))
+ * The sums are taken of the advantages less the first one because the unshifted S2 = sum a_i^2 outgrows 53 bits
+ * from some 32 equal rows on and S2 - S1 * mean then keeps a rounding residue of a few ulp(S2): 1,537 rows of
+ * 6836.862 gave a scale of 10,032 instead of 1e8.  Shifted, constant advantages have every d_i = 0, so S1 = S2 = 0,
+ * mean = c0 and var = 0 exactly, scale = 1e8 and (a_i - shift) * scale = 0 for every row, whatever Bm and the value;
+ * and in general the cancellation in S2 - S1 * ms is of the spread against the distance of the mean from a_0, not
+ * against the mean itself.  PBG_E_ARG (before any HIP call) for
+ * n_rows < 2, n_batch < 1, n_rows > n_batch with idx NULL, adv or out NULL.  pbg_adv_norm_host: the same on HOST
+ * pointers with no GPU, the same bits; it validates the indices (PBG_E_ARG). */
+int pbg_adv_norm(int n_batch, int n_rows, const float* adv, const int64_t* idx, float* out, void* stream);
+int pbg_adv_norm_host(int n_batch, int n_rows, const float* adv, const int64_t* idx, float* out);
+
+/* pbg_ppo_opt: Adam with global-norm clipping over n_blocks (1 .. 8) flat float32 blocks of sizes[b] >= 1 elements.
+ * The object owns, on its device, the moments m and v (float32, zero at creation), the workspace of launch 1 and
+ * one state word: the step count t (uint32, 0) and the float64 running products b1t = beta1^t and b2t = beta2^t
+ * (1), advanced by one multiplication per step, never by pow.  Because the state lives on the device a captured
+ * step replayed twice equals two eager steps.
+ *
+ * One step, with g, p, m, v a block's gradient, parameter and moments:
+ *   t += 1;  b1t *= beta1;  b2t *= beta2
+ *   norm = sqrt(sum of g * g over all blocks)                 (the order of the adds: below)
+ *   coef = max_grad_norm > 0 ? min(1, max_grad_norm / (norm + 1e-6)) : 1        (clip_grad_norm_'s expression)
+ *   c1 = lr / (1 - b1t);  c2 = sqrt(1 - b2t)                  (the products after this step's multiplication)
+ *   per element:
+ *     gd = g * coef
+ *     md = beta1 * m + (1 - beta1) * gd
+ *     vd = beta2 * v + (1 - beta2) * (gd * gd)
+ *     p  = (float)(p - c1 * (md / (sqrt(vd) / c2 + eps)))     (the UNROUNDED md and vd enter p)
+ *     m  = (float)md;  v = (float)vd
+ * g, p, m, v are widened to float64 first; 1 - beta1 and 1 - beta2 are formed once in float64.  A non-finite norm
+ * propagates as in torch.  With clipping (max_grad_norm > 0) a NaN norm makes coef NaN and with it every parameter, m
+ * and v of every block; an infinite norm makes coef 0, every element whose gradient is infinite NaN (inf * 0) and
+ * gd = 0 for the others, which then move by their old moments alone.  Without clipping coef is 1 and only the
+ * elements whose own gradient is not finite become NaN.  A block whose gradient is all zero keeps its parameters.
+ *
+ * The order of the adds of the norm.  Block b has G_b = min(ceil(ceil(sizes[b] / 4) / 256), 64) workgroups of 256
+ * lanes.  Lane l of the block's workgroup w owns the groups of four consecutive elements q = w * 256 + l + k *
+ * (256 G_b), k = 0, 1, ..., that is the elements 4 q .. 4 q + 3 below sizes[b]; it adds their squares (exact in
+ * float64) in ascending element order onto 0.0.  The workgroup's 256 lane sums are added by the tree of
+ * pbg_adv_norm (s = 128, 64, ..., 1) into the workgroup's partial.  Launch 1 stores the partials in the order
+ * (block ascending, w ascending); launch 2 adds them in that order onto 0.0 in every workgroup.
+ *
+ * pbg_ppo_opt_step is two launches on `stream`, no host work, no synchronisation: it captures as a plain chain.
+ * Launch 1 writes the partials and one of its lanes advances the state word, which that launch reads nowhere
+ * else; launch 2 reads the advanced word, re-adds the partials and updates its elements in the geometry above.  The
+ * parameters are updated where they lie.  Blocks whose param and grad pointers are both 16-byte aligned are
+ * accessed as float4, the others element by element; the arithmetic and its order are the same.  Two steps of one
+ * object must not overlap on the device. */
+#define PBG_PPO_OPT_MAX_BLOCKS 8
+typedef struct pbg_ppo_opt pbg_ppo_opt;
+
+/* Pointers: DEVICE memory of the object's GPU (pbg_ppo_opt_step) or HOST memory (pbg_ppo_opt_host); entries at and
+ * after n_blocks are ignored.  Versioned by struct_size like pbg_ppo_grad_io_t: PBG_E_ARG for a size below the first
+ * version's (which ends with bpow), above the library's, or not a multiple of 4. */
+typedef struct {
+  uint32_t struct_size;
+  int reserved;                                /* 0 */
+  float* param[PBG_PPO_OPT_MAX_BLOCKS];        /* [sizes[b]] in/out, updated in place */
+  const float* grad[PBG_PPO_OPT_MAX_BLOCKS];   /* [sizes[b]] */
+  double lr;
+  double beta1, beta2;                         /* each in [0, 1) */
+  double eps;                                  /* > 0 */
+  double max_grad_norm;                        /* <= 0: no clipping (coef = 1) */
+  double* info;                                /* [2] out, nullable: norm, coef */
+  /* the state as HOST arrays, pbg_ppo_opt_host only (pbg_ppo_opt_step ignores them: the object holds its own) */
+  float* m[PBG_PPO_OPT_MAX_BLOCKS];            /* [sizes[b]] in/out */
+  float* v[PBG_PPO_OPT_MAX_BLOCKS];            /* [sizes[b]] in/out */
+  uint32_t* t;                                 /* [1] in/out */
+  double* bpow;                                /* [2] in/out: b1t, b2t (1, 1 before the first step) */
+} pbg_ppo_opt_io_t;
+
+/* PBG_E_ARG (before any HIP call) for n_blocks outside 1 .. 8, a size < 1, sizes or out NULL, device < 0; PBG_E_HIP
+ * for a device that does not exist.  *out is NULL after every failure. */
+int pbg_ppo_opt_create(int device, int n_blocks, const int64_t* sizes, pbg_ppo_opt** out);
+void pbg_ppo_opt_destroy(pbg_ppo_opt* opt);
+/* PBG_E_ARG (before any HIP call) for a NULL object or io, a bad struct_size, a NULL param or grad of a block below
+ * n_blocks, a beta outside [0, 1), eps <= 0 (NaNs included). */
+int pbg_ppo_opt_step(pbg_ppo_opt* opt, const pbg_ppo_opt_io_t* io, void* stream);
+/* m = v = 0, t = 0, b1t = b2t = 1, on `stream`. */
+int pbg_ppo_opt_reset(pbg_ppo_opt* opt, void* stream);
+/* Copies on `stream` to DEVICE arrays, each nullable: m_out, v_out float32 [sum of sizes], the blocks concatenated in
+ * order; t_out uint32 [1]. */
+int pbg_ppo_opt_get_state(const pbg_ppo_opt* opt, float* m_out, float* v_out, uint32_t* t_out, void* stream);
+/* One step on HOST pointers with no GPU: the same sums in the same order and the same element function, the same
+ * bits.  Further PBG_E_ARG: n_blocks or sizes as in create; a NULL m or v of a block; t or bpow NULL. */
+int pbg_ppo_opt_host(int n_blocks, const int64_t* sizes, const pbg_ppo_opt_io_t* io);
+
 #ifdef __cplusplus
 }
 #endif

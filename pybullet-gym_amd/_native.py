@@ -88,6 +88,27 @@ class PPOGradIO(ctypes.Structure):
         super().__init__(struct_size=ctypes.sizeof(PPOGradIO), **kw)
 
 
+PPO_OPT_MAX_BLOCKS = 8  # PBG_PPO_OPT_MAX_BLOCKS
+
+
+class PPOOptIO(ctypes.Structure):
+    """pbg_ppo_opt_io_t (pbg_ppo_opt_step, pbg_ppo_opt_host): versioned by struct_size; m, v, t, bpow: the host
+    twin's state."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("reserved", ctypes.c_int),
+                ("param", ctypes.c_void_p * PPO_OPT_MAX_BLOCKS), ("grad", ctypes.c_void_p * PPO_OPT_MAX_BLOCKS),
+                ("lr", ctypes.c_double), ("beta1", ctypes.c_double), ("beta2", ctypes.c_double),
+                ("eps", ctypes.c_double), ("max_grad_norm", ctypes.c_double), ("info", ctypes.c_void_p),
+                ("m", ctypes.c_void_p * PPO_OPT_MAX_BLOCKS), ("v", ctypes.c_void_p * PPO_OPT_MAX_BLOCKS),
+                ("t", ctypes.c_void_p), ("bpow", ctypes.c_void_p)]
+
+    def __init__(self, **kw):
+        arrays = {k: kw.pop(k) for k in ("param", "grad", "m", "v") if k in kw}
+        super().__init__(struct_size=ctypes.sizeof(PPOOptIO), **kw)
+        for k, ptrs in arrays.items():
+            for b, p in enumerate(ptrs):
+                getattr(self, k)[b] = p
+
+
 POLICY_MAX_DIM = 256  # PBG_POLICY_MAX_DIM: obs_dim, h1, h2
 POLICY_MAX_ACT = 64   # PBG_POLICY_MAX_ACT
 
@@ -200,6 +221,20 @@ def lib():
         for f in PPO_GRAD_EXPORTED:
             if f != "pbg_ppo_grad_destroy":
                 getattr(L, f).restype = I
+    if hasattr(L, "pbg_ppo_opt_create"):  # the advantage normaliser and the clip + Adam step
+        I64P = ctypes.POINTER(ctypes.c_int64)
+        L.pbg_adv_norm.argtypes = [I, I, P, P, P, P]
+        L.pbg_adv_norm_host.argtypes = [I, I, P, P, P]
+        L.pbg_ppo_opt_create.argtypes = [I, I, I64P, ctypes.POINTER(H)]
+        L.pbg_ppo_opt_destroy.argtypes = [H]
+        L.pbg_ppo_opt_destroy.restype = None
+        L.pbg_ppo_opt_step.argtypes = [H, ctypes.POINTER(PPOOptIO), P]
+        L.pbg_ppo_opt_reset.argtypes = [H, P]
+        L.pbg_ppo_opt_get_state.argtypes = [H, P, P, P, P]
+        L.pbg_ppo_opt_host.argtypes = [I, I64P, ctypes.POINTER(PPOOptIO)]
+        for f in PPO_OPT_EXPORTED:
+            if f != "pbg_ppo_opt_destroy":
+                getattr(L, f).restype = I
     for f in ("pbg_info", "pbg_reset", "pbg_step", "pbg_step_ex", "pbg_get_state", "pbg_set_state",
               "pbg_pack_record_sizes", "pbg_pack", "pbg_create_debug", "pbg_sample_actions", "pbg_create_ex",
               "pbg_default_sim_params", "pbg_get_sim_params", "pbg_create_v2", "pbg_precision"):
@@ -221,12 +256,14 @@ ACTION_NOISE_EXPORTED = ("pbg_action_noise_create", "pbg_action_noise_destroy", 
                          "pbg_action_noise_fill", "pbg_action_noise_host", "pbg_policy_attach_action_noise",
                          "pbg_population_attach_action_noise", "pbg_gae", "pbg_gae_host")
 PPO_GRAD_EXPORTED = ("pbg_ppo_grad_create", "pbg_ppo_grad_destroy", "pbg_ppo_grad_run", "pbg_ppo_grad_host")
+PPO_OPT_EXPORTED = ("pbg_adv_norm", "pbg_adv_norm_host", "pbg_ppo_opt_create", "pbg_ppo_opt_destroy", "pbg_ppo_opt_step",
+                    "pbg_ppo_opt_reset", "pbg_ppo_opt_get_state", "pbg_ppo_opt_host")
 EXPORTED = ("pbg_create", "pbg_create_debug", "pbg_create_ex", "pbg_create_v2", "pbg_precision",
             "pbg_default_sim_params", "pbg_get_sim_params",
             "pbg_destroy", "pbg_info", "pbg_reset", "pbg_step", "pbg_step_ex",
             "pbg_get_state", "pbg_set_state", "pbg_pack_record_sizes", "pbg_pack", "pbg_sample_actions",
             "pbg_debug_poison", "pbg_last_error") + POLICY_EXPORTED + POPULATION_EXPORTED + OBS_NORM_EXPORTED + \
-    ACTION_NOISE_EXPORTED + PPO_GRAD_EXPORTED
+    ACTION_NOISE_EXPORTED + PPO_GRAD_EXPORTED + PPO_OPT_EXPORTED
 
 
 def check(rc: int, what: str):

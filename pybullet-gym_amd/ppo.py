@@ -6,7 +6,9 @@ inside the actor launch and records ``sum eps^2`` for the log-probability (inclu
 actions"), the critic's values are one ``MLPPopulation.act`` over the whole trajectory, and ``gae`` is one
 launch (pbg_gae).  The backward pass is torch autograd by default (``PPO(backward="torch")``); with
 ``backward="hip"`` each minibatch's gradient is ``PPOGrad.run``: two launches (pbg_ppo_grad, include/pbg.h "PPO
-gradient").  The collection half of an iteration has no host work between its launches."""
+gradient"), and with ``optimizer="hip"`` the advantage normaliser, the gradient clipping and Adam are ``adv_norm`` and
+``AdamClip`` (pbg_adv_norm, pbg_ppo_opt, include/pbg.h "PPO optimiser step"): three more launches, optionally
+the whole update as one captured graph.  The collection half of an iteration has no host work between its launches."""
 from __future__ import annotations
 
 import ctypes
@@ -179,6 +181,151 @@ class PPOGrad:
             pass
 
 
+def _need_opt():
+    if not hasattr(_native.lib(), "pbg_ppo_opt_create"):
+        raise _native.PbgError(f"{_native.LIB_PATH} has no pbg_ppo_opt_create: a build without the PPO optimiser step")
+    return _native.lib()
+
+
+def adv_norm(adv, idx=None, out=None):
+    """``out``, float32 ``[2]``: the ``(shift, scale) = (mean, 1 / (std + 1e-8))`` pair of the advantages ``adv[idx]``
+    (``adv`` float32 ``[B]``; ``idx`` int64 ``[Bm]``, ``None``: all of ``adv``; Bessel's correction, ``Tensor.std()``)
+    that ``PPOGrad.run`` takes as ``adv_norm``: pbg_adv_norm, one launch, float64 sums in the order include/pbg.h
+    states.  Contiguous tensors on one GPU run the launch (the indices are not validated there); numpy arrays run
+    the same sums on the host (pbg_adv_norm_host, the same bits, the indices validated)."""
+    L = _need_opt()
+    host = isinstance(adv, np.ndarray)
+    f32, i64 = (np.float32, np.int64) if host else (torch.float32, torch.int64)
+    if getattr(adv, "ndim", 0) != 1:
+        raise _native.PbgError("adv_norm: adv must be a float32 [B] array or GPU tensor")
+    B = int(adv.shape[0])
+    Bm = int(idx.shape[0]) if idx is not None and getattr(idx, "ndim", 0) == 1 else B
+    if out is None:
+        out = np.empty(2, np.float32) if host else torch.empty(2, dtype=torch.float32, device=adv.device)
+    for name, t, shape, dt in (("adv", adv, (B,), f32), ("idx", idx, (Bm,), i64), ("out", out, (2,), f32)):
+        if t is None and name == "idx":
+            continue
+        ok = isinstance(t, np.ndarray) and t.flags.c_contiguous if host else \
+            isinstance(t, torch.Tensor) and t.is_contiguous() and t.is_cuda and t.device == adv.device
+        if not ok or tuple(t.shape) != shape or t.dtype != dt:
+            raise _native.PbgError(f"adv_norm: {name} must be a contiguous {dt} {'array' if host else 'GPU tensor'} of shape "
+                                   f"{shape}, all on one device")
+    if host:
+        _native.check(L.pbg_adv_norm_host(B, Bm, adv.ctypes.data, None if idx is None else idx.ctypes.data, out.ctypes.data),
+                      "pbg_adv_norm_host")
+        return out
+    with torch.cuda.device(adv.device):
+        stream = ctypes.c_void_p(torch.cuda.current_stream(adv.device).cuda_stream)
+        _native.check(L.pbg_adv_norm(B, Bm, adv.data_ptr(), None if idx is None else idx.data_ptr(), out.data_ptr(), stream),
+                      "pbg_adv_norm")
+    return out
+
+
+class AdamClip:
+    """Adam with global-norm gradient clipping over up to 8 flat float32 blocks as two HIP launches (include/pbg.h
+    "PPO optimiser step", pbg_ppo_opt).  ``sizes``: the blocks' element counts.  ``device``: a GPU, whose object then
+    owns the moments, the step count and the running powers of the betas on the device (so a captured step that is
+    replayed advances like an eager one), or ``None`` / ``"cpu"`` for the host twin (pbg_ppo_opt_host: numpy arrays,
+    no GPU, the state kept here as numpy arrays; the same bits)."""
+
+    def __init__(self, sizes, device=None):
+        L = _need_opt()
+        self.sizes = tuple(int(s) for s in sizes)
+        if not 1 <= len(self.sizes) <= _native.PPO_OPT_MAX_BLOCKS or min(self.sizes) < 1:
+            raise _native.PbgError(f"AdamClip: 1 .. {_native.PPO_OPT_MAX_BLOCKS} blocks of at least one element, got {sizes!r}")
+        self._sizes = (ctypes.c_int64 * len(self.sizes))(*self.sizes)
+        self.host = device is None or str(device) == "cpu"
+        self.device = None if self.host else torch.device(device)
+        self._h = ctypes.c_void_p()
+        if self.host:
+            self.reset()
+            return
+        if self.device.type != "cuda":
+            raise _native.PbgError(f"AdamClip: device must be a GPU or None, got {device!r}")
+        index = self.device.index if self.device.index is not None else torch.cuda.current_device()
+        self.device = torch.device("cuda", index)
+        _native.check(L.pbg_ppo_opt_create(index, len(self.sizes), self._sizes, ctypes.byref(self._h)), "pbg_ppo_opt_create")
+
+    def _stream(self):
+        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _open(self, what):
+        if not self.host and not self._h:
+            raise _native.PbgError(f"AdamClip.{what}: the object is closed")
+
+    def step(self, params, grads, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, max_grad_norm: float = 0.0, info=None):
+        """One step on ``params`` (updated in place) with ``grads``: sequences of contiguous float32 ``[sizes[b]]``
+        tensors on the object's GPU (numpy arrays on the host).  ``max_grad_norm`` 0 (or None): no clipping.  ``info``:
+        optional float64 ``[2]`` that receives the gradient's global norm and the clipping coefficient.  ``lr`` and
+        the other scalars are launch arguments: a captured step keeps the values it was captured with, so a
+        learning-rate schedule needs a new capture."""
+        self._open("step")
+        f32, f64 = (np.float32, np.float64) if self.host else (torch.float32, torch.float64)
+        params, grads = list(params), list(grads)
+        if len(params) != len(self.sizes) or len(grads) != len(self.sizes):
+            raise _native.PbgError(f"AdamClip.step: {len(self.sizes)} blocks expected, got {len(params)} params and "
+                                   f"{len(grads)} grads")
+        checks = [(f"params[{b}]", t, (s,), f32) for b, (t, s) in enumerate(zip(params, self.sizes))]
+        checks += [(f"grads[{b}]", t, (s,), f32) for b, (t, s) in enumerate(zip(grads, self.sizes))]
+        if info is not None:
+            checks.append(("info", info, (2,), f64))
+        for name, t, shape, dt in checks:
+            ok = isinstance(t, np.ndarray) and t.flags.c_contiguous if self.host else \
+                isinstance(t, torch.Tensor) and t.is_contiguous() and t.device == self.device
+            if not ok or tuple(t.shape) != shape or t.dtype != dt:
+                raise _native.PbgError(f"AdamClip.step: {name} must be a contiguous {dt} "
+                                       f"{'array' if self.host else f'tensor on {self.device}'} of shape {shape}")
+        ptr = (lambda t: t.ctypes.data) if self.host else (lambda t: t.data_ptr())
+        kw = dict(param=[ptr(t) for t in params], grad=[ptr(t) for t in grads], lr=float(lr), beta1=float(betas[0]),
+                  beta2=float(betas[1]), eps=float(eps), max_grad_norm=float(max_grad_norm or 0.0),
+                  info=None if info is None else ptr(info))
+        if self.host:
+            io = _native.PPOOptIO(m=[ptr(t) for t in self._m], v=[ptr(t) for t in self._v], t=self._t.ctypes.data,
+                                  bpow=self._bpow.ctypes.data, **kw)
+            _native.check(_native.lib().pbg_ppo_opt_host(len(self.sizes), self._sizes, ctypes.byref(io)), "pbg_ppo_opt_host")
+            return
+        io = _native.PPOOptIO(**kw)
+        with torch.cuda.device(self.device):
+            _native.check(_native.lib().pbg_ppo_opt_step(self._h, ctypes.byref(io), self._stream()), "pbg_ppo_opt_step")
+
+    def reset(self):
+        """Zero moments, step count 0 (stream order on a GPU)."""
+        if self.host:
+            self._m = [np.zeros(s, np.float32) for s in self.sizes]
+            self._v = [np.zeros(s, np.float32) for s in self.sizes]
+            self._t, self._bpow = np.zeros(1, np.uint32), np.ones(2, np.float64)
+            return
+        self._open("reset")
+        with torch.cuda.device(self.device):
+            _native.check(_native.lib().pbg_ppo_opt_reset(self._h, self._stream()), "pbg_ppo_opt_reset")
+
+    def state(self):
+        """``(m, v, t)``: the two moments as lists of float32 ``[sizes[b]]`` and the step count (``[1]``: int32 bits of
+        the uint32 on a GPU, uint32 on the host): fresh device tensors, copied on the stream (copies of the numpy state on
+        the host)."""
+        if self.host:
+            return [a.copy() for a in self._m], [a.copy() for a in self._v], self._t.copy()
+        self._open("state")
+        n = sum(self.sizes)
+        m, v = (torch.empty(n, dtype=torch.float32, device=self.device) for _ in range(2))
+        t = torch.zeros(1, dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            _native.check(_native.lib().pbg_ppo_opt_get_state(self._h, m.data_ptr(), v.data_ptr(), t.data_ptr(), self._stream()),
+                          "pbg_ppo_opt_get_state")
+        return list(m.split(self.sizes)), list(v.split(self.sizes)), t
+
+    def close(self):
+        if self._h:
+            _native.lib().pbg_ppo_opt_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 @dataclass
 class Batch:
     """One iteration's data (views of the env's rollout buffers and this object's own): ``[T, n, ...]``."""
@@ -203,15 +350,28 @@ class PPO:
     during the rollout and finalized into both networks' normaliser after the update, which uses the normaliser
     its data was collected under.  ``backward="hip"``: every minibatch's gradient comes from ``PPOGrad.run`` (two
     launches, written straight into the parameters' ``.grad``) instead of torch autograd; the permutation, the
-    gradient clipping and Adam are the same, and ``update``'s stats gain ``clipfrac`` and ``kl``."""
+    gradient clipping and Adam are the same, and ``update``'s stats gain ``clipfrac`` and ``kl``.
+    ``optimizer="hip"`` (needs ``backward="hip"``): the advantage normaliser, the gradient clipping and Adam are the
+    library's too (``adv_norm``, ``AdamClip``: the torch path's lr, betas (0.9, 0.999), eps 1e-5 and ``max_grad_norm``), a
+    minibatch is at most five launches and no torch kernel, and the stats gain ``grad_norm``; the permutation stays
+    ``torch.randperm``.  ``graph=True`` (needs ``optimizer="hip"``): the whole ``epochs x minibatches`` chain is one
+    captured graph, replayed every iteration; ``lr`` is a launch argument, so the graph keeps the captured value (no
+    learning-rate schedule)."""
 
     def __init__(self, env, hidden=(64, 64), steps: int = 64, seed: int = 0, gamma: float = 0.99, lam: float = 0.95,
                  clip: float = 0.2, lr: float = 3e-4, epochs: int = 4, minibatches: int = 4, vf_coef: float = 0.5,
                  ent_coef: float = 0.0, log_std: float = -0.5, max_grad_norm: float = 0.5, norm_adv: bool = True,
-                 obs_norm: bool = False, obs_clip: float = 5.0, backward: str = "torch"):
+                 obs_norm: bool = False, obs_clip: float = 5.0, backward: str = "torch", optimizer: str = "torch",
+                 graph: bool = False):
         n, dev = env.num_envs, env.device
         if backward not in ("torch", "hip"):
             raise _native.PbgError(f"PPO: backward must be 'torch' or 'hip', got {backward!r}")
+        if optimizer not in ("torch", "hip"):
+            raise _native.PbgError(f"PPO: optimizer must be 'torch' or 'hip', got {optimizer!r}")
+        if optimizer == "hip" and backward != "hip":
+            raise _native.PbgError("PPO: optimizer='hip' takes its gradient from pbg_ppo_grad: it needs backward='hip'")
+        if graph and optimizer != "hip":
+            raise _native.PbgError("PPO: graph=True captures the library's launches alone: it needs optimizer='hip'")
         self.backward = backward
         if n % 2 != 0 or not env.autoreset:
             raise _native.PbgError("PPO: the env must have an even number of envs (the actors are populations of one "
@@ -234,6 +394,7 @@ class PPO:
         self.actor_theta = torch.nn.Parameter(ta)
         self.critic_theta = torch.nn.Parameter(tc)
         self.log_std = torch.nn.Parameter(torch.full((act_dim,), float(log_std), dtype=torch.float32, device=dev))
+        # with optimizer="hip" this object is built and never stepped: the moments and the step count are self.adam's
         self.opt = torch.optim.Adam([self.actor_theta, self.critic_theta, self.log_std], lr=float(lr), eps=1e-5)
         self._gen = torch.Generator(device=dev)
         self._gen.manual_seed(self.seed)
@@ -255,6 +416,20 @@ class PPO:
             for p in (self.actor_theta, self.critic_theta, self.log_std):
                 p.grad = torch.zeros_like(p.data)
             self._grad_stats = torch.zeros(4, dtype=torch.float64, device=dev)
+        self.adam = self._graph = None
+        if optimizer == "hip":
+            if norm_adv and (T * n) // self.minibatches < 2:
+                raise _native.PbgError("PPO: optimizer='hip' with norm_adv needs minibatches of at least 2 rows")
+            self._params = [self.actor_theta.data, self.critic_theta.data, self.log_std.data]
+            self._grads = [self.actor_theta.grad, self.critic_theta.grad, self.log_std.grad]
+            self.adam = AdamClip([p.numel() for p in self._params], dev)
+            self.lr, self.use_graph = float(lr), bool(graph)
+            self._adv_norm = torch.zeros(2, **kw)
+            self._opt_info = torch.zeros(2, dtype=torch.float64, device=dev)
+            if graph:
+                # what a replay reads and a new iteration must refill in place
+                self._perm = torch.zeros((self.epochs, self.minibatches, (T * n) // self.minibatches), dtype=torch.int64, device=dev)
+                self._logp_old = torch.zeros(T * n, **kw)
         env.reset()
 
     def _set_norm(self):
@@ -286,6 +461,8 @@ class PPO:
     def update(self, b: Batch) -> dict:
         """``epochs`` passes of ``minibatches`` clipped-surrogate steps over the batch (Adam; the gradient by torch
         autograd, or by pbg_ppo_grad with ``backward="hip"``)."""
+        if self.adam is not None:
+            return self._update_opt(b)
         if self.grad is not None:
             return self._update_hip(b)
         T, n = self.steps, self.env.num_envs
@@ -342,6 +519,65 @@ class PPO:
         st = self._grad_stats.clone()   # the last minibatch's
         return dict(pg=st[0], vf=st[1], clipfrac=st[2], kl=st[3])
 
+    def _minibatch_opt(self, obs, act, logp_old, adv, ret, idx):
+        """One minibatch step as at most five launches of the library: pbg_adv_norm, pbg_ppo_grad_run (two),
+        pbg_ppo_opt_step (two)."""
+        norm = adv_norm(adv, idx, out=self._adv_norm) if self.norm_adv else None
+        self.grad.run(self._params[0], self._params[1], self._params[2], obs, act, logp_old, adv, ret, idx=idx, adv_norm=norm,
+                      obs_norm=self.actor.obs_norm, clip_eps=self.clip, vf_coef=self.vf_coef, ent_coef=self.ent_coef,
+                      grad_actor=self._grads[0], grad_critic=self._grads[1], grad_log_std=self._grads[2],
+                      stats=self._grad_stats)
+        self.adam.step(self._params, self._grads, self.lr, (0.9, 0.999), 1e-5, self.max_grad_norm, info=self._opt_info)
+
+    def _update_opt(self, b: Batch) -> dict:
+        """``update`` with ``optimizer="hip"``: the permutations are ``_update_hip``'s (the same generator), every
+        minibatch is ``_minibatch_opt``.  With ``graph=True`` the ``epochs x minibatches`` chain is captured at the
+        first call and replayed from then on: the permutations and ``logp_old`` are written into the buffers the
+        graph reads, and every other pointer it baked (the rollout's trajectories, ``adv``, ``ret``, the normaliser)
+        is checked to be the one it was captured with: they are allocated once, so the check fires only if something
+        outside the trainer moves them, and it raises rather than replaying on stale addresses.  (``VecEnv.rollout``
+        keeps one set of trajectory buffers per ``(steps, trajectory)``: a rollout of the trainer's env with another
+        ``steps`` between iterations does not move the trainer's.)  ``lr`` is a launch argument: the graph keeps the value it
+        was captured with."""
+        T, n = self.steps, self.env.num_envs
+        B, A = T * n, self.actor_dims[3]
+        obs, act = b.obs.reshape(B, -1), b.act.reshape(B, A)
+        ret, adv = b.ret.reshape(B), b.adv.reshape(B)
+        if not self.use_graph:
+            logp_old = b.logp.reshape(B).float()
+            for _ in range(self.epochs):
+                perm = torch.randperm(B, device=obs.device, generator=self._gen).view(self.minibatches, -1)
+                for idx in perm:
+                    self._minibatch_opt(obs, act, logp_old, adv, ret, idx)
+        else:
+            self._logp_old.copy_(b.logp.reshape(B))
+            for e in range(self.epochs):
+                torch.randperm(B, device=obs.device, generator=self._gen, out=self._perm[e].view(B))
+            norm = self.actor.obs_norm
+            baked = tuple(t.data_ptr() for t in (obs, act, adv, ret) + (() if norm is None else norm[:2])) + \
+                (None if norm is None else norm[2],)
+            if self._graph is None:
+                # once eagerly what writes only outputs the chain overwrites before it reads them (the normaliser pair,
+                # the gradient, its stats): no kernel is launched for the first time inside the capture
+                idx = self._perm[0, 0]
+                self.grad.run(self._params[0], self._params[1], self._params[2], obs, act, self._logp_old, adv, ret, idx=idx,
+                              adv_norm=adv_norm(adv, idx, out=self._adv_norm) if self.norm_adv else None,
+                              obs_norm=norm, clip_eps=self.clip, vf_coef=self.vf_coef, ent_coef=self.ent_coef,
+                              grad_actor=self._grads[0], grad_critic=self._grads[1], grad_log_std=self._grads[2],
+                              stats=self._grad_stats)
+                with torch.cuda.device(obs.device):
+                    graph = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(graph):
+                        for e in range(self.epochs):
+                            for idx in self._perm[e]:
+                                self._minibatch_opt(obs, act, self._logp_old, adv, ret, idx)
+                self._graph, self._baked = graph, baked
+            elif baked != self._baked:
+                raise _native.PbgError("PPO.update: a buffer the captured update reads has moved since the capture")
+            self._graph.replay()
+        st, info = self._grad_stats.clone(), self._opt_info.clone()   # the last minibatch's
+        return dict(pg=st[0], vf=st[1], clipfrac=st[2], kl=st[3], grad_norm=info[0])
+
     def iterate(self) -> dict:
         b = self.collect()
         stats = self.update(b)
@@ -368,6 +604,7 @@ class PPO:
 
     def close(self):
         self.actor.attach_action_noise(None)
-        for o in (self.actor, self.critic, self.noise, self.obs_stats, self.grad):
+        self._graph = None
+        for o in (self.actor, self.critic, self.noise, self.obs_stats, self.grad, self.adam):
             if o is not None:
                 o.close()

@@ -7,9 +7,12 @@ as an npz that tools/enjoy.py and MLPPolicy.from_npz load.
          [--lr 3e-3] [--epochs 4] [--minibatches 4] [--gamma 0.99] [--lam 0.95] [--clip 0.2] [--log-std -0.5]
          [--ent-coef 0.0] [--vf-coef 0.5] [--seed 0] [--precision 64] [--hidden 64 64] [--out ppo_policy.npz]
          [--obs-norm] [--obs-clip 5.0] [--eval-envs 256] [--eval-steps 200] [--eval-every 1] [--curve curve.json]
+         [--backward hip] [--optimizer hip] [--graph]
 
 --obs-norm trains under running observation normalisation (PPO(obs_norm=True)) and saves the final normaliser
-in the npz (obs_mean, obs_inv_std, obs_clip); --curve writes the per-iteration evaluation as JSON.
+in the npz (obs_mean, obs_inv_std, obs_clip); --curve writes the per-iteration evaluation as JSON.  --optimizer hip
+(with --backward hip) also runs the advantage normaliser, the gradient clipping and Adam as the library's launches
+(pbg_adv_norm, pbg_ppo_opt), and --graph replays the whole update as one captured graph.
 
 Per evaluated iteration it prints the noise-free mean policy's mean first-episode return and length over
 --eval-envs envs of a separate batch without auto-reset."""
@@ -49,6 +52,9 @@ def main():
     ap.add_argument("--obs-clip", type=float, default=5.0)
     ap.add_argument("--backward", choices=("torch", "hip"), default="torch",
                     help="the update's gradient: torch autograd, or the HIP backward pass (pbg_ppo_grad)")
+    ap.add_argument("--optimizer", choices=("torch", "hip"), default="torch",
+                    help="gradient clipping and Adam: torch, or the HIP step (pbg_ppo_opt; needs --backward hip)")
+    ap.add_argument("--graph", action="store_true", help="capture the update as one graph (needs --optimizer hip)")
     ap.add_argument("--curve", default=None, help="write the per-iteration evaluation here (JSON)")
     args = ap.parse_args()
 
@@ -63,10 +69,12 @@ def main():
     test = VecEnv(args.env_id, args.eval_envs, device="cuda:0", seed=args.seed + 1, autoreset=False, precision=args.precision)
     ppo = PPO(env, hidden=args.hidden, steps=args.steps, seed=args.seed, gamma=args.gamma, lam=args.lam, clip=args.clip,
               lr=args.lr, epochs=args.epochs, minibatches=args.minibatches, vf_coef=args.vf_coef, ent_coef=args.ent_coef,
-              log_std=args.log_std, obs_norm=args.obs_norm, obs_clip=args.obs_clip, backward=args.backward)
+              log_std=args.log_std, obs_norm=args.obs_norm, obs_clip=args.obs_clip, backward=args.backward,
+              optimizer=args.optimizer, graph=args.graph)
     print(f"{args.env_id} (float{args.precision}): {args.envs} envs x {args.steps} steps per iteration, actor MLP "
           f"{ppo.actor_dims}, lr {args.lr}, {args.epochs} epochs x {args.minibatches} minibatches, observation "
-          f"normalisation {'on' if args.obs_norm else 'off'}, backward pass {args.backward}")
+          f"normalisation {'on' if args.obs_norm else 'off'}, backward pass {args.backward}, optimizer "
+          f"{args.optimizer}{' (one graph)' if args.graph else ''}")
     curve = []
 
     def report(it):
