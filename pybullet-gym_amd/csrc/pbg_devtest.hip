@@ -10,6 +10,8 @@
 //     primitive is plain C++ (sincos_fast(float), pbg::sincos_reduced64).
 // The lane entry points take n = a multiple of 64: whole waves, so every helper sees the full EXEC mask
 // its contract requires (anything else is refused with hipErrorInvalidValue before any launch).
+// pbgdt_lds_peek_dev: what a workgroup finds in its LDS, the witness of tests/poison.py's LDS poison
+// (tests/test_learner_invariance_gpu.py).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -43,9 +45,28 @@ int launch_waves(long n, hipStream_t s, F f) {
   return (int)hipGetLastError();
 }
 
+// tests/poison.py's witness: what a workgroup finds in its LDS.  Dynamic LDS, so the loads cannot be folded away;
+// loads only, no LDS word is written.
+__global__ __launch_bounds__(256) void lds_peek_kernel(uint32_t* out, int words_per_wg) {
+  extern __shared__ uint32_t lds_peek[];
+  for (int i = threadIdx.x; i < words_per_wg; i += 256) out[(size_t)blockIdx.x * words_per_wg + i] = lds_peek[i];
+}
+
 }  // namespace
 
 extern "C" {
+
+// ---------------------------------------------------------------- the LDS a workgroup starts on
+// out[w * words_per_wg + i] = word i of workgroup w's LDS as it found it, n_wg workgroups of 256 lanes with
+// words_per_wg words (at most the 160 KiB of a CU) of dynamic LDS each; out: n_wg * words_per_wg words on the device
+int pbgdt_lds_peek_dev(uint32_t* out, int words_per_wg, int n_wg, hipStream_t st) {
+  if (!out || words_per_wg < 1 || words_per_wg > 163840 / 4 || n_wg < 1 || n_wg > 8192) return (int)hipErrorInvalidValue;
+  const hipError_t e = hipFuncSetAttribute((const void*)lds_peek_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           words_per_wg * 4);
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL(lds_peek_kernel, dim3((unsigned)n_wg), dim3(256), (size_t)words_per_wg * 4, st, out, words_per_wg);
+  return (int)hipGetLastError();
+}
 
 // ---------------------------------------------------------------- sin / cos
 int pbgdt_sincos32_dev(const float* x, float* s, float* c, long n, hipStream_t st) {

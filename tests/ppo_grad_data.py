@@ -20,8 +20,20 @@ BLOCKS = ("w1", "b1", "w2", "b2", "w3", "b3")
 # the widest MLP the library admits.
 # Each seed is the smallest whose batch meets the generator's three conditions with and without a normaliser (2 % of
 # a batch of 24 rows is no row at all, so a seed that needs one redraw is passed over).
+#
+# The last four reach paths of the device kernel the others leave out.  The widest MLP on a ragged tile: with 5 rows
+# the float64 forward's second half-tile pass does not run, with 13 it is partial.  (5, 129, 16, 1) at 8,209 rows: a
+# hidden layer above 128 columns (one column group) whose workgroups 0 and 1 own a second tile, so the weight gradient
+# accumulates onto the workgroup's partial in memory.  The widest MLP at 1,921 rows: WIDEST_TILES tiles for the
+# WIDEST_WGS workgroups its workspace cap allows, so again workgroups 0 and 1 own two tiles.
 CASES = (((3, 1, 1, 1), 24, 1, 1), ((3, 1, 1, 1), 24, 17, 0), ((5, 16, 8, 1), 40, 33, 0), ((28, 64, 64, 8), 300, 257, 0),
-         ((44, 65, 129, 17), 64, 48, 1), ((256, 256, 256, 64), 24, 16, 3))
+         ((44, 65, 129, 17), 64, 48, 1), ((256, 256, 256, 64), 24, 16, 3),
+         ((256, 256, 256, 64), 24, 5, 1), ((256, 256, 256, 64), 24, 13, 0), ((5, 129, 16, 1), 8300, 8209, 0),
+         ((256, 256, 256, 64), 2000, 1921, 0))
+# pbg_ppo_grad_create's geometry for (256, 256, 256, 64): Dtot = Da + Dc + A = 148,032 + 131,841 + 64 = 279,937 floats
+# and four doubles of statistics per workgroup, 1,119,780 bytes; the 128 MiB workspace cap admits 119 of them
+WIDEST_WGS = (128 << 20) // (4 * 279937 + 4 * 8)
+WIDEST_TILES = -(-1921 // 16)
 OPTIONS = [(norm, an, ent) for norm in (False, True) for an in (False, True) for ent in (0.0, 0.01)]
 
 
