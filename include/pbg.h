@@ -689,8 +689,8 @@ int pbg_adv_norm_host(int n_batch, int n_rows, const float* adv, const int64_t* 
 typedef struct pbg_ppo_opt pbg_ppo_opt;
 
 /* Pointers: DEVICE memory of the object's GPU (pbg_ppo_opt_step) or HOST memory (pbg_ppo_opt_host); entries at and
- * after n_blocks are ignored.  Versioned by struct_size like pbg_ppo_grad_io_t: PBG_E_ARG for a size below the first
- * version's (which ends with bpow), above the library's, or not a multiple of 4. */
+ * after n_blocks are ignored.  Versioned by struct_size like pbg_ppo_grad_io_t: PBG_E_ARG for a size that is neither the
+ * first version's (which ends with bpow) nor the library's (which appends lr_ptr). */
 typedef struct {
   uint32_t struct_size;
   int reserved;                                /* 0 */
@@ -706,6 +706,9 @@ typedef struct {
   float* v[PBG_PPO_OPT_MAX_BLOCKS];            /* [sizes[b]] in/out */
   uint32_t* t;                                 /* [1] in/out */
   double* bpow;                                /* [2] in/out: b1t, b2t (1, 1 before the first step) */
+  /* appended ("Counter-based permutations and an on-device learning rate" below); a caller built with the struct
+   * that ends with bpow passes its struct_size and gets NULL */
+  const double* lr_ptr;                        /* [1], nullable: when set, the step uses *lr_ptr in place of lr */
 } pbg_ppo_opt_io_t;
 
 /* PBG_E_ARG (before any HIP call) for n_blocks outside 1 .. 8, a size < 1, sizes or out NULL, device < 0; PBG_E_HIP
@@ -723,6 +726,60 @@ int pbg_ppo_opt_get_state(const pbg_ppo_opt* opt, float* m_out, float* v_out, ui
 /* One step on HOST pointers with no GPU: the same sums in the same order and the same element function, the same
  * bits.  Further PBG_E_ARG: n_blocks or sizes as in create; a NULL m or v of a block; t or bpow NULL. */
 int pbg_ppo_opt_host(int n_blocks, const int64_t* sizes, const pbg_ppo_opt_io_t* io);
+
+/* ---- Counter-based permutations and an on-device learning rate (appended; nothing above changes) ----
+ * What keeps a PPO iteration from being a function of the seed alone that runs with no host work: the minibatch
+ * permutation and a learning rate that can change under a replayed graph.
+ *
+ * perm(seed, c, B)[i] for i in 0 .. B - 1, 1 <= B <= 2^31 - 1: a Feistel network on the smallest even number of
+ * bits that holds B, cycle-walked into range.  All arithmetic is uint32.
+ *   k    = max(2, bit_length(B - 1));  k += k & 1;  half = k / 2;  mask = (1 << half) - 1
+ *   K[0..7] = the four words of Philox4x32-10(key = seed as (lo, hi), counter = (c, 0, 0, 0x9E)), then the four
+ *             of counter (c, 1, 0, 0x9E)
+ *   x = i
+ *   do:  L = x >> half;  R = x & mask
+ *        for r = 0 .. 7:  F = fmix32(R + K[r]) & mask;  (L, R) = (R, L ^ F)        (fmix32: murmur3's finaliser)
+ *        x = (L << half) | R
+ *   while x >= B
+ *   perm[i] = x
+ * The eight rounds are a bijection of [0, 2^k) and 2^k < 4 B.  The walk starts at i < B, which lies on its own
+ * cycle, so it comes back below B: it ends for every input and the result is a bijection of [0, B).  The tag 0x9E
+ * keeps the stream apart from 0xE5, 0xAC, 0xAC7 and 0x5EED.
+ *
+ * A pbg_perm lives on one device and owns one DEVICE uint32 counter (0 at creation).  pbg_perm_fill writes
+ * out (DEVICE int64 [n_perms, n_rows]): row j = perm(seed, counter + j, n_rows), then counter += n_perms (uint32:
+ * it wraps), all on `stream` with no host work: it captures as a plain chain, and because the counter lives on the
+ * device a captured fill replayed twice leaves what two eager fills leave.  The arrangement is two launches: the
+ * first (one lane per element, the permutation index the grid's second dimension) only reads the counter, the
+ * second is one lane that advances it after every workgroup of the first has read it.  pbg_perm_host is the same
+ * function on a HOST array with no GPU, the same bits. */
+typedef struct pbg_perm pbg_perm;
+
+/* PBG_E_ARG (before any HIP call) for device < 0 or out NULL; PBG_E_HIP for a device that does not exist.  *out
+ * is NULL after every failure. */
+int pbg_perm_create(int device, uint64_t seed, pbg_perm** out);
+void pbg_perm_destroy(pbg_perm* p);
+/* PBG_E_ARG (before any HIP call) for a NULL object or out, n_rows < 1, n_perms outside 1 .. 65535. */
+int pbg_perm_fill(pbg_perm* p, int n_rows, int n_perms, int64_t* out, void* stream);
+/* The counter: set on `stream`; get copies it into a DEVICE uint32 on `stream`. */
+int pbg_perm_set_counter(pbg_perm* p, uint32_t c, void* stream);
+int pbg_perm_get_counter(const pbg_perm* p, uint32_t* c_out, void* stream);
+/* out: HOST int64 [n_perms, n_rows], rows at the counters counter, counter + 1, ... (wrapping).  PBG_E_ARG as
+ * pbg_perm_fill. */
+int pbg_perm_host(uint64_t seed, uint32_t counter, int n_rows, int n_perms, int64_t* out);
+
+/* The optimiser's learning rate from device memory.  pbg_ppo_opt_io_t.lr_ptr (above), when not NULL, is a DEVICE
+ * (pbg_ppo_opt_step) or HOST (pbg_ppo_opt_host) float64 [1] that launch 2 reads in place of io->lr: the bits are
+ * those of passing the same value as lr, and a captured step follows what the memory holds at each replay.  The
+ * value is not validated on the device.
+ *
+ * pbg_ppo_lr_linear: one launch of one lane on `stream`, float64, nothing contracted:
+ *   q = (double)min(*it, n_total) / (double)n_total;   *lr_out = lr0 * (1.0 - q)
+ * it: DEVICE uint32 [1] (an iteration count the caller advances on the stream), lr_out: DEVICE float64 [1].
+ * PBG_E_ARG (before any HIP call) for n_total < 1 or a NULL pointer.  pbg_ppo_lr_linear_host: the same function on
+ * HOST pointers, the same bits. */
+int pbg_ppo_lr_linear(const uint32_t* it, uint32_t n_total, double lr0, double* lr_out, void* stream);
+int pbg_ppo_lr_linear_host(const uint32_t* it, uint32_t n_total, double lr0, double* lr_out);
 
 #ifdef __cplusplus
 }

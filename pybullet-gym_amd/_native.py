@@ -93,7 +93,7 @@ PPO_OPT_MAX_BLOCKS = 8  # PBG_PPO_OPT_MAX_BLOCKS
 
 class PPOOptIO(ctypes.Structure):
     """pbg_ppo_opt_io_t (pbg_ppo_opt_step, pbg_ppo_opt_host): versioned by struct_size; m, v, t, bpow: the host
-    twin's state."""
+    twin's state.  The struct's first version, which ends with bpow: the library keeps accepting it."""
     _fields_ = [("struct_size", ctypes.c_uint32), ("reserved", ctypes.c_int),
                 ("param", ctypes.c_void_p * PPO_OPT_MAX_BLOCKS), ("grad", ctypes.c_void_p * PPO_OPT_MAX_BLOCKS),
                 ("lr", ctypes.c_double), ("beta1", ctypes.c_double), ("beta2", ctypes.c_double),
@@ -103,10 +103,15 @@ class PPOOptIO(ctypes.Structure):
 
     def __init__(self, **kw):
         arrays = {k: kw.pop(k) for k in ("param", "grad", "m", "v") if k in kw}
-        super().__init__(struct_size=ctypes.sizeof(PPOOptIO), **kw)
+        super().__init__(struct_size=ctypes.sizeof(type(self)), **kw)
         for k, ptrs in arrays.items():
             for b, p in enumerate(ptrs):
                 getattr(self, k)[b] = p
+
+
+class PPOOptIO2(PPOOptIO):
+    """pbg_ppo_opt_io_t with the appended lr_ptr: a float64 [1] the step reads in place of lr (None: lr)."""
+    _fields_ = [("lr_ptr", ctypes.c_void_p)]
 
 
 POLICY_MAX_DIM = 256  # PBG_POLICY_MAX_DIM: obs_dim, h1, h2
@@ -228,12 +233,26 @@ def lib():
         L.pbg_ppo_opt_create.argtypes = [I, I, I64P, ctypes.POINTER(H)]
         L.pbg_ppo_opt_destroy.argtypes = [H]
         L.pbg_ppo_opt_destroy.restype = None
-        L.pbg_ppo_opt_step.argtypes = [H, ctypes.POINTER(PPOOptIO), P]
+        L.pbg_ppo_opt_step.argtypes = [H, P, P]
         L.pbg_ppo_opt_reset.argtypes = [H, P]
         L.pbg_ppo_opt_get_state.argtypes = [H, P, P, P, P]
-        L.pbg_ppo_opt_host.argtypes = [I, I64P, ctypes.POINTER(PPOOptIO)]
+        L.pbg_ppo_opt_host.argtypes = [I, I64P, P]
         for f in PPO_OPT_EXPORTED:
             if f != "pbg_ppo_opt_destroy":
+                getattr(L, f).restype = I
+    if hasattr(L, "pbg_perm_create"):  # counter-based permutations and the on-device learning rate
+        U64, U32, D = ctypes.c_uint64, ctypes.c_uint32, ctypes.c_double
+        L.pbg_perm_create.argtypes = [I, U64, ctypes.POINTER(H)]
+        L.pbg_perm_destroy.argtypes = [H]
+        L.pbg_perm_destroy.restype = None
+        L.pbg_perm_fill.argtypes = [H, I, I, P, P]
+        L.pbg_perm_set_counter.argtypes = [H, U32, P]
+        L.pbg_perm_get_counter.argtypes = [H, P, P]
+        L.pbg_perm_host.argtypes = [U64, U32, I, I, P]
+        L.pbg_ppo_lr_linear.argtypes = [P, U32, D, P, P]
+        L.pbg_ppo_lr_linear_host.argtypes = [P, U32, D, P]
+        for f in PERM_EXPORTED:
+            if f != "pbg_perm_destroy":
                 getattr(L, f).restype = I
     for f in ("pbg_info", "pbg_reset", "pbg_step", "pbg_step_ex", "pbg_get_state", "pbg_set_state",
               "pbg_pack_record_sizes", "pbg_pack", "pbg_create_debug", "pbg_sample_actions", "pbg_create_ex",
@@ -258,12 +277,14 @@ ACTION_NOISE_EXPORTED = ("pbg_action_noise_create", "pbg_action_noise_destroy", 
 PPO_GRAD_EXPORTED = ("pbg_ppo_grad_create", "pbg_ppo_grad_destroy", "pbg_ppo_grad_run", "pbg_ppo_grad_host")
 PPO_OPT_EXPORTED = ("pbg_adv_norm", "pbg_adv_norm_host", "pbg_ppo_opt_create", "pbg_ppo_opt_destroy", "pbg_ppo_opt_step",
                     "pbg_ppo_opt_reset", "pbg_ppo_opt_get_state", "pbg_ppo_opt_host")
+PERM_EXPORTED = ("pbg_perm_create", "pbg_perm_destroy", "pbg_perm_fill", "pbg_perm_set_counter", "pbg_perm_get_counter",
+                 "pbg_perm_host", "pbg_ppo_lr_linear", "pbg_ppo_lr_linear_host")
 EXPORTED = ("pbg_create", "pbg_create_debug", "pbg_create_ex", "pbg_create_v2", "pbg_precision",
             "pbg_default_sim_params", "pbg_get_sim_params",
             "pbg_destroy", "pbg_info", "pbg_reset", "pbg_step", "pbg_step_ex",
             "pbg_get_state", "pbg_set_state", "pbg_pack_record_sizes", "pbg_pack", "pbg_sample_actions",
             "pbg_debug_poison", "pbg_last_error") + POLICY_EXPORTED + POPULATION_EXPORTED + OBS_NORM_EXPORTED + \
-    ACTION_NOISE_EXPORTED + PPO_GRAD_EXPORTED + PPO_OPT_EXPORTED
+    ACTION_NOISE_EXPORTED + PPO_GRAD_EXPORTED + PPO_OPT_EXPORTED + PERM_EXPORTED
 
 
 def check(rc: int, what: str):

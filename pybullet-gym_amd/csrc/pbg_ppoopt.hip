@@ -1,7 +1,8 @@
 // pbg_ppoopt.hip -- what is left of a PPO minibatch step once the gradient is there (include/pbg.h "PPO optimiser
 // step"): the advantage normaliser's (shift, scale) pair as one launch (pbg_adv_norm, pbg_adv_norm_host) and Adam
 // with global-norm gradient clipping over up to 8 flat float32 blocks as two launches with its moments, its step
-// count and the running powers of the betas on the device (pbg_ppo_opt_*, pbg_ppo_opt_host).
+// count and the running powers of the betas on the device (pbg_ppo_opt_*, pbg_ppo_opt_host), its learning rate
+// optionally read from device memory (io.lr_ptr; pbg_perm.hip's pbg_ppo_lr_linear writes one).
 //
 // Every sum is float64 in the order pbg.h states, every per-element expression one __host__ __device__ function
 // compiled with contraction off, so the host twins give the device's bits.  (The optimiser's summed squares are
@@ -150,6 +151,7 @@ struct OptArgs {
   double* partial;  // [wg0[n_blocks]]
   double lr, beta1, beta2, eps, max_grad_norm;
   double* info;     // [2], nullable
+  const double* lr_ptr;  // nullable: launch 2 reads the learning rate here instead of lr
 };
 
 // the block of workgroup `wg` and its fields, by selects: no indexed access into the argument struct
@@ -218,7 +220,8 @@ __global__ __launch_bounds__(OB) void ppoopt_step_kernel(OptArgs a) {
     a.info[0] = norm;
     a.info[1] = coef;
   }
-  const AdamK k = adam_factors(coef, a.lr, a.beta1, a.beta2, a.eps, a.state->b1t, a.state->b2t);
+  const double lr = a.lr_ptr ? *a.lr_ptr : a.lr;  // a uniform load: one value for the launch
+  const AdamK k = adam_factors(coef, lr, a.beta1, a.beta2, a.eps, a.state->b1t, a.state->b2t);
   const Mine b = mine(a, (int)blockIdx.x);
   const size_t groups = (b.size + 3) / 4, stride = (size_t)b.G * OB;
   for (size_t q = (size_t)b.w * OB + threadIdx.x; q < groups; q += stride) {
@@ -279,7 +282,8 @@ int check_io(const char* who, const pbg_ppo_opt_io_t* uio, int n_blocks, pbg_ppo
     return pbg::capi_fail(PBG_E_ARG, msg);
   }
   constexpr uint32_t v1_size = (uint32_t)(offsetof(pbg_ppo_opt_io_t, bpow) + sizeof(double*));
-  if (uio->struct_size < v1_size || uio->struct_size > (uint32_t)sizeof(pbg_ppo_opt_io_t) || uio->struct_size % 4u != 0u) {
+  // the two versions: the one that ends with bpow and this library's, which appends lr_ptr (NULL for the first)
+  if (uio->struct_size != v1_size && uio->struct_size != (uint32_t)sizeof(pbg_ppo_opt_io_t)) {
     snprintf(msg, sizeof(msg), "%s: io->struct_size %u is not a pbg_ppo_opt_io_t size", who, uio->struct_size);
     return pbg::capi_fail(PBG_E_ARG, msg);
   }
@@ -425,6 +429,7 @@ int pbg_ppo_opt_step(pbg_ppo_opt* o, const pbg_ppo_opt_io_t* uio, void* stream) 
   a.partial = o->partial;
   a.lr = io.lr; a.beta1 = io.beta1; a.beta2 = io.beta2; a.eps = io.eps; a.max_grad_norm = io.max_grad_norm;
   a.info = io.info;
+  a.lr_ptr = io.lr_ptr;
   DeviceGuard dg(o->device);
   const unsigned G = (unsigned)o->wg0[o->n_blocks];
   hipLaunchKernelGGL(ppoopt_sumsq_kernel, dim3(G), dim3(OB), 0, (hipStream_t)stream, a);
@@ -498,7 +503,7 @@ int pbg_ppo_opt_host(int n_blocks, const int64_t* sizes, const pbg_ppo_opt_io_t*
     io.info[0] = norm;
     io.info[1] = coef;
   }
-  const AdamK k = adam_factors(coef, io.lr, io.beta1, io.beta2, io.eps, io.bpow[0], io.bpow[1]);
+  const AdamK k = adam_factors(coef, io.lr_ptr ? *io.lr_ptr : io.lr, io.beta1, io.beta2, io.eps, io.bpow[0], io.bpow[1]);
   for (int b = 0; b < n_blocks; b++)
     for (size_t i = 0; i < (size_t)sizes[b]; i++) adam_elem(k, io.grad[b][i], io.param[b][i], io.m[b][i], io.v[b][i]);
   return PBG_OK;

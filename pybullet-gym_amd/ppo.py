@@ -8,7 +8,10 @@ launch (pbg_gae).  The backward pass is torch autograd by default (``PPO(backwar
 ``backward="hip"`` each minibatch's gradient is ``PPOGrad.run``: two launches (pbg_ppo_grad, include/pbg.h "PPO
 gradient"), and with ``optimizer="hip"`` the advantage normaliser, the gradient clipping and Adam are ``adv_norm`` and
 ``AdamClip`` (pbg_adv_norm, pbg_ppo_opt, include/pbg.h "PPO optimiser step"): three more launches, optionally
-the whole update as one captured graph.  The collection half of an iteration has no host work between its launches."""
+the whole update as one captured graph.  The collection half of an iteration has no host work between its launches.
+``Permutation`` (pbg_perm, include/pbg.h "Counter-based permutations") draws the minibatch permutations on the device,
+``lr_linear`` (pbg_ppo_lr_linear) writes a scheduled learning rate that ``AdamClip.step`` reads from device memory, and
+with both an iteration can be one captured graph (``PPO(graph="iteration")``)."""
 from __future__ import annotations
 
 import ctypes
@@ -253,15 +256,17 @@ class AdamClip:
         if not self.host and not self._h:
             raise _native.PbgError(f"AdamClip.{what}: the object is closed")
 
-    def step(self, params, grads, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, max_grad_norm: float = 0.0, info=None):
+    def step(self, params, grads, lr, betas=(0.9, 0.999), eps: float = 1e-8, max_grad_norm: float = 0.0, info=None):
         """One step on ``params`` (updated in place) with ``grads``: sequences of contiguous float32 ``[sizes[b]]``
         tensors on the object's GPU (numpy arrays on the host).  ``max_grad_norm`` 0 (or None): no clipping.  ``info``:
-        optional float64 ``[2]`` that receives the gradient's global norm and the clipping coefficient.  ``lr`` and
-        the other scalars are launch arguments: a captured step keeps the values it was captured with, so a
-        learning-rate schedule needs a new capture."""
+        optional float64 ``[2]`` that receives the gradient's global norm and the clipping coefficient.  ``lr``: a
+        float, a launch argument like the other scalars (a captured step keeps the value it was captured with), or a
+        float64 ``[1]`` tensor on the object's GPU (a numpy ``[1]`` array on the host) that the step reads where it
+        lies: the bits of the same value passed as a float, and a captured step follows the tensor."""
         self._open("step")
         f32, f64 = (np.float32, np.float64) if self.host else (torch.float32, torch.float64)
         params, grads = list(params), list(grads)
+        lr_t = lr if isinstance(lr, (np.ndarray, torch.Tensor)) else None
         if len(params) != len(self.sizes) or len(grads) != len(self.sizes):
             raise _native.PbgError(f"AdamClip.step: {len(self.sizes)} blocks expected, got {len(params)} params and "
                                    f"{len(grads)} grads")
@@ -269,6 +274,8 @@ class AdamClip:
         checks += [(f"grads[{b}]", t, (s,), f32) for b, (t, s) in enumerate(zip(grads, self.sizes))]
         if info is not None:
             checks.append(("info", info, (2,), f64))
+        if lr_t is not None:
+            checks.append(("lr", lr_t, (1,), f64))
         for name, t, shape, dt in checks:
             ok = isinstance(t, np.ndarray) and t.flags.c_contiguous if self.host else \
                 isinstance(t, torch.Tensor) and t.is_contiguous() and t.device == self.device
@@ -276,15 +283,20 @@ class AdamClip:
                 raise _native.PbgError(f"AdamClip.step: {name} must be a contiguous {dt} "
                                        f"{'array' if self.host else f'tensor on {self.device}'} of shape {shape}")
         ptr = (lambda t: t.ctypes.data) if self.host else (lambda t: t.data_ptr())
-        kw = dict(param=[ptr(t) for t in params], grad=[ptr(t) for t in grads], lr=float(lr), beta1=float(betas[0]),
-                  beta2=float(betas[1]), eps=float(eps), max_grad_norm=float(max_grad_norm or 0.0),
+        kw = dict(param=[ptr(t) for t in params], grad=[ptr(t) for t in grads], lr=0.0 if lr_t is not None else float(lr),
+                  beta1=float(betas[0]), beta2=float(betas[1]), eps=float(eps), max_grad_norm=float(max_grad_norm or 0.0),
                   info=None if info is None else ptr(info))
+        # the struct's first version while no lr tensor is given: a library from before lr_ptr keeps working
+        IO = _native.PPOOptIO
+        if lr_t is not None:
+            _need_perm()
+            IO, kw["lr_ptr"] = _native.PPOOptIO2, ptr(lr_t)
         if self.host:
-            io = _native.PPOOptIO(m=[ptr(t) for t in self._m], v=[ptr(t) for t in self._v], t=self._t.ctypes.data,
+            io = IO(m=[ptr(t) for t in self._m], v=[ptr(t) for t in self._v], t=self._t.ctypes.data,
                                   bpow=self._bpow.ctypes.data, **kw)
             _native.check(_native.lib().pbg_ppo_opt_host(len(self.sizes), self._sizes, ctypes.byref(io)), "pbg_ppo_opt_host")
             return
-        io = _native.PPOOptIO(**kw)
+        io = IO(**kw)
         with torch.cuda.device(self.device):
             _native.check(_native.lib().pbg_ppo_opt_step(self._h, ctypes.byref(io), self._stream()), "pbg_ppo_opt_step")
 
@@ -326,6 +338,126 @@ class AdamClip:
             pass
 
 
+def _need_perm():
+    if not hasattr(_native.lib(), "pbg_perm_create"):
+        raise _native.PbgError(f"{_native.LIB_PATH} has no pbg_perm_create: a build without counter-based permutations")
+    return _native.lib()
+
+
+class Permutation:
+    """Counter-based permutations of ``0 .. B - 1`` (include/pbg.h "Counter-based permutations", pbg_perm): an
+    eight-round Feistel network keyed by Philox words of ``(seed, counter)``, cycle-walked into range; ``rng.permutation``
+    is the numpy mirror with the same bits.  ``device``: a GPU, whose object owns the counter on the device (so a
+    captured fill that is replayed draws the next permutations like an eager one), or ``None`` / ``"cpu"`` for the host
+    twin (pbg_perm_host on numpy arrays, the counter kept here)."""
+
+    def __init__(self, seed: int, device=None):
+        L = _need_perm()
+        self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.host = device is None or str(device) == "cpu"
+        self.device = None if self.host else torch.device(device)
+        self._h = ctypes.c_void_p()
+        self._counter = 0
+        if self.host:
+            return
+        if self.device.type != "cuda":
+            raise _native.PbgError(f"Permutation: device must be a GPU or None, got {device!r}")
+        index = self.device.index if self.device.index is not None else torch.cuda.current_device()
+        self.device = torch.device("cuda", index)
+        _native.check(L.pbg_perm_create(index, self.seed, ctypes.byref(self._h)), "pbg_perm_create")
+
+    def _stream(self):
+        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _open(self, what):
+        if not self.host and not self._h:
+            raise _native.PbgError(f"Permutation.{what}: the object is closed")
+
+    def fill(self, B: int, n_perms: int = 1, out=None):
+        """``out``, int64 ``[n_perms, B]``: row j is the permutation at ``counter + j``; the counter then advances by
+        ``n_perms`` (uint32, it wraps).  On a GPU: two launches on the current stream, no host work."""
+        self._open("fill")
+        B, n_perms = int(B), int(n_perms)
+        if B < 1 or not 1 <= n_perms <= 65535:
+            raise _native.PbgError(f"Permutation.fill: B = {B} must be >= 1 and n_perms = {n_perms} in 1 .. 65535")
+        if out is None:
+            out = np.empty((n_perms, B), np.int64) if self.host else \
+                torch.empty((n_perms, B), dtype=torch.int64, device=self.device)
+        ok = isinstance(out, np.ndarray) and out.flags.c_contiguous and out.dtype == np.int64 if self.host else \
+            isinstance(out, torch.Tensor) and out.is_contiguous() and out.device == self.device and out.dtype == torch.int64
+        if not ok or tuple(out.shape) != (n_perms, B):
+            raise _native.PbgError(f"Permutation.fill: out must be a contiguous int64 "
+                                   f"{'array' if self.host else f'tensor on {self.device}'} of shape {(n_perms, B)}")
+        if self.host:
+            _native.check(_native.lib().pbg_perm_host(self.seed, self._counter, B, n_perms, out.ctypes.data), "pbg_perm_host")
+            self._counter = (self._counter + n_perms) & 0xFFFFFFFF
+            return out
+        with torch.cuda.device(self.device):
+            _native.check(_native.lib().pbg_perm_fill(self._h, B, n_perms, out.data_ptr(), self._stream()), "pbg_perm_fill")
+        return out
+
+    @property
+    def counter(self) -> int:
+        """Permutations drawn so far, modulo 2^32 (on a GPU it synchronises to read it); assignable."""
+        if self.host:
+            return self._counter
+        self._open("counter")
+        out = torch.zeros(1, dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            _native.check(_native.lib().pbg_perm_get_counter(self._h, out.data_ptr(), self._stream()), "pbg_perm_get_counter")
+        return int(out.item()) & 0xFFFFFFFF
+
+    @counter.setter
+    def counter(self, value):
+        if self.host:
+            self._counter = int(value) & 0xFFFFFFFF
+            return
+        self._open("counter")
+        with torch.cuda.device(self.device):
+            _native.check(_native.lib().pbg_perm_set_counter(self._h, int(value) & 0xFFFFFFFF, self._stream()),
+                          "pbg_perm_set_counter")
+
+    def close(self):
+        if self._h:
+            _native.lib().pbg_perm_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def lr_linear(it, n_total: int, lr0: float, out=None):
+    """``out``, float64 ``[1]`` = ``lr0 * (1 - min(it, n_total) / n_total)``: pbg_ppo_lr_linear, one launch of one lane,
+    float64 in that order (``rng.lr_linear`` gives the same bits).  ``it``: an int32 ``[1]`` tensor on a GPU (read as
+    uint32), or a numpy uint32 ``[1]`` array for the host twin (pbg_ppo_lr_linear_host)."""
+    L = _need_perm()
+    host = isinstance(it, np.ndarray)
+    n_total = int(n_total)
+    if not 1 <= n_total <= 0xFFFFFFFF:
+        raise _native.PbgError(f"lr_linear: n_total = {n_total} outside 1 .. 2^32 - 1")
+    if out is None:
+        out = np.empty(1, np.float64) if host else torch.empty(1, dtype=torch.float64, device=it.device)
+    if host:
+        ok = it.dtype == np.uint32 and it.shape == (1,) and isinstance(out, np.ndarray) and out.dtype == np.float64 and \
+            out.shape == (1,)
+    else:
+        ok = isinstance(it, torch.Tensor) and it.is_cuda and it.dtype == torch.int32 and tuple(it.shape) == (1,) and \
+            isinstance(out, torch.Tensor) and out.device == it.device and out.dtype == torch.float64 and tuple(out.shape) == (1,)
+    if not ok:
+        raise _native.PbgError("lr_linear: it must be an int32 [1] GPU tensor (a uint32 [1] array on the host) and out a "
+                               "float64 [1] on the same device")
+    if host:
+        _native.check(L.pbg_ppo_lr_linear_host(it.ctypes.data, n_total, float(lr0), out.ctypes.data), "pbg_ppo_lr_linear_host")
+        return out
+    with torch.cuda.device(it.device):
+        stream = ctypes.c_void_p(torch.cuda.current_stream(it.device).cuda_stream)
+        _native.check(L.pbg_ppo_lr_linear(it.data_ptr(), n_total, float(lr0), out.data_ptr(), stream), "pbg_ppo_lr_linear")
+    return out
+
+
 @dataclass
 class Batch:
     """One iteration's data (views of the env's rollout buffers and this object's own): ``[T, n, ...]``."""
@@ -355,14 +487,31 @@ class PPO:
     library's too (``adv_norm``, ``AdamClip``: the torch path's lr, betas (0.9, 0.999), eps 1e-5 and ``max_grad_norm``), a
     minibatch is at most five launches and no torch kernel, and the stats gain ``grad_norm``; the permutation stays
     ``torch.randperm``.  ``graph=True`` (needs ``optimizer="hip"``): the whole ``epochs x minibatches`` chain is one
-    captured graph, replayed every iteration; ``lr`` is a launch argument, so the graph keeps the captured value (no
-    learning-rate schedule)."""
+    captured graph, replayed every iteration; ``lr`` is a launch argument, so the graph keeps the captured value unless a
+    schedule is set (below).
+
+    ``permutation="device"`` (needs ``optimizer="hip"``): the minibatch permutations come from a ``Permutation(seed)``
+    (pbg_perm_fill, one fill of ``epochs`` rows per update) instead of ``torch.randperm``: iteration i, epoch e uses
+    ``rng.permutation(B, seed, i * epochs + e)``, which numpy restates and no torch version changes; with ``graph=True``
+    the fill is part of the captured update.  ``lr_schedule="linear", schedule_iterations=N`` (needs ``optimizer="hip"``):
+    the trainer keeps its iteration count in a device int32 ``[1]`` (``_it_dev``, advanced on the stream at the end of
+    ``iterate``), every update starts with pbg_ppo_lr_linear into a device float64 ``[1]`` (``_lr_dev``: ``lr * (1 -
+    min(i, N) / N)``, ``rng.lr_linear``) and ``AdamClip.step`` reads that tensor, so the schedule advances under a
+    replayed graph too.  ``graph="iteration"`` (needs ``optimizer="hip"`` and ``permutation="device"``): the first
+    ``iterate()`` runs eagerly as iteration 0 (so every kernel has been launched once) and then captures the whole
+    iteration -- ``set_all``, the std, the rollout with its statistics, the critic, ``gae``, ``logp_old``, the schedule
+    launch, the permutation fill, the ``epochs x minibatches`` steps, the normaliser's ``finalize`` / ``set_obs_norm`` and
+    the iteration count's increment -- as one graph; every later ``iterate()`` is one replay and returns device tensors
+    without synchronising.  The actor kernel takes the statistics and the noise as launch arguments, so the graph bakes
+    them: what is attached on the host at replay time does not matter, and ``evaluate()`` between two replays (which
+    detaches the noise on the host and never attaches the statistics) changes nothing the replay does.  The pointers the
+    graph baked are compared before each replay; a moved one raises ``PbgError``."""
 
     def __init__(self, env, hidden=(64, 64), steps: int = 64, seed: int = 0, gamma: float = 0.99, lam: float = 0.95,
                  clip: float = 0.2, lr: float = 3e-4, epochs: int = 4, minibatches: int = 4, vf_coef: float = 0.5,
                  ent_coef: float = 0.0, log_std: float = -0.5, max_grad_norm: float = 0.5, norm_adv: bool = True,
                  obs_norm: bool = False, obs_clip: float = 5.0, backward: str = "torch", optimizer: str = "torch",
-                 graph: bool = False):
+                 graph=False, permutation: str = "torch", lr_schedule=None, schedule_iterations=None):
         n, dev = env.num_envs, env.device
         if backward not in ("torch", "hip"):
             raise _native.PbgError(f"PPO: backward must be 'torch' or 'hip', got {backward!r}")
@@ -372,6 +521,22 @@ class PPO:
             raise _native.PbgError("PPO: optimizer='hip' takes its gradient from pbg_ppo_grad: it needs backward='hip'")
         if graph and optimizer != "hip":
             raise _native.PbgError("PPO: graph=True captures the library's launches alone: it needs optimizer='hip'")
+        if not isinstance(graph, bool) and graph != "iteration":
+            raise _native.PbgError(f"PPO: graph must be False, True or 'iteration', got {graph!r}")
+        if permutation not in ("torch", "device"):
+            raise _native.PbgError(f"PPO: permutation must be 'torch' or 'device', got {permutation!r}")
+        if permutation == "device" and optimizer != "hip":
+            raise _native.PbgError("PPO: permutation='device' fills the index buffer of the library's update: it needs "
+                                   "optimizer='hip'")
+        if graph == "iteration" and permutation != "device":
+            raise _native.PbgError("PPO: graph='iteration' captures the permutation's draw: it needs permutation='device'")
+        if lr_schedule not in (None, "linear"):
+            raise _native.PbgError(f"PPO: lr_schedule must be None or 'linear', got {lr_schedule!r}")
+        if lr_schedule is not None and optimizer != "hip":
+            raise _native.PbgError("PPO: lr_schedule is read from device memory by the library's optimiser: it needs "
+                                   "optimizer='hip'")
+        if lr_schedule is not None and (schedule_iterations is None or int(schedule_iterations) < 1):
+            raise _native.PbgError(f"PPO: lr_schedule needs schedule_iterations >= 1, got {schedule_iterations!r}")
         self.backward = backward
         if n % 2 != 0 or not env.autoreset:
             raise _native.PbgError("PPO: the env must have an even number of envs (the actors are populations of one "
@@ -416,17 +581,28 @@ class PPO:
             for p in (self.actor_theta, self.critic_theta, self.log_std):
                 p.grad = torch.zeros_like(p.data)
             self._grad_stats = torch.zeros(4, dtype=torch.float64, device=dev)
-        self.adam = self._graph = None
+        self.adam = self._graph = self.perm = self._it_dev = self._iter_graph = None
+        self.permutation, self.lr_schedule, self.graph_iteration = permutation, lr_schedule, graph == "iteration"
         if optimizer == "hip":
             if norm_adv and (T * n) // self.minibatches < 2:
                 raise _native.PbgError("PPO: optimizer='hip' with norm_adv needs minibatches of at least 2 rows")
             self._params = [self.actor_theta.data, self.critic_theta.data, self.log_std.data]
             self._grads = [self.actor_theta.grad, self.critic_theta.grad, self.log_std.grad]
             self.adam = AdamClip([p.numel() for p in self._params], dev)
-            self.lr, self.use_graph = float(lr), bool(graph)
+            self.lr, self.use_graph = float(lr), graph is True
             self._adv_norm = torch.zeros(2, **kw)
             self._opt_info = torch.zeros(2, dtype=torch.float64, device=dev)
-            if graph:
+            self._lr_now = self.lr   # what AdamClip.step gets: the float, or the schedule's device tensor
+            if lr_schedule is not None or graph == "iteration":
+                # the iteration count the schedule reads, advanced on the stream (inside a captured iteration)
+                self._it_dev = torch.zeros(1, dtype=torch.int32, device=dev)
+            if lr_schedule is not None:
+                self.schedule_iterations = int(schedule_iterations)
+                self._lr_dev = torch.zeros(1, dtype=torch.float64, device=dev)
+                self._lr_now = self._lr_dev
+            if permutation == "device":
+                self.perm = Permutation(self.seed, dev)
+            if graph or permutation == "device":
                 # what a replay reads and a new iteration must refill in place
                 self._perm = torch.zeros((self.epochs, self.minibatches, (T * n) // self.minibatches), dtype=torch.int64, device=dev)
                 self._logp_old = torch.zeros(T * n, **kw)
@@ -527,7 +703,16 @@ class PPO:
                       obs_norm=self.actor.obs_norm, clip_eps=self.clip, vf_coef=self.vf_coef, ent_coef=self.ent_coef,
                       grad_actor=self._grads[0], grad_critic=self._grads[1], grad_log_std=self._grads[2],
                       stats=self._grad_stats)
-        self.adam.step(self._params, self._grads, self.lr, (0.9, 0.999), 1e-5, self.max_grad_norm, info=self._opt_info)
+        self.adam.step(self._params, self._grads, self._lr_now, (0.9, 0.999), 1e-5, self.max_grad_norm, info=self._opt_info)
+
+    def _schedule(self):
+        """The schedule's launch: this iteration's learning rate into ``_lr_dev``, from the device's iteration count."""
+        if self.lr_schedule is not None:
+            lr_linear(self._it_dev, self.schedule_iterations, self.lr, out=self._lr_dev)
+
+    def _draw(self, B):
+        """This update's ``epochs`` permutations into ``_perm`` (``permutation="device"``: one fill)."""
+        self.perm.fill(B, self.epochs, out=self._perm.view(self.epochs, B))
 
     def _update_opt(self, b: Batch) -> dict:
         """``update`` with ``optimizer="hip"``: the permutations are ``_update_hip``'s (the same generator), every
@@ -538,21 +723,35 @@ class PPO:
         outside the trainer moves them, and it raises rather than replaying on stale addresses.  (``VecEnv.rollout``
         keeps one set of trajectory buffers per ``(steps, trajectory)``: a rollout of the trainer's env with another
         ``steps`` between iterations does not move the trainer's.)  ``lr`` is a launch argument: the graph keeps the value it
-        was captured with."""
+        was captured with, unless ``lr_schedule`` is set: then the chain starts with the schedule's launch and every step
+        reads ``_lr_dev``.  With ``permutation="device"`` the chain's second item is the permutation fill (inside the
+        graph with ``graph=True``) and ``torch.randperm`` is not called."""
         T, n = self.steps, self.env.num_envs
         B, A = T * n, self.actor_dims[3]
         obs, act = b.obs.reshape(B, -1), b.act.reshape(B, A)
         ret, adv = b.ret.reshape(B), b.adv.reshape(B)
+        device_perm = self.permutation == "device"
         if not self.use_graph:
-            logp_old = b.logp.reshape(B).float()
-            for _ in range(self.epochs):
-                perm = torch.randperm(B, device=obs.device, generator=self._gen).view(self.minibatches, -1)
-                for idx in perm:
-                    self._minibatch_opt(obs, act, logp_old, adv, ret, idx)
+            self._schedule()
+            if device_perm:
+                self._logp_old.copy_(b.logp.reshape(B))
+                self._draw(B)
+                for e in range(self.epochs):
+                    for idx in self._perm[e]:
+                        self._minibatch_opt(obs, act, self._logp_old, adv, ret, idx)
+            else:
+                logp_old = b.logp.reshape(B).float()
+                for _ in range(self.epochs):
+                    perm = torch.randperm(B, device=obs.device, generator=self._gen).view(self.minibatches, -1)
+                    for idx in perm:
+                        self._minibatch_opt(obs, act, logp_old, adv, ret, idx)
+            if self._capturing:   # graph="iteration": nothing may be read back inside the capture
+                return {}
         else:
             self._logp_old.copy_(b.logp.reshape(B))
-            for e in range(self.epochs):
-                torch.randperm(B, device=obs.device, generator=self._gen, out=self._perm[e].view(B))
+            if not device_perm:
+                for e in range(self.epochs):
+                    torch.randperm(B, device=obs.device, generator=self._gen, out=self._perm[e].view(B))
             norm = self.actor.obs_norm
             baked = tuple(t.data_ptr() for t in (obs, act, adv, ret) + (() if norm is None else norm[:2])) + \
                 (None if norm is None else norm[2],)
@@ -560,6 +759,7 @@ class PPO:
                 # once eagerly what writes only outputs the chain overwrites before it reads them (the normaliser pair,
                 # the gradient, its stats): no kernel is launched for the first time inside the capture
                 idx = self._perm[0, 0]
+                self._schedule()   # it writes only the learning rate the chain's first launch writes again
                 self.grad.run(self._params[0], self._params[1], self._params[2], obs, act, self._logp_old, adv, ret, idx=idx,
                               adv_norm=adv_norm(adv, idx, out=self._adv_norm) if self.norm_adv else None,
                               obs_norm=norm, clip_eps=self.clip, vf_coef=self.vf_coef, ent_coef=self.ent_coef,
@@ -568,6 +768,9 @@ class PPO:
                 with torch.cuda.device(obs.device):
                     graph = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(graph):
+                        self._schedule()
+                        if device_perm:
+                            self._draw(B)
                         for e in range(self.epochs):
                             for idx in self._perm[e]:
                                 self._minibatch_opt(obs, act, self._logp_old, adv, ret, idx)
@@ -575,14 +778,57 @@ class PPO:
             elif baked != self._baked:
                 raise _native.PbgError("PPO.update: a buffer the captured update reads has moved since the capture")
             self._graph.replay()
-        st, info = self._grad_stats.clone(), self._opt_info.clone()   # the last minibatch's
-        return dict(pg=st[0], vf=st[1], clipfrac=st[2], kl=st[3], grad_norm=info[0])
+        return self._stats_now()
 
-    def iterate(self) -> dict:
+    _capturing = False
+
+    def _iterate_once(self) -> dict:
+        """One iteration's launches in order, the device's iteration count included."""
         b = self.collect()
         stats = self.update(b)
         if self.obs_stats is not None:
             self._set_norm()
+        if self._it_dev is not None:
+            self._it_dev.add_(1)
+        return stats
+
+    def _stats_now(self) -> dict:
+        st, info = self._grad_stats.clone(), self._opt_info.clone()   # the last minibatch's
+        return dict(pg=st[0], vf=st[1], clipfrac=st[2], kl=st[3], grad_norm=info[0])
+
+    def _baked_iteration(self):
+        """The addresses an iteration's launches take that the trainer does not own alone: the env's observation and
+        rollout buffers, and the normaliser's copies."""
+        env, T = self.env, self.steps
+        io, traj = env._ro_io[(T, True)]
+        ts = [env.obs] + list(env._ro_work.values()) + list(env._ro_acc.values()) + [traj[k] for k in sorted(traj)]
+        norm = self.actor.obs_norm
+        return tuple(t.data_ptr() for t in ts + ([] if norm is None else list(norm[:2]))) + \
+            (None if norm is None else norm[2],)
+
+    def iterate(self) -> dict:
+        if not self.graph_iteration:
+            stats = self._iterate_once()
+            self.iteration += 1
+            return stats
+        if self._iter_graph is None:
+            # iteration 0 runs eagerly: every kernel the graph will launch has then been launched once, every lazily
+            # allocated buffer exists, and nothing has to be undone.  The capture itself executes nothing
+            stats = self._iterate_once()
+            with torch.cuda.device(self.env.device):
+                graph = torch.cuda.CUDAGraph()
+                self._capturing = True
+                try:
+                    with torch.cuda.graph(graph):
+                        self._iterate_once()
+                finally:
+                    self._capturing = False
+            self._iter_graph, self._iter_baked = graph, self._baked_iteration()
+        else:
+            if self._baked_iteration() != self._iter_baked:
+                raise _native.PbgError("PPO.iterate: a buffer the captured iteration reads has moved since the capture")
+            self._iter_graph.replay()
+            stats = self._stats_now()
         self.iteration += 1
         return stats
 
@@ -604,7 +850,7 @@ class PPO:
 
     def close(self):
         self.actor.attach_action_noise(None)
-        self._graph = None
-        for o in (self.actor, self.critic, self.noise, self.obs_stats, self.grad, self.adam):
+        self._graph = self._iter_graph = None
+        for o in (self.actor, self.critic, self.noise, self.obs_stats, self.grad, self.adam, self.perm):
             if o is not None:
                 o.close()

@@ -99,6 +99,58 @@ def _normal_rows(width: int, seed: int, row0: int, n_rows: int, third: int, tag:
     return np.ascontiguousarray(out.reshape(n_rows, 4 * nb)[:, :width])
 
 
+def fmix32(h):
+    """murmur3's finaliser on a uint32 array (csrc/sim_params.h's contact hash ends with it)."""
+    h = np.asarray(h, dtype=np.uint32).copy()
+    h ^= h >> np.uint32(16)
+    h *= np.uint32(0x85EBCA6B)
+    h ^= h >> np.uint32(13)
+    h *= np.uint32(0xC2B2AE35)
+    h ^= h >> np.uint32(16)
+    return h
+
+
+def permutation_keys(seed: int, counter: int) -> np.ndarray:
+    """uint32 [8]: the round keys of ``permutation``: the four words of Philox4x32-10 (key = seed) at counter
+    (counter, 0, 0, 0x9E), then the four at (counter, 1, 0, 0x9E)."""
+    c = int(counter) & 0xFFFFFFFF
+    key = (seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF)
+    ctr = np.array([[c, 0, 0, 0x9E], [c, 1, 0, 0x9E]], dtype=np.uint32)
+    return philox4x32_10(ctr, key).reshape(8)
+
+
+def permutation(B: int, seed: int, counter: int) -> np.ndarray:
+    """int64 [B]: pbg_perm_fill's permutation of 0 .. B - 1 (include/pbg.h "Counter-based permutations"): an
+    eight-round Feistel network on the smallest even number of bits that holds B, keyed by ``permutation_keys``,
+    cycle-walked into range.  The same bits as the device and as pbg_perm_host."""
+    B = int(B)
+    if not 1 <= B <= 2 ** 31 - 1:
+        raise ValueError(f"permutation: B = {B} outside 1 .. 2^31 - 1")
+    k = max(2, (B - 1).bit_length())
+    k += k & 1
+    half = np.uint32(k // 2)
+    mask = np.uint32((1 << (k // 2)) - 1)
+    K = permutation_keys(seed, counter)
+    x = np.arange(B, dtype=np.uint32)
+    todo = np.arange(B)
+    with np.errstate(over="ignore"):
+        while todo.size:
+            v = x[todo]
+            L, R = v >> half, v & mask
+            for r in range(8):
+                L, R = R, L ^ (fmix32(R + K[r]) & mask)
+            v = (L << half) | R
+            x[todo] = v
+            todo = todo[v >= np.uint32(B)]
+    return x.astype(np.int64)
+
+
+def lr_linear(it: int, n_total: int, lr0: float) -> float:
+    """pbg_ppo_lr_linear's value: ``lr0 * (1 - min(it, n_total) / n_total)`` in float64, the same bits."""
+    q = np.float64(min(int(it), int(n_total))) / np.float64(int(n_total))
+    return float(np.float64(lr0) * (np.float64(1.0) - q))
+
+
 def action_noise(act_dim: int, seed: int, n: int, env_offset: int, step: int) -> np.ndarray:
     """float32 [n, act_dim]: the action noise of pbg_action_noise_fill (include/pbg.h "Stochastic Gaussian
     actions": the Noise contract's block at counter = (block of 4 components, env_offset + e, step, 0xAC)),

@@ -7,12 +7,16 @@ as an npz that tools/enjoy.py and MLPPolicy.from_npz load.
          [--lr 3e-3] [--epochs 4] [--minibatches 4] [--gamma 0.99] [--lam 0.95] [--clip 0.2] [--log-std -0.5]
          [--ent-coef 0.0] [--vf-coef 0.5] [--seed 0] [--precision 64] [--hidden 64 64] [--out ppo_policy.npz]
          [--obs-norm] [--obs-clip 5.0] [--eval-envs 256] [--eval-steps 200] [--eval-every 1] [--curve curve.json]
-         [--backward hip] [--optimizer hip] [--graph]
+         [--backward hip] [--optimizer hip] [--graph [iteration]] [--permutation device]
+         [--lr-schedule linear --schedule-iterations N]
 
 --obs-norm trains under running observation normalisation (PPO(obs_norm=True)) and saves the final normaliser
 in the npz (obs_mean, obs_inv_std, obs_clip); --curve writes the per-iteration evaluation as JSON.  --optimizer hip
 (with --backward hip) also runs the advantage normaliser, the gradient clipping and Adam as the library's launches
-(pbg_adv_norm, pbg_ppo_opt), and --graph replays the whole update as one captured graph.
+(pbg_adv_norm, pbg_ppo_opt), and --graph replays the whole update as one captured graph.  --permutation device draws
+the minibatch permutations on the device (pbg_perm_fill, a function of the seed that numpy restates), --lr-schedule
+linear anneals the learning rate to zero over --schedule-iterations iterations from a device-side iteration count, and
+--graph iteration (needs --permutation device) replays a whole iteration, rollout included, as one captured graph.
 
 Per evaluated iteration it prints the noise-free mean policy's mean first-episode return and length over
 --eval-envs envs of a separate batch without auto-reset."""
@@ -54,7 +58,19 @@ def main():
                     help="the update's gradient: torch autograd, or the HIP backward pass (pbg_ppo_grad)")
     ap.add_argument("--optimizer", choices=("torch", "hip"), default="torch",
                     help="gradient clipping and Adam: torch, or the HIP step (pbg_ppo_opt; needs --backward hip)")
-    ap.add_argument("--graph", action="store_true", help="capture the update as one graph (needs --optimizer hip)")
+    def graph_arg(s):
+        if s != "iteration":
+            raise argparse.ArgumentTypeError("--graph takes no value (the update as one graph) or 'iteration'")
+        return s
+
+    ap.add_argument("--graph", nargs="?", const=True, default=False, type=graph_arg,
+                    help="capture the update as one graph (needs --optimizer hip); --graph iteration: the whole "
+                         "iteration (needs --permutation device)")
+    ap.add_argument("--permutation", choices=("torch", "device"), default="torch",
+                    help="the minibatch permutations: torch.randperm, or pbg_perm_fill (needs --optimizer hip)")
+    ap.add_argument("--lr-schedule", choices=("linear",), default=None,
+                    help="anneal the learning rate on the device (needs --optimizer hip and --schedule-iterations)")
+    ap.add_argument("--schedule-iterations", type=int, default=None, help="iterations over which lr reaches zero")
     ap.add_argument("--curve", default=None, help="write the per-iteration evaluation here (JSON)")
     args = ap.parse_args()
 
@@ -70,11 +86,13 @@ def main():
     ppo = PPO(env, hidden=args.hidden, steps=args.steps, seed=args.seed, gamma=args.gamma, lam=args.lam, clip=args.clip,
               lr=args.lr, epochs=args.epochs, minibatches=args.minibatches, vf_coef=args.vf_coef, ent_coef=args.ent_coef,
               log_std=args.log_std, obs_norm=args.obs_norm, obs_clip=args.obs_clip, backward=args.backward,
-              optimizer=args.optimizer, graph=args.graph)
+              optimizer=args.optimizer, graph=args.graph, permutation=args.permutation, lr_schedule=args.lr_schedule,
+              schedule_iterations=args.schedule_iterations)
     print(f"{args.env_id} (float{args.precision}): {args.envs} envs x {args.steps} steps per iteration, actor MLP "
           f"{ppo.actor_dims}, lr {args.lr}, {args.epochs} epochs x {args.minibatches} minibatches, observation "
           f"normalisation {'on' if args.obs_norm else 'off'}, backward pass {args.backward}, optimizer "
-          f"{args.optimizer}{' (one graph)' if args.graph else ''}")
+          f"{args.optimizer}{' (one graph per iteration)' if args.graph == 'iteration' else ' (one graph)' if args.graph else ''}, "
+          f"permutation {args.permutation}, lr schedule {args.lr_schedule}")
     curve = []
 
     def report(it):
