@@ -620,6 +620,59 @@ void pbg_ppo_grad_destroy(pbg_ppo_grad* g);
 int pbg_ppo_grad_run(pbg_ppo_grad* g, const pbg_ppo_grad_io_t* io, void* stream);
 int pbg_ppo_grad_host(int obs_dim, int h1, int h2, int act_dim, const pbg_ppo_grad_io_t* io);
 
+/* The matrix-core path (appended to this block; nothing above changes).  An object created by
+ * pbg_ppo_grad_create_ex with path = PBG_PPO_GRAD_MFMA computes the same function with the six products of each
+ * network (three forward, two back-propagations, three weight gradients) on gfx950's exact float32 matrix instruction
+ * v_mfma_f32_16x16x4_f32, whose result is bit for bit a k-ordered fmaf chain from its C input with one rounding per
+ * product.  pbg_ppo_grad_run, pbg_ppo_grad_io_t, pbg_ppo_grad_destroy and pbg_ppo_grad_host serve both paths; the
+ * host twin, whose backward is a float64 sum over rows, is the twin of both.
+ *
+ * Forward.  mu, v, v_out, logp_out and the ReLU masks are those of the Numeric contract's k-ascending chain from the
+ * bias: the instruction takes the bias as C and four consecutive k per issue in ascending order.  They equal the FMA
+ * path's and pbg_population_act's values.  A K that is no multiple of 4 is padded with zeros on both operands:
+ * fmaf(0, 0, acc) returns acc, except that it turns an acc of -0 into +0.  An output is -0 only when its bias and
+ * every one of its products are -0, and the two zeros compare equal; that sign is the one difference.
+ *
+ * Per-row part.  ppo_actor_row, ppo_critic_row and ppo_stats_row of the FMA path, unchanged: float64 per row,
+ * rounded once.  `stats` keeps its second, float64 forward of the actor (on the vector unit) and its contract.
+ *
+ * Backward, the order of every sum.  The minibatch is cut into tiles of 16 consecutive rows; the launch has
+ * G = min(number of tiles, the object's workgroup count) workgroups and workgroup b owns the tiles b, b + G, ...
+ * The workgroup count is fixed at creation: min(ceil(max_rows / 16), 256, as many partials as fit 128 MiB), at least
+ * 1.  A workgroup does the actor for all its tiles, then the critic for all its tiles.  A back-propagated activation
+ * is one float32 fmaf chain over the layer's outputs j in ascending order started from zero (the FMA path's chain,
+ * j padded to a multiple of 4 with zeros).  A weight-gradient element is ONE float32 fmaf chain started from zero
+ * over all the rows of all the workgroup's tiles: tiles in ascending order, and inside a tile the rows in the order
+ * e = 0, 4, 8, 12, 1, 5, 9, 13, 2, 6, 10, 14, 3, 7, 11, 15 (rows past the minibatch's end enter as zeros); there is
+ * no per-tile value that is added afterwards.  A bias or log_std element is, as on the FMA path, the float32 sum over
+ * the tile's rows ascending from zero, added in float32 onto the workgroup's running value in ascending tile order.
+ * The float32 values of the G workgroups meet in the reduction, which adds them in ascending b in float64 and rounds
+ * once (grad_log_std: after subtracting ent_coef in float64).  The four stats are summed as on the FMA path.
+ *
+ * Where the chain lives.  Every 16 x 16 patch of a weight gradient belongs to one wave of its workgroup.  For
+ * obs_dim <= 80, h1 <= 256, h2 <= 128 and act_dim <= 32 (every network shape the project ships a policy for; at most
+ * 224 patches a network) the chains stay in accumulator registers over all the workgroup's tiles and are stored
+ * once; for every other shape (up to 576 patches at (256, 256, 256, 64); (44, 256, 256, 17) with 336 is one) a
+ * chain's running value is stored to the workgroup's own partial after each tile and loaded back as the C input of
+ * the next.  A float32 store and load is exact, so which route a shape takes does not enter its bits.
+ *
+ * Determinism.  There are no atomics.  The result is a function of the inputs, of max_rows and of the path alone:
+ * the same bits on every call, on every stream and inside a replayed graph. */
+#define PBG_PPO_GRAD_FMA 0
+#define PBG_PPO_GRAD_MFMA 1
+
+/* Versioned by struct_size like the other option structs. */
+typedef struct {
+  uint32_t struct_size;
+  int path;  /* PBG_PPO_GRAD_FMA or PBG_PPO_GRAD_MFMA */
+} pbg_ppo_grad_opts_t;
+
+/* opts NULL or path PBG_PPO_GRAD_FMA: exactly pbg_ppo_grad_create.  PBG_E_ARG (before any HIP call) for an unknown
+ * path, a struct_size that is not the struct's, and everything pbg_ppo_grad_create refuses; *out is NULL after every
+ * failure.  The matrix-core path accepts every shape pbg_policy_create accepts and every mb_rows >= 1. */
+int pbg_ppo_grad_create_ex(int device, int obs_dim, int h1, int h2, int act_dim, int max_rows,
+                           const pbg_ppo_grad_opts_t* opts, pbg_ppo_grad** out);
+
 /* ---- PPO optimiser step (appended; nothing above changes) ----
  * What a PPO minibatch step does besides the gradient: the advantage normaliser's (shift, scale) pair, and Adam
  * (Kingma & Ba 2015) with global-norm gradient clipping.  All arithmetic below is IEEE float64 add, multiply,

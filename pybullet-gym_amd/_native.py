@@ -72,6 +72,17 @@ class RolloutIO(ctypes.Structure):
         super().__init__(struct_size=ctypes.sizeof(RolloutIO), **kw)
 
 
+PPO_GRAD_FMA, PPO_GRAD_MFMA = 0, 1  # PBG_PPO_GRAD_FMA, PBG_PPO_GRAD_MFMA
+
+
+class PPOGradOpts(ctypes.Structure):
+    """pbg_ppo_grad_opts_t (pbg_ppo_grad_create_ex): versioned by struct_size."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("path", ctypes.c_int)]
+
+    def __init__(self, **kw):
+        super().__init__(struct_size=ctypes.sizeof(PPOGradOpts), **kw)
+
+
 class PPOGradIO(ctypes.Structure):
     """pbg_ppo_grad_io_t (pbg_ppo_grad_run, pbg_ppo_grad_host): versioned by struct_size."""
     _fields_ = [("struct_size", ctypes.c_uint32), ("batch_rows", ctypes.c_int), ("mb_rows", ctypes.c_int),
@@ -226,6 +237,9 @@ def lib():
         for f in PPO_GRAD_EXPORTED:
             if f != "pbg_ppo_grad_destroy":
                 getattr(L, f).restype = I
+    if hasattr(L, "pbg_ppo_grad_create_ex"):  # its matrix-core path
+        L.pbg_ppo_grad_create_ex.argtypes = [I, I, I, I, I, I, ctypes.POINTER(PPOGradOpts), ctypes.POINTER(H)]
+        L.pbg_ppo_grad_create_ex.restype = I
     if hasattr(L, "pbg_ppo_opt_create"):  # the advantage normaliser and the clip + Adam step
         I64P = ctypes.POINTER(ctypes.c_int64)
         L.pbg_adv_norm.argtypes = [I, I, P, P, P, P]
@@ -275,6 +289,7 @@ ACTION_NOISE_EXPORTED = ("pbg_action_noise_create", "pbg_action_noise_destroy", 
                          "pbg_action_noise_fill", "pbg_action_noise_host", "pbg_policy_attach_action_noise",
                          "pbg_population_attach_action_noise", "pbg_gae", "pbg_gae_host")
 PPO_GRAD_EXPORTED = ("pbg_ppo_grad_create", "pbg_ppo_grad_destroy", "pbg_ppo_grad_run", "pbg_ppo_grad_host")
+PPO_GRAD_EX_EXPORTED = ("pbg_ppo_grad_create_ex",)
 PPO_OPT_EXPORTED = ("pbg_adv_norm", "pbg_adv_norm_host", "pbg_ppo_opt_create", "pbg_ppo_opt_destroy", "pbg_ppo_opt_step",
                     "pbg_ppo_opt_reset", "pbg_ppo_opt_get_state", "pbg_ppo_opt_host")
 PERM_EXPORTED = ("pbg_perm_create", "pbg_perm_destroy", "pbg_perm_fill", "pbg_perm_set_counter", "pbg_perm_get_counter",
@@ -284,7 +299,7 @@ EXPORTED = ("pbg_create", "pbg_create_debug", "pbg_create_ex", "pbg_create_v2", 
             "pbg_destroy", "pbg_info", "pbg_reset", "pbg_step", "pbg_step_ex",
             "pbg_get_state", "pbg_set_state", "pbg_pack_record_sizes", "pbg_pack", "pbg_sample_actions",
             "pbg_debug_poison", "pbg_last_error") + POLICY_EXPORTED + POPULATION_EXPORTED + OBS_NORM_EXPORTED + \
-    ACTION_NOISE_EXPORTED + PPO_GRAD_EXPORTED + PPO_OPT_EXPORTED + PERM_EXPORTED
+    ACTION_NOISE_EXPORTED + PPO_GRAD_EXPORTED + PPO_OPT_EXPORTED + PERM_EXPORTED + PPO_GRAD_EX_EXPORTED
 
 
 def check(rc: int, what: str):

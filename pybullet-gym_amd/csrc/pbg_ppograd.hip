@@ -20,53 +20,17 @@
 
 #include <new>
 
-#include "pbg_policy_dev.h"
-
-struct pbg_ppo_grad {
-  int device, obs_dim, h1, h2, act_dim, max_rows;
-  int Da, Dc, Dtot;   // Dtot = Da + Dc + act_dim: a workgroup's float32 partial
-  int n_wg;           // workgroups of the widest launch
-  float* part;        // device [n_wg, Dtot]
-  double* part_stats; // device [n_wg, 4], the same allocation
-};
+#include "pbg_ppograd_dev.h"
 
 namespace {
 
 using namespace pbg::policy;
+using namespace pbg::ppograd;  // Args, gather_tile, actor_forward64
 using pbg::DeviceGuard;
 
 constexpr int MAX_WG = 512;                       // two workgroups per CU
 constexpr size_t MAX_WS_BYTES = (size_t)128 << 20;
 constexpr int RK = 16;                            // REG: weight-gradient accumulators per lane and layer
-constexpr int NA_MAX = PBG_POLICY_MAX_ACT;
-
-struct Args {
-  const float *theta_a, *theta_c, *log_std;
-  Norm nm;
-  const float *obs, *act, *logp_old, *adv, *ret;
-  const int64_t* idx;
-  const float* adv_norm;
-  float clip_eps, vf_coef;
-  int Bm, obs_dim, h1, h2, A, Da, Dtot;
-  float* part;
-  double* part_stats;
-  float *logp_out, *v_out;
-};
-
-// the tile's rows, gathered: row e is batch row idx[row0 + e] (idx NULL: row0 + e) -> xT [K0][PT], zero past `rows`
-__device__ __forceinline__ void gather_tile(int K0, const int64_t* __restrict__ idx, int row0, int rows,
-                                            const float* __restrict__ obs, const Norm nm, float* xT) {
-  for (int i = threadIdx.x; i < PT * K0; i += PB) {
-    const int e = i / K0, k = i - e * K0;
-    float v = 0.f;
-    if (e < rows) {
-      const size_t r = idx ? (size_t)idx[row0 + e] : (size_t)(row0 + e);
-      v = obs[r * K0 + k];
-      if (nm.mean) v = normalise(v, nm.mean[k], nm.inv_std[k], nm.clip);
-    }
-    xT[k * PT + e] = v;
-  }
-}
 
 // out[k][e] = act[k][e] > 0 ? sum_j W[k][j] dy[j][e] : 0 for this lane's row k and envs e0 .. e0 + EL
 template <int EL>
@@ -200,77 +164,6 @@ __device__ __forceinline__ void zero(NetAcc& a) {
 struct Planes {
   float *X, *H1, *H2, *E, *D, *D2;
 };
-
-// ---- the statistics' float64 forward of the actor, R rows of the tile at a time in [width][R] double planes laid
-// over float [PD][PT] planes: the whole tile when obs_dim, h1, h2 <= PD / 2, half a tile otherwise
-static_assert(PD * (PT / 2) * sizeof(double) == PD * PT * sizeof(float), "a double half-tile plane fits a float plane");
-
-// one layer for this lane's column j and rows e0 .. e0 + EL of the pass: pbg_policy_dev.h's chain in float64;
-// xT [K][R] -> yT [H][YS]
-template <int EL, int R, int YS>
-__device__ __forceinline__ void layer64_cols(const float* __restrict__ W, const float* __restrict__ bias, int K, int H, int j,
-                                             int e0, bool relu, const double* xT, double* yT) {
-  double acc[EL];
-  const double bj = (double)bias[j];
-#pragma unroll
-  for (int e = 0; e < EL; e++) acc[e] = bj;
-  const float* wp = W + j;
-#pragma unroll 4
-  for (int k = 0; k < K; k++) {
-    const double w = (double)wp[(size_t)k * H];
-#pragma unroll
-    for (int e = 0; e < EL; e++) acc[e] = __builtin_fma(xT[k * R + e0 + e], w, acc[e]);
-  }
-#pragma unroll
-  for (int e = 0; e < EL; e++) yT[j * YS + e0 + e] = relu && acc[e] < 0.0 ? 0.0 : acc[e];
-}
-
-// `layer`'s split of the columns over the lanes, for R rows
-template <int R, int YS>
-__device__ __forceinline__ void layer64(const float* __restrict__ W, const float* __restrict__ bias, int K, int H, bool relu,
-                                        const double* xT, double* yT) {
-  const int tid = threadIdx.x;
-  if (H <= 64) {
-    const int j = tid & 63, g = tid >> 6;
-    if (j < H) layer64_cols<R / 4, R, YS>(W, bias, K, H, j, (R / 4) * g, relu, xT, yT);
-  } else if (H <= 128) {
-    const int j = tid & 127, g = tid >> 7;
-    if (j < H) layer64_cols<R / 2, R, YS>(W, bias, K, H, j, (R / 2) * g, relu, xT, yT);
-  } else {
-    if (tid < H) layer64_cols<R, R, YS>(W, bias, K, H, tid, 0, relu, xT, yT);
-  }
-}
-
-// The float64 means of the tile's rows -> mu64 [A][PT].  x, h1, h2: three idle float planes.  Called behind a
-// barrier; one barrier closes it.
-template <int R>
-__device__ __forceinline__ void actor_forward64(const Weights& P, const Norm nm, const int64_t* __restrict__ idx, int row0,
-                                                int rows, const float* __restrict__ obs, float* x, float* h1, float* h2,
-                                                double* mu64) {
-  double* dX = reinterpret_cast<double*>(x);
-  double* dH1 = reinterpret_cast<double*>(h1);
-  double* dH2 = reinterpret_cast<double*>(h2);
-  const int K0 = P.obs_dim;
-  for (int p = 0; p * R < rows; p++) {  // uniform over the workgroup
-    for (int i = threadIdx.x; i < R * K0; i += PB) {
-      const int e = i / K0, k = i - e * K0, row = p * R + e;
-      double v = 0.0;
-      if (row < rows) {
-        const size_t r = idx ? (size_t)idx[row0 + row] : (size_t)(row0 + row);
-        const float o = obs[r * K0 + k];
-        v = nm.mean ? normalise64(o, nm.mean[k], nm.inv_std[k], nm.clip) : (double)o;
-      }
-      dX[k * R + e] = v;
-    }
-    __syncthreads();
-    layer64<R, R>(P.w1, P.b1, K0, P.h1, true, dX, dH1);
-    __syncthreads();
-    layer64<R, R>(P.w2, P.b2, P.h1, P.h2, true, dH1, dH2);
-    __syncthreads();
-    layer64<R, PT>(P.w3, P.b3, P.h2, P.act_dim, false, dH2, mu64 + p * R);
-  }
-  __syncthreads();
-}
 
 // forward of one network on the tile in L.X: H1, H2 and the outputs D [NA][PT]
 __device__ __forceinline__ void net_forward(const Weights& P, const Planes& L) {
@@ -476,22 +369,23 @@ int check_io(const char* who, const pbg_ppo_grad_io_t* uio, pbg_ppo_grad_io_t* i
   return PBG_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int pbg_ppo_grad_create(int device, int obs_dim, int h1, int h2, int act_dim, int max_rows, pbg_ppo_grad** out) {
-  if (!out) return pbg::capi_fail(PBG_E_ARG, "pbg_ppo_grad_create: out is NULL");
-  *out = nullptr;
-  if (const int rc = check_dims("pbg_ppo_grad_create", obs_dim, h1, h2, act_dim)) return rc;
+// pbg_ppo_grad_create and pbg_ppo_grad_create_ex behind their own checks of `out` and `opts`; max_wg: the path's
+// workgroup cap
+int create_object(const char* who, int device, int obs_dim, int h1, int h2, int act_dim, int max_rows, int path, int max_wg,
+                  pbg_ppo_grad** out) {
+  char msg[160];
+  if (const int rc = check_dims(who, obs_dim, h1, h2, act_dim)) return rc;
   if (max_rows < 1 || device < 0) {
-    char msg[128];
-    snprintf(msg, sizeof(msg), "pbg_ppo_grad_create: max_rows %d < 1 or device %d < 0", max_rows, device);
+    snprintf(msg, sizeof(msg), "%s: max_rows %d < 1 or device %d < 0", who, max_rows, device);
     return pbg::capi_fail(PBG_E_ARG, msg);
   }
-  if (const int rc = check_device("pbg_ppo_grad_create", device)) return rc;
+  if (const int rc = check_device(who, device)) return rc;
   pbg_ppo_grad* g = new (std::nothrow) pbg_ppo_grad();
-  if (!g) return pbg::capi_fail(PBG_E_NOMEM, "pbg_ppo_grad_create: out of host memory");
+  if (!g) {
+    snprintf(msg, sizeof(msg), "%s: out of host memory", who);
+    return pbg::capi_fail(PBG_E_NOMEM, msg);
+  }
+  g->path = path;
   g->device = device;
   g->obs_dim = obs_dim; g->h1 = h1; g->h2 = h2; g->act_dim = act_dim;
   g->max_rows = max_rows;
@@ -500,7 +394,7 @@ int pbg_ppo_grad_create(int device, int obs_dim, int h1, int h2, int act_dim, in
   g->Dtot = g->Da + g->Dc + act_dim;
   const size_t per_wg = (size_t)g->Dtot * sizeof(float) + 4 * sizeof(double);
   long long n = ((long long)max_rows + PT - 1) / PT;
-  if (n > MAX_WG) n = MAX_WG;
+  if (n > max_wg) n = max_wg;
   if (n > (long long)(MAX_WS_BYTES / per_wg)) n = (long long)(MAX_WS_BYTES / per_wg);
   g->n_wg = n < 1 ? 1 : (int)n;
   g->part = nullptr;
@@ -513,12 +407,46 @@ int pbg_ppo_grad_create(int device, int obs_dim, int h1, int h2, int act_dim, in
   if (e) {
     if (ws) (void)hipFree(ws);
     delete g;
-    return hip_fail(e, "pbg_ppo_grad_create: workspace");
+    snprintf(msg, sizeof(msg), "%s: workspace", who);
+    return hip_fail(e, msg);
   }
   g->part_stats = reinterpret_cast<double*>(ws);
   g->part = reinterpret_cast<float*>(g->part_stats + (size_t)g->n_wg * 4);
   *out = g;
   return PBG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pbg_ppo_grad_create(int device, int obs_dim, int h1, int h2, int act_dim, int max_rows, pbg_ppo_grad** out) {
+  if (!out) return pbg::capi_fail(PBG_E_ARG, "pbg_ppo_grad_create: out is NULL");
+  *out = nullptr;
+  return create_object("pbg_ppo_grad_create", device, obs_dim, h1, h2, act_dim, max_rows, PBG_PPO_GRAD_FMA, MAX_WG, out);
+}
+
+int pbg_ppo_grad_create_ex(int device, int obs_dim, int h1, int h2, int act_dim, int max_rows, const pbg_ppo_grad_opts_t* opts,
+                           pbg_ppo_grad** out) {
+  if (!out) return pbg::capi_fail(PBG_E_ARG, "pbg_ppo_grad_create_ex: out is NULL");
+  *out = nullptr;
+  int path = PBG_PPO_GRAD_FMA;
+  if (opts) {
+    char msg[128];
+    if (opts->struct_size != (uint32_t)sizeof(pbg_ppo_grad_opts_t)) {
+      snprintf(msg, sizeof(msg), "pbg_ppo_grad_create_ex: opts->struct_size %u is not a pbg_ppo_grad_opts_t size",
+               opts->struct_size);
+      return pbg::capi_fail(PBG_E_ARG, msg);
+    }
+    path = opts->path;
+    if (path != PBG_PPO_GRAD_FMA && path != PBG_PPO_GRAD_MFMA) {
+      snprintf(msg, sizeof(msg), "pbg_ppo_grad_create_ex: opts->path %d is neither PBG_PPO_GRAD_FMA nor PBG_PPO_GRAD_MFMA", path);
+      return pbg::capi_fail(PBG_E_ARG, msg);
+    }
+  }
+  if (path == PBG_PPO_GRAD_FMA)
+    return create_object("pbg_ppo_grad_create", device, obs_dim, h1, h2, act_dim, max_rows, path, MAX_WG, out);
+  return create_object("pbg_ppo_grad_create_ex", device, obs_dim, h1, h2, act_dim, max_rows, path, MFMA_MAX_WG, out);
 }
 
 void pbg_ppo_grad_destroy(pbg_ppo_grad* g) {
@@ -553,11 +481,16 @@ int pbg_ppo_grad_run(pbg_ppo_grad* g, const pbg_ppo_grad_io_t* uio, void* stream
   const int ntiles = (io.mb_rows + PT - 1) / PT;
   const int G = ntiles < g->n_wg ? ntiles : g->n_wg;
   const bool reg = g->obs_dim <= 64 && g->h1 <= 64 && g->h2 <= 64;
-  if (reg)
-    hipLaunchKernelGGL(ppograd_tiles_kernel<true>, dim3((unsigned)G), dim3(PB), 0, s, a);
-  else
-    hipLaunchKernelGGL(ppograd_tiles_kernel<false>, dim3((unsigned)G), dim3(PB), 0, s, a);
-  int e = (int)hipGetLastError();
+  int e;
+  if (g->path == PBG_PPO_GRAD_MFMA) {
+    e = launch_tiles_mfma(a, G, s);
+  } else {
+    if (reg)
+      hipLaunchKernelGGL(ppograd_tiles_kernel<true>, dim3((unsigned)G), dim3(PB), 0, s, a);
+    else
+      hipLaunchKernelGGL(ppograd_tiles_kernel<false>, dim3((unsigned)G), dim3(PB), 0, s, a);
+    e = (int)hipGetLastError();
+  }
   if (e) return hip_fail(e, "ppograd_tiles_kernel launch");
   hipLaunchKernelGGL(ppograd_reduce_kernel, dim3((unsigned)((g->Dtot + 255) / 256)), dim3(256), 0, s, g->part, g->part_stats, G,
                      g->Da, g->Dc, g->Dtot, io.ent_coef, io.mb_rows, io.grad_actor, io.grad_critic, io.grad_log_std, io.stats);

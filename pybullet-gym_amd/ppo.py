@@ -83,11 +83,19 @@ class PPOGrad:
     """The gradient of the clipped-surrogate loss of one minibatch as two HIP launches (include/pbg.h "PPO
     gradient", pbg_ppo_grad).  ``dims = (obs_dim, h1, h2, act_dim)``: the actor's; the critic is obs_dim -> h1 -> h2
     -> 1.  ``device``: a GPU, or ``None`` / ``"cpu"`` for the host twin (pbg_ppo_grad_host, numpy arrays, no GPU).
-    ``max_rows``: the largest minibatch ``run`` will see (it sizes the reduction's workspace)."""
+    ``max_rows``: the largest minibatch ``run`` will see (it sizes the reduction's workspace).  ``path``: ``"fma"``
+    (pbg_ppo_grad_create) or ``"mfma"``, the matrix-core path for wide networks (pbg_ppo_grad_create_ex with
+    PBG_PPO_GRAD_MFMA: the same forward bits, another order of the backward's sums); the host twin serves both and
+    computes the same thing for either."""
 
-    def __init__(self, dims, max_rows: int, device=None):
+    PATHS = {"fma": _native.PPO_GRAD_FMA, "mfma": _native.PPO_GRAD_MFMA}
+
+    def __init__(self, dims, max_rows: int, device=None, path: str = "fma"):
         if not hasattr(_native.lib(), "pbg_ppo_grad_create"):
             raise _native.PbgError(f"{_native.LIB_PATH} has no pbg_ppo_grad_create: a build without the PPO gradient")
+        if path not in self.PATHS:
+            raise _native.PbgError(f"PPOGrad: path must be 'fma' or 'mfma', got {path!r}")
+        self.path = path
         self.dims = tuple(int(d) for d in dims)
         if len(self.dims) != 4:
             raise _native.PbgError(f"PPOGrad: dims must be (obs_dim, h1, h2, act_dim), got {dims!r}")
@@ -107,8 +115,15 @@ class PPOGrad:
             raise _native.PbgError(f"PPOGrad: device must be a GPU or None, got {device!r}")
         index = self.device.index if self.device.index is not None else torch.cuda.current_device()
         self.device = torch.device("cuda", index)
-        _native.check(_native.lib().pbg_ppo_grad_create(index, o, h1, h2, a, self.max_rows, ctypes.byref(self._h)),
-                      "pbg_ppo_grad_create")
+        if path == "fma":
+            _native.check(_native.lib().pbg_ppo_grad_create(index, o, h1, h2, a, self.max_rows, ctypes.byref(self._h)),
+                          "pbg_ppo_grad_create")
+        else:
+            if not hasattr(_native.lib(), "pbg_ppo_grad_create_ex"):
+                raise _native.PbgError(f"{_native.LIB_PATH} has no pbg_ppo_grad_create_ex: a build without the matrix-core path")
+            opts = _native.PPOGradOpts(path=self.PATHS[path])
+            _native.check(_native.lib().pbg_ppo_grad_create_ex(index, o, h1, h2, a, self.max_rows, ctypes.byref(opts),
+                                                               ctypes.byref(self._h)), "pbg_ppo_grad_create_ex")
 
     def _ok(self, t, shape, dt):
         if self.host:
@@ -505,13 +520,17 @@ class PPO:
     without synchronising.  The actor kernel takes the statistics and the noise as launch arguments, so the graph bakes
     them: what is attached on the host at replay time does not matter, and ``evaluate()`` between two replays (which
     detaches the noise on the host and never attaches the statistics) changes nothing the replay does.  The pointers the
-    graph baked are compared before each replay; a moved one raises ``PbgError``."""
+    graph baked are compared before each replay; a moved one raises ``PbgError``.
+
+    ``grad_path="mfma"`` (needs ``backward="hip"``): the gradient object is ``PPOGrad(path="mfma")``, the matrix-core
+    path for networks wider than 64; it works with every optimizer, graph and permutation setting above."""
 
     def __init__(self, env, hidden=(64, 64), steps: int = 64, seed: int = 0, gamma: float = 0.99, lam: float = 0.95,
                  clip: float = 0.2, lr: float = 3e-4, epochs: int = 4, minibatches: int = 4, vf_coef: float = 0.5,
                  ent_coef: float = 0.0, log_std: float = -0.5, max_grad_norm: float = 0.5, norm_adv: bool = True,
                  obs_norm: bool = False, obs_clip: float = 5.0, backward: str = "torch", optimizer: str = "torch",
-                 graph=False, permutation: str = "torch", lr_schedule=None, schedule_iterations=None):
+                 graph=False, permutation: str = "torch", lr_schedule=None, schedule_iterations=None,
+                 grad_path: str = "fma"):
         n, dev = env.num_envs, env.device
         if backward not in ("torch", "hip"):
             raise _native.PbgError(f"PPO: backward must be 'torch' or 'hip', got {backward!r}")
@@ -537,7 +556,11 @@ class PPO:
                                    "optimizer='hip'")
         if lr_schedule is not None and (schedule_iterations is None or int(schedule_iterations) < 1):
             raise _native.PbgError(f"PPO: lr_schedule needs schedule_iterations >= 1, got {schedule_iterations!r}")
-        self.backward = backward
+        if grad_path not in PPOGrad.PATHS:
+            raise _native.PbgError(f"PPO: grad_path must be 'fma' or 'mfma', got {grad_path!r}")
+        if grad_path != "fma" and backward != "hip":
+            raise _native.PbgError("PPO: grad_path selects a path of pbg_ppo_grad: it needs backward='hip'")
+        self.backward, self.grad_path = backward, grad_path
         if n % 2 != 0 or not env.autoreset:
             raise _native.PbgError("PPO: the env must have an even number of envs (the actors are populations of one "
                                    "pair) and autoreset=True")
@@ -577,7 +600,7 @@ class PPO:
         self.grad = None
         if backward == "hip":
             # the gradient tensors pbg_ppo_grad writes, bound once to the parameters' .grad
-            self.grad = PPOGrad(self.actor_dims, (T * n) // self.minibatches, dev)
+            self.grad = PPOGrad(self.actor_dims, (T * n) // self.minibatches, dev, path=grad_path)
             for p in (self.actor_theta, self.critic_theta, self.log_std):
                 p.grad = torch.zeros_like(p.data)
             self._grad_stats = torch.zeros(4, dtype=torch.float64, device=dev)

@@ -1,19 +1,24 @@
 #!/usr/bin/env python3
-"""The PPO update's gradient: torch autograd beside pbg_ppo_grad.
+"""The PPO update's gradient: torch autograd beside pbg_ppo_grad (DESIGN.md sections 14 and 17).
 
-Two legs compute one minibatch's gradient from the same data, eager launches as the trainer issues them:
+Three legs compute one minibatch's gradient from the same data, eager launches as the trainer issues them:
 
-  torch  the body of PPO.update from the gather to loss.backward() (ppo.py's torch path)
-  hip    PPOGrad.run: the tile kernel and the reduction (plus the two torch reductions that form adv_norm)
+  torch     the body of PPO.update from the gather to loss.backward() (ppo.py's torch path)
+  hip       PPOGrad.run: the tile kernel and the reduction (plus the two torch reductions that form adv_norm)
+  hip_mfma  the same with PPOGrad(path="mfma"), the matrix-core path
 
-at three shapes: the pendulum trainer's (5, 64, 64, 1) with 2,048 rows of 8,192, Ant's (28, 64, 64, 8) with
-131,072 rows of 524,288, and (44, 256, 256, 17) with 16,384 rows of 65,536.  Then one whole PPO.iterate() of the
+at five shapes: the pendulum trainer's (5, 64, 64, 1) with 2,048 rows of 8,192, Ant's (28, 64, 64, 8) with
+131,072 rows of 524,288, (44, 256, 256, 17) with 16,384 rows of 65,536, and the two reference networks, Ant's
+(28, 128, 64, 8) with 131,072 rows of 524,288 and Humanoid's (44, 256, 128, 17) with 16,384 rows of 65,536.  Then
+(unless --skip-iterate) one whole PPO.iterate() of the
 pendulum trainer (256 envs x 32 steps, 4 epochs x 4 minibatches) in both modes.  Section 11's protocol: warm-up,
 five windows bracketed by device events (iterate: a host clock around a synchronise), the legs alternated per
 window, medians with [min, max].  The FLOP count is the algorithm's: per row and network 2 K H for each layer's
 forward, 2 K H for its weight gradient and 2 K H for the input gradient of layers two and three.
 
-  python tools/bench_ppo_update.py [--out profiles/ppo_grad.json]
+  python tools/bench_ppo_update.py [--out profiles/ppo_grad_mfma.json] [--shapes wide ant_ref ...] [--skip-iterate]
+
+profiles/ppo_grad.json is the record of the two-leg version of this tool (section 14) and is not rewritten.
 """
 from __future__ import annotations
 
@@ -29,7 +34,8 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 
 SHAPES = {"pendulum": ((5, 64, 64, 1), 8192, 2048), "ant": ((28, 64, 64, 8), 524288, 131072),
-          "wide": ((44, 256, 256, 17), 65536, 16384)}
+          "wide": ((44, 256, 256, 17), 65536, 16384), "ant_ref": ((28, 128, 64, 8), 524288, 131072),
+          "humanoid_ref": ((44, 256, 128, 17), 65536, 16384)}
 PEAK_FP32_TF = 157.0
 CLIP, VF_COEF, ENT_COEF = 0.2, 0.5, 0.0
 
@@ -86,22 +92,29 @@ def bench_shape(name, dims, B, Bm, args, dev):
         ret = (mlp_forward(theta_c, cd, obs).squeeze(1) + rnd(B)).contiguous()
     adv = rnd(B)
     idx = torch.randperm(B, device=dev, generator=gen)[:Bm].contiguous()
-    g = PPOGrad(dims, Bm, dev)
+    g, gm = PPOGrad(dims, Bm, dev), PPOGrad(dims, Bm, dev, path="mfma")
     ga, gc, gl = torch.zeros_like(theta_a.data), torch.zeros_like(theta_c.data), torch.zeros_like(log_std.data)
     stats = torch.zeros(4, dtype=torch.float64, device=dev)
 
-    def hip():
+    def hip(obj=g):
         a_mb = adv[idx]
         adv_norm = torch.stack((a_mb.mean(), 1.0 / (a_mb.std() + 1e-8)))
-        g.run(theta_a.data, theta_c.data, log_std.data, obs, act, logp_old, adv, ret, idx=idx, adv_norm=adv_norm, clip_eps=CLIP,
-              vf_coef=VF_COEF, ent_coef=ENT_COEF, grad_actor=ga, grad_critic=gc, grad_log_std=gl, stats=stats)
+        obj.run(theta_a.data, theta_c.data, log_std.data, obs, act, logp_old, adv, ret, idx=idx, adv_norm=adv_norm, clip_eps=CLIP,
+                vf_coef=VF_COEF, ent_coef=ENT_COEF, grad_actor=ga, grad_critic=gc, grad_log_std=gl, stats=stats)
 
-    legs = {"torch": lambda: torch_gradient(theta_a, theta_c, log_std, dims, obs, act, logp_old, adv, ret, idx), "hip": hip}
+    legs = {"torch": lambda: torch_gradient(theta_a, theta_c, log_std, dims, obs, act, logp_old, adv, ret, idx), "hip": hip,
+            "hip_mfma": lambda: hip(gm)}
+    rel = lambda: max(float((x - p.grad).abs().max() / p.grad.abs().max())  # noqa: E731
+                      for x, p in ((ga, theta_a), (gc, theta_c), (gl, log_std)))
     for _ in range(args.warmup):
         for f in legs.values():
             f()
+    # ga, gc, gl hold the last leg's result: the matrix-core path's; then the FMA path's once more
     torch.cuda.synchronize(dev)
-    diff = max(float((x - p.grad).abs().max() / p.grad.abs().max()) for x, p in ((ga, theta_a), (gc, theta_c), (gl, log_std)))
+    diff_mfma = rel()
+    hip()
+    torch.cuda.synchronize(dev)
+    diff = rel()
     stream = torch.cuda.current_stream(dev)
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     w = {leg: [] for leg in legs}
@@ -115,14 +128,18 @@ def bench_shape(name, dims, B, Bm, args, dev):
             torch.cuda.synchronize(dev)
             w[leg].append(e0.elapsed_time(e1) * 1e3 / args.calls)
     g.close()
+    gm.close()
     med = {k: statistics.median(v) for k, v in w.items()}
     fl = flops_per_row(dims) * Bm
     return {"dims": dims, "batch_rows": B, "minibatch_rows": Bm, "unit": "us per minibatch gradient", "windows": w, "median": med,
             "min": {k: min(v) for k, v in w.items()}, "max": {k: max(v) for k, v in w.items()},
-            "torch_over_hip": med["torch"] / med["hip"], "flops_per_minibatch": fl,
+            "torch_over_hip": med["torch"] / med["hip"], "torch_over_hip_mfma": med["torch"] / med["hip_mfma"],
+            "hip_over_hip_mfma": med["hip"] / med["hip_mfma"],
+            "hip_mfma_median_below_hip_window_minimum": med["hip_mfma"] < min(w["hip"]), "flops_per_minibatch": fl,
             "achieved_TFLOPs": {k: fl / (us * 1e-6) / 1e12 for k, us in med.items()},
             "share_of_fp32_peak": {k: fl / (us * 1e-6) / 1e12 / PEAK_FP32_TF for k, us in med.items()},
-            "max_relative_difference_of_the_gradients": diff, "calls_per_window": args.calls}
+            "max_relative_difference_of_the_gradients": diff,
+            "max_relative_difference_of_the_gradients_mfma": diff_mfma, "calls_per_window": args.calls}
 
 
 def bench_iterate(args, dev):
@@ -131,9 +148,10 @@ def bench_iterate(args, dev):
     from pybulletgym_amd.vec_env import VecEnv
     hp = dict(hidden=(64, 64), steps=32, lr=3e-3, epochs=4, minibatches=4, log_std=-0.5)
     tr = {}
-    for mode in ("torch", "hip"):
+    for mode in ("torch", "hip", "hip_mfma"):
         env = VecEnv("InvertedPendulumPyBulletEnv-v0", 256, device=dev, seed=0, autoreset=True, precision=64)
-        tr[mode] = (env, PPO(env, seed=0, backward=mode, **hp))
+        kw = dict(backward="hip", grad_path="mfma") if mode == "hip_mfma" else dict(backward=mode)
+        tr[mode] = (env, PPO(env, seed=0, **kw, **hp))
         for _ in range(3):
             tr[mode][1].iterate()
     w = {mode: [] for mode in tr}
@@ -156,12 +174,13 @@ def bench_iterate(args, dev):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "ppo_grad.json"))
+    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "ppo_grad_mfma.json"))
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--windows", type=int, default=5)
     ap.add_argument("--calls", type=int, default=20, help="gradient calls per timed window")
     ap.add_argument("--iterations", type=int, default=5, help="PPO.iterate() calls per timed window")
     ap.add_argument("--shapes", nargs="*", default=list(SHAPES))
+    ap.add_argument("--skip-iterate", action="store_true", help="the gradient legs only")
     args = ap.parse_args()
     import torch
     import pybulletgym_amd  # noqa: F401
@@ -171,11 +190,14 @@ def main():
         res["shapes"][name] = r = bench_shape(name, *SHAPES[name], args, dev)
         print(f"{name} {r['dims']} x {r['minibatch_rows']}: us median [min, max]  " + "  ".join(
             f"{k} {r['median'][k]:.1f} [{r['min'][k]:.1f}, {r['max'][k]:.1f}] ({r['achieved_TFLOPs'][k]:.2f} TF)"
-            for k in r["median"]) + f"  torch / hip {r['torch_over_hip']:.2f}  grad diff {r['max_relative_difference_of_the_gradients']:.1e}")
-    res["iterate"] = r = bench_iterate(args, dev)
-    print("PPO.iterate() ms median [min, max]  " + "  ".join(
-        f"{k} {r['median'][k]:.2f} [{r['min'][k]:.2f}, {r['max'][k]:.2f}]" for k in r["median"]) +
-        f"  torch / hip {r['torch_over_hip']:.2f}")
+            for k in r["median"]) + f"  torch / hip {r['torch_over_hip']:.2f}  torch / hip_mfma {r['torch_over_hip_mfma']:.2f}  "
+            f"grad diff {r['max_relative_difference_of_the_gradients']:.1e} (mfma {r['max_relative_difference_of_the_gradients_mfma']:.1e})",
+            flush=True)
+    if not args.skip_iterate:
+        res["iterate"] = r = bench_iterate(args, dev)
+        print("PPO.iterate() ms median [min, max]  " + "  ".join(
+            f"{k} {r['median'][k]:.2f} [{r['min'][k]:.2f}, {r['max'][k]:.2f}]" for k in r["median"]) +
+            f"  torch / hip {r['torch_over_hip']:.2f}")
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(res, f, indent=1)

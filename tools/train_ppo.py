@@ -8,7 +8,7 @@ as an npz that tools/enjoy.py and MLPPolicy.from_npz load.
          [--ent-coef 0.0] [--vf-coef 0.5] [--seed 0] [--precision 64] [--hidden 64 64] [--out ppo_policy.npz]
          [--obs-norm] [--obs-clip 5.0] [--eval-envs 256] [--eval-steps 200] [--eval-every 1] [--curve curve.json]
          [--backward hip] [--optimizer hip] [--graph [iteration]] [--permutation device]
-         [--lr-schedule linear --schedule-iterations N]
+         [--lr-schedule linear --schedule-iterations N] [--grad-path mfma]
 
 --obs-norm trains under running observation normalisation (PPO(obs_norm=True)) and saves the final normaliser
 in the npz (obs_mean, obs_inv_std, obs_clip); --curve writes the per-iteration evaluation as JSON.  --optimizer hip
@@ -17,6 +17,8 @@ in the npz (obs_mean, obs_inv_std, obs_clip); --curve writes the per-iteration e
 the minibatch permutations on the device (pbg_perm_fill, a function of the seed that numpy restates), --lr-schedule
 linear anneals the learning rate to zero over --schedule-iterations iterations from a device-side iteration count, and
 --graph iteration (needs --permutation device) replays a whole iteration, rollout included, as one captured graph.
+--grad-path mfma (with --backward hip) takes the gradient from the matrix-core path of pbg_ppo_grad, the one for hidden
+layers wider than 64.
 
 Per evaluated iteration it prints the noise-free mean policy's mean first-episode return and length over
 --eval-envs envs of a separate batch without auto-reset."""
@@ -71,6 +73,8 @@ def main():
     ap.add_argument("--lr-schedule", choices=("linear",), default=None,
                     help="anneal the learning rate on the device (needs --optimizer hip and --schedule-iterations)")
     ap.add_argument("--schedule-iterations", type=int, default=None, help="iterations over which lr reaches zero")
+    ap.add_argument("--grad-path", choices=("fma", "mfma"), default="fma",
+                    help="the path of pbg_ppo_grad: vector FMA, or the matrix cores for wide networks (needs --backward hip)")
     ap.add_argument("--curve", default=None, help="write the per-iteration evaluation here (JSON)")
     args = ap.parse_args()
 
@@ -87,12 +91,12 @@ def main():
               lr=args.lr, epochs=args.epochs, minibatches=args.minibatches, vf_coef=args.vf_coef, ent_coef=args.ent_coef,
               log_std=args.log_std, obs_norm=args.obs_norm, obs_clip=args.obs_clip, backward=args.backward,
               optimizer=args.optimizer, graph=args.graph, permutation=args.permutation, lr_schedule=args.lr_schedule,
-              schedule_iterations=args.schedule_iterations)
+              schedule_iterations=args.schedule_iterations, grad_path=args.grad_path)
     print(f"{args.env_id} (float{args.precision}): {args.envs} envs x {args.steps} steps per iteration, actor MLP "
           f"{ppo.actor_dims}, lr {args.lr}, {args.epochs} epochs x {args.minibatches} minibatches, observation "
           f"normalisation {'on' if args.obs_norm else 'off'}, backward pass {args.backward}, optimizer "
           f"{args.optimizer}{' (one graph per iteration)' if args.graph == 'iteration' else ' (one graph)' if args.graph else ''}, "
-          f"permutation {args.permutation}, lr schedule {args.lr_schedule}")
+          f"permutation {args.permutation}, lr schedule {args.lr_schedule}, gradient path {args.grad_path}")
     curve = []
 
     def report(it):
