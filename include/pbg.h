@@ -834,6 +834,52 @@ int pbg_perm_host(uint64_t seed, uint32_t counter, int n_rows, int n_perms, int6
 int pbg_ppo_lr_linear(const uint32_t* it, uint32_t n_total, double lr0, double* lr_out, void* stream);
 int pbg_ppo_lr_linear_host(const uint32_t* it, uint32_t n_total, double lr0, double* lr_out);
 
+/* ---- The PPO gradient as parts, and the statistics' slots (appended; nothing above changes) ----
+ * What a data-parallel learner needs to hold the one-device learner's bits.  A workgroup's partial of
+ * pbg_ppo_grad_run depends on its global index b and on the global workgroup count G (workgroup b owns the tiles
+ * b, b + G, ...), not on the launch it ran in or the device it ran on.  So a gradient can be cut into ranges of
+ * workgroups, each range run by its own launch (on its own device, given the same inputs), the partials brought
+ * into one [G, Dtot] buffer, and the unchanged reduction run over them.
+ *
+ * Contract.  For any cut of 0 .. G into consecutive ranges, pbg_ppo_grad_run_part for each range with part_out and
+ * part_stats_out at the range's first row of one [G, Dtot] / [G, 4] buffer, then pbg_ppo_grad_reduce over that
+ * buffer, leave in grad_actor, grad_critic, grad_log_std, stats, logp_out and v_out what pbg_ppo_grad_run leaves,
+ * bit for bit: on either path, on any stream and inside a replayed graph.  The parts may come from objects on
+ * several devices as long as the objects were created alike (dims, max_rows, path) and the inputs are equal.
+ *
+ * pbg_ppo_grad_geometry: host only, no HIP call.  *G_out = the G pbg_ppo_grad_run launches for mb_rows,
+ * min(ceil(mb_rows / 16), the object's workgroup count); *dtot_out = Dtot = Da + Dc + A, the floats of a partial.
+ * PBG_E_ARG for a NULL argument or mb_rows outside 1 .. max_rows. */
+int pbg_ppo_grad_geometry(const pbg_ppo_grad* g, int mb_rows, int* G_out, int64_t* dtot_out);
+/* One launch of wg_count workgroups on `stream`: the global workgroups wg_first .. wg_first + wg_count - 1 of the
+ * G that io->mb_rows implies.  Workgroup wg_first + i writes row i of part_out (DEVICE float32 [wg_count, Dtot])
+ * and of part_stats_out (DEVICE float64 [wg_count, 4]); the object's own workspace is not touched, so calls with
+ * one object may overlap.  logp_out / v_out are written for the rows of the tiles these workgroups own, every other
+ * row is left untouched.  io's grad_actor, grad_critic, grad_log_std and stats are not written and may be NULL.
+ * wg_count == 0 is valid and launches nothing (the outputs may then be NULL).  PBG_E_ARG (before any HIP call)
+ * for a range outside 0 .. G, a negative count, NULL outputs with wg_count > 0, and everything pbg_ppo_grad_run
+ * refuses of the fields it reads. */
+int pbg_ppo_grad_run_part(pbg_ppo_grad* g, const pbg_ppo_grad_io_t* io, int wg_first, int wg_count, float* part_out,
+                          double* part_stats_out, void* stream);
+/* pbg_ppo_grad_run's reduction, one launch on `stream`, over the caller's part (DEVICE float32 [G, Dtot]) and
+ * part_stats (DEVICE float64 [G, 4]): the G partials in ascending order in float64 into io's grad_actor,
+ * grad_critic, grad_log_std (less io->ent_coef) and stats (divided by io->mb_rows).  Of io only these, struct_size,
+ * batch_rows and mb_rows are read.  PBG_E_ARG (before any HIP call) for a NULL argument or output, a bad
+ * struct_size or mb_rows, and a G that is not pbg_ppo_grad_geometry's for io->mb_rows. */
+int pbg_ppo_grad_reduce(pbg_ppo_grad* g, const pbg_ppo_grad_io_t* io, int G, const float* part, const double* part_stats,
+                        void* stream);
+
+/* The slots of a pbg_obs_stats, `count` of them from `first`: counts DEVICE int64 [count], sums DEVICE float64
+ * [count, 2 K], per slot sum[K] | sumsq[K].  Each is one launch on `stream` (none for count == 0).  get copies
+ * the slots out and zeroes nothing; set overwrites them.  PBG_E_ARG (before any HIP call) for a NULL pointer or a
+ * range outside the object's slots.
+ * pbg_obs_stats_finalize folds the slots in ascending order, and slot b is workgroup b of the actor's launch.  So
+ * when every shard's tiles are tiles of the whole launch (equal shards whose rows per group are a multiple of 16),
+ * each shard's slots set in shard order into one object and finalized there give the totals, mean and inv_std of
+ * the object that saw the whole launch, bit for bit.  A slot that was never written adds +0.0 and 0. */
+int pbg_obs_stats_get_slots(const pbg_obs_stats* s, int first, int count, int64_t* counts_out, double* sums_out, void* stream);
+int pbg_obs_stats_set_slots(pbg_obs_stats* s, int first, int count, const int64_t* counts, const double* sums, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -268,6 +268,14 @@ def lib():
         for f in PERM_EXPORTED:
             if f != "pbg_perm_destroy":
                 getattr(L, f).restype = I
+    if hasattr(L, "pbg_ppo_grad_run_part"):  # the gradient as parts and the statistics' slots
+        L.pbg_ppo_grad_geometry.argtypes = [H, I, ctypes.POINTER(I), ctypes.POINTER(ctypes.c_int64)]
+        L.pbg_ppo_grad_run_part.argtypes = [H, ctypes.POINTER(PPOGradIO), I, I, P, P, P]
+        L.pbg_ppo_grad_reduce.argtypes = [H, ctypes.POINTER(PPOGradIO), I, P, P, P]
+        L.pbg_obs_stats_get_slots.argtypes = [H, I, I, P, P, P]
+        L.pbg_obs_stats_set_slots.argtypes = [H, I, I, P, P, P]
+        for f in PPO_PARTS_EXPORTED:
+            getattr(L, f).restype = I
     for f in ("pbg_info", "pbg_reset", "pbg_step", "pbg_step_ex", "pbg_get_state", "pbg_set_state",
               "pbg_pack_record_sizes", "pbg_pack", "pbg_create_debug", "pbg_sample_actions", "pbg_create_ex",
               "pbg_default_sim_params", "pbg_get_sim_params", "pbg_create_v2", "pbg_precision"):
@@ -294,12 +302,14 @@ PPO_OPT_EXPORTED = ("pbg_adv_norm", "pbg_adv_norm_host", "pbg_ppo_opt_create", "
                     "pbg_ppo_opt_reset", "pbg_ppo_opt_get_state", "pbg_ppo_opt_host")
 PERM_EXPORTED = ("pbg_perm_create", "pbg_perm_destroy", "pbg_perm_fill", "pbg_perm_set_counter", "pbg_perm_get_counter",
                  "pbg_perm_host", "pbg_ppo_lr_linear", "pbg_ppo_lr_linear_host")
+PPO_PARTS_EXPORTED = ("pbg_ppo_grad_geometry", "pbg_ppo_grad_run_part", "pbg_ppo_grad_reduce", "pbg_obs_stats_get_slots",
+                      "pbg_obs_stats_set_slots")
 EXPORTED = ("pbg_create", "pbg_create_debug", "pbg_create_ex", "pbg_create_v2", "pbg_precision",
             "pbg_default_sim_params", "pbg_get_sim_params",
             "pbg_destroy", "pbg_info", "pbg_reset", "pbg_step", "pbg_step_ex",
             "pbg_get_state", "pbg_set_state", "pbg_pack_record_sizes", "pbg_pack", "pbg_sample_actions",
             "pbg_debug_poison", "pbg_last_error") + POLICY_EXPORTED + POPULATION_EXPORTED + OBS_NORM_EXPORTED + \
-    ACTION_NOISE_EXPORTED + PPO_GRAD_EXPORTED + PPO_OPT_EXPORTED + PERM_EXPORTED + PPO_GRAD_EX_EXPORTED
+    ACTION_NOISE_EXPORTED + PPO_GRAD_EXPORTED + PPO_OPT_EXPORTED + PERM_EXPORTED + PPO_GRAD_EX_EXPORTED + PPO_PARTS_EXPORTED
 
 
 def check(rc: int, what: str):

@@ -199,7 +199,7 @@ __device__ __forceinline__ void net_flush(const Weights& P, const Weights& G, co
   flush_b(P.act_dim, const_cast<float*>(G.b3), acc.b3);
 }
 
-// Workgroup b: the tiles b, b + gridDim.x, ... of the minibatch into partial b.  LDS: four [256][16] planes and
+// Workgroup b = a.wg0 + blockIdx.x of a.G: the tiles b, b + a.G, ... of the minibatch into row blockIdx.x of a.part.  LDS: four [256][16] planes and
 // two [64][16] ones, 72 KiB, plus the row lanes' doubles.
 template <bool REG>
 __global__ __launch_bounds__(PB) void ppograd_tiles_kernel(const Args a) {
@@ -233,7 +233,7 @@ __global__ __launch_bounds__(PB) void ppograd_tiles_kernel(const Args a) {
 
   const int ntiles = (a.Bm + PT - 1) / PT;
   bool first = true;
-  for (int t = blockIdx.x; t < ntiles; t += gridDim.x, first = false) {
+  for (int t = a.wg0 + (int)blockIdx.x; t < ntiles; t += a.G, first = false) {
     const int row0 = t * PT, rows = min(PT, a.Bm - row0);
     if (!first) __syncthreads();  // the previous tile's last weight gradient reads bX and bH2
     gather_tile(a.obs_dim, a.idx, row0, rows, a.obs, a.nm, bX);
@@ -334,8 +334,10 @@ __global__ __launch_bounds__(256) void ppograd_reduce_kernel(const float* __rest
   }
 }
 
-// what run and host check alike: the struct's version, then its fields; copies the caller's struct into `io`
-int check_io(const char* who, const pbg_ppo_grad_io_t* uio, pbg_ppo_grad_io_t* io) {
+// what run and host check alike: the struct's version, then its fields; copies the caller's struct into `io`.
+// need_in: the batch, the parameters and the loss's constants (all but reduce); need_out: grad_* and stats (all but
+// run_part)
+int check_io(const char* who, const pbg_ppo_grad_io_t* uio, pbg_ppo_grad_io_t* io, bool need_in = true, bool need_out = true) {
   char msg[200];
   if (!uio) {
     snprintf(msg, sizeof(msg), "%s: io is NULL", who);
@@ -353,11 +355,13 @@ int check_io(const char* who, const pbg_ppo_grad_io_t* uio, pbg_ppo_grad_io_t* i
              io->mb_rows, io->batch_rows);
     return pbg::capi_fail(PBG_E_ARG, msg);
   }
-  if (!io->theta_actor || !io->theta_critic || !io->log_std || !io->obs || !io->act || !io->logp_old || !io->adv || !io->ret ||
-      !io->grad_actor || !io->grad_critic || !io->grad_log_std || !io->stats) {
+  if ((need_in && (!io->theta_actor || !io->theta_critic || !io->log_std || !io->obs || !io->act || !io->logp_old || !io->adv ||
+                   !io->ret)) ||
+      (need_out && (!io->grad_actor || !io->grad_critic || !io->grad_log_std || !io->stats))) {
     snprintf(msg, sizeof(msg), "%s: NULL required pointer", who);
     return pbg::capi_fail(PBG_E_ARG, msg);
   }
+  if (!need_in) return PBG_OK;
   if ((io->mean == nullptr) != (io->inv_std == nullptr) || (io->mean && !(io->clip > 0.f))) {
     snprintf(msg, sizeof(msg), "%s: mean and inv_std must both be given with a clip > 0, or both NULL", who);
     return pbg::capi_fail(PBG_E_ARG, msg);
@@ -416,6 +420,55 @@ int create_object(const char* who, int device, int obs_dim, int h1, int h2, int 
   return PBG_OK;
 }
 
+// the workgroups of a whole gradient over mb_rows rows: min(tiles, n_wg)
+int workgroups_of(const pbg_ppo_grad* g, int mb_rows) {
+  const int ntiles = (mb_rows + PT - 1) / PT;
+  return ntiles < g->n_wg ? ntiles : g->n_wg;
+}
+
+int check_rows(const char* who, const pbg_ppo_grad* g, int mb_rows) {
+  if (mb_rows <= g->max_rows) return PBG_OK;
+  char msg[160];
+  snprintf(msg, sizeof(msg), "%s: mb_rows %d exceeds the object's max_rows %d", who, mb_rows, g->max_rows);
+  return pbg::capi_fail(PBG_E_ARG, msg);
+}
+
+// the tile kernel of the object's path for the workgroups wg0 .. wg0 + count - 1 of G, row i of part / part_stats
+// for workgroup wg0 + i
+int launch_tiles(const pbg_ppo_grad* g, const pbg_ppo_grad_io_t& io, int wg0, int count, int G, float* part, double* part_stats,
+                 hipStream_t s) {
+  Args a;
+  a.theta_a = io.theta_actor; a.theta_c = io.theta_critic; a.log_std = io.log_std;
+  a.nm = io.mean ? Norm{io.mean, io.inv_std, io.clip} : Norm{nullptr, nullptr, 0.f};
+  a.obs = io.obs; a.act = io.act; a.logp_old = io.logp_old; a.adv = io.adv; a.ret = io.ret;
+  a.idx = io.idx; a.adv_norm = io.adv_norm;
+  a.clip_eps = io.clip_eps; a.vf_coef = io.vf_coef;
+  a.Bm = io.mb_rows; a.obs_dim = g->obs_dim; a.h1 = g->h1; a.h2 = g->h2; a.A = g->act_dim; a.Da = g->Da; a.Dtot = g->Dtot;
+  a.wg0 = wg0; a.G = G;
+  a.part = part; a.part_stats = part_stats;
+  a.logp_out = io.logp_out; a.v_out = io.v_out;
+  const bool reg = g->obs_dim <= 64 && g->h1 <= 64 && g->h2 <= 64;
+  int e;
+  if (g->path == PBG_PPO_GRAD_MFMA) {
+    e = launch_tiles_mfma(a, count, s);
+  } else {
+    if (reg)
+      hipLaunchKernelGGL(ppograd_tiles_kernel<true>, dim3((unsigned)count), dim3(PB), 0, s, a);
+    else
+      hipLaunchKernelGGL(ppograd_tiles_kernel<false>, dim3((unsigned)count), dim3(PB), 0, s, a);
+    e = (int)hipGetLastError();
+  }
+  return e ? hip_fail(e, "ppograd_tiles_kernel launch") : PBG_OK;
+}
+
+int launch_reduce(const pbg_ppo_grad* g, const pbg_ppo_grad_io_t& io, int G, const float* part, const double* part_stats,
+                  hipStream_t s) {
+  hipLaunchKernelGGL(ppograd_reduce_kernel, dim3((unsigned)((g->Dtot + 255) / 256)), dim3(256), 0, s, part, part_stats, G, g->Da,
+                     g->Dc, g->Dtot, io.ent_coef, io.mb_rows, io.grad_actor, io.grad_critic, io.grad_log_std, io.stats);
+  const int e = (int)hipGetLastError();
+  return e ? hip_fail(e, "ppograd_reduce_kernel launch") : PBG_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -462,40 +515,57 @@ int pbg_ppo_grad_run(pbg_ppo_grad* g, const pbg_ppo_grad_io_t* uio, void* stream
   if (!g) return pbg::capi_fail(PBG_E_ARG, "pbg_ppo_grad_run: the object is NULL");
   pbg_ppo_grad_io_t io;
   if (const int rc = check_io("pbg_ppo_grad_run", uio, &io)) return rc;
-  if (io.mb_rows > g->max_rows) {
-    char msg[128];
-    snprintf(msg, sizeof(msg), "pbg_ppo_grad_run: mb_rows %d exceeds the object's max_rows %d", io.mb_rows, g->max_rows);
-    return pbg::capi_fail(PBG_E_ARG, msg);
-  }
+  if (const int rc = check_rows("pbg_ppo_grad_run", g, io.mb_rows)) return rc;
   DeviceGuard dg(g->device);
   hipStream_t s = (hipStream_t)stream;
-  Args a;
-  a.theta_a = io.theta_actor; a.theta_c = io.theta_critic; a.log_std = io.log_std;
-  a.nm = io.mean ? Norm{io.mean, io.inv_std, io.clip} : Norm{nullptr, nullptr, 0.f};
-  a.obs = io.obs; a.act = io.act; a.logp_old = io.logp_old; a.adv = io.adv; a.ret = io.ret;
-  a.idx = io.idx; a.adv_norm = io.adv_norm;
-  a.clip_eps = io.clip_eps; a.vf_coef = io.vf_coef;
-  a.Bm = io.mb_rows; a.obs_dim = g->obs_dim; a.h1 = g->h1; a.h2 = g->h2; a.A = g->act_dim; a.Da = g->Da; a.Dtot = g->Dtot;
-  a.part = g->part; a.part_stats = g->part_stats;
-  a.logp_out = io.logp_out; a.v_out = io.v_out;
-  const int ntiles = (io.mb_rows + PT - 1) / PT;
-  const int G = ntiles < g->n_wg ? ntiles : g->n_wg;
-  const bool reg = g->obs_dim <= 64 && g->h1 <= 64 && g->h2 <= 64;
-  int e;
-  if (g->path == PBG_PPO_GRAD_MFMA) {
-    e = launch_tiles_mfma(a, G, s);
-  } else {
-    if (reg)
-      hipLaunchKernelGGL(ppograd_tiles_kernel<true>, dim3((unsigned)G), dim3(PB), 0, s, a);
-    else
-      hipLaunchKernelGGL(ppograd_tiles_kernel<false>, dim3((unsigned)G), dim3(PB), 0, s, a);
-    e = (int)hipGetLastError();
+  const int G = workgroups_of(g, io.mb_rows);
+  if (const int rc = launch_tiles(g, io, 0, G, G, g->part, g->part_stats, s)) return rc;
+  return launch_reduce(g, io, G, g->part, g->part_stats, s);
+}
+
+int pbg_ppo_grad_geometry(const pbg_ppo_grad* g, int mb_rows, int* G_out, int64_t* dtot_out) {
+  if (!g || !G_out || !dtot_out) return pbg::capi_fail(PBG_E_ARG, "pbg_ppo_grad_geometry: NULL object, G_out or dtot_out");
+  if (mb_rows < 1) return pbg::capi_fail(PBG_E_ARG, "pbg_ppo_grad_geometry: mb_rows must be >= 1");
+  if (const int rc = check_rows("pbg_ppo_grad_geometry", g, mb_rows)) return rc;
+  *G_out = workgroups_of(g, mb_rows);
+  *dtot_out = (int64_t)g->Dtot;
+  return PBG_OK;
+}
+
+int pbg_ppo_grad_run_part(pbg_ppo_grad* g, const pbg_ppo_grad_io_t* uio, int wg_first, int wg_count, float* part_out,
+                          double* part_stats_out, void* stream) {
+  if (!g) return pbg::capi_fail(PBG_E_ARG, "pbg_ppo_grad_run_part: the object is NULL");
+  pbg_ppo_grad_io_t io;
+  if (const int rc = check_io("pbg_ppo_grad_run_part", uio, &io, true, false)) return rc;
+  if (const int rc = check_rows("pbg_ppo_grad_run_part", g, io.mb_rows)) return rc;
+  const int G = workgroups_of(g, io.mb_rows);
+  char msg[160];
+  if (wg_first < 0 || wg_count < 0 || (long long)wg_first + wg_count > (long long)G) {
+    snprintf(msg, sizeof(msg), "pbg_ppo_grad_run_part: workgroups %d .. %d + %d are outside 0 .. %d", wg_first, wg_first, wg_count,
+             G);
+    return pbg::capi_fail(PBG_E_ARG, msg);
   }
-  if (e) return hip_fail(e, "ppograd_tiles_kernel launch");
-  hipLaunchKernelGGL(ppograd_reduce_kernel, dim3((unsigned)((g->Dtot + 255) / 256)), dim3(256), 0, s, g->part, g->part_stats, G,
-                     g->Da, g->Dc, g->Dtot, io.ent_coef, io.mb_rows, io.grad_actor, io.grad_critic, io.grad_log_std, io.stats);
-  e = (int)hipGetLastError();
-  return e ? hip_fail(e, "ppograd_reduce_kernel launch") : PBG_OK;
+  if (wg_count == 0) return PBG_OK;
+  if (!part_out || !part_stats_out) return pbg::capi_fail(PBG_E_ARG, "pbg_ppo_grad_run_part: NULL part_out or part_stats_out");
+  DeviceGuard dg(g->device);
+  return launch_tiles(g, io, wg_first, wg_count, G, part_out, part_stats_out, (hipStream_t)stream);
+}
+
+int pbg_ppo_grad_reduce(pbg_ppo_grad* g, const pbg_ppo_grad_io_t* uio, int G, const float* part, const double* part_stats,
+                        void* stream) {
+  if (!g) return pbg::capi_fail(PBG_E_ARG, "pbg_ppo_grad_reduce: the object is NULL");
+  pbg_ppo_grad_io_t io;
+  if (const int rc = check_io("pbg_ppo_grad_reduce", uio, &io, false, true)) return rc;
+  if (const int rc = check_rows("pbg_ppo_grad_reduce", g, io.mb_rows)) return rc;
+  if (G != workgroups_of(g, io.mb_rows)) {
+    char msg[160];
+    snprintf(msg, sizeof(msg), "pbg_ppo_grad_reduce: G %d is not the %d workgroups of mb_rows %d", G, workgroups_of(g, io.mb_rows),
+             io.mb_rows);
+    return pbg::capi_fail(PBG_E_ARG, msg);
+  }
+  if (!part || !part_stats) return pbg::capi_fail(PBG_E_ARG, "pbg_ppo_grad_reduce: NULL part or part_stats");
+  DeviceGuard dg(g->device);
+  return launch_reduce(g, io, G, part, part_stats, (hipStream_t)stream);
 }
 
 int pbg_ppo_grad_host(int obs_dim, int h1, int h2, int act_dim, const pbg_ppo_grad_io_t* uio) {

@@ -32,13 +32,15 @@ struct Args {
   const float* adv_norm;
   float clip_eps, vf_coef;
   int Bm, obs_dim, h1, h2, A, Da, Dtot;
-  float* part;
-  double* part_stats;
+  int wg0, G;         // the launch's first workgroup and the workgroups of the whole gradient: block i is workgroup wg0 + i
+  float* part;        // [gridDim.x, Dtot]: row i is block i's
+  double* part_stats; // [gridDim.x, 4]
   float *logp_out, *v_out;
 };
 
-// The matrix-core path's tile kernel (pbg_ppograd_mfma.hip) for G workgroups on `stream`: the hipError_t of the launch
-int launch_tiles_mfma(const Args& a, int G, hipStream_t stream);
+// The matrix-core path's tile kernel (pbg_ppograd_mfma.hip) for the `count` workgroups a.wg0 .. a.wg0 + count - 1 on
+// `stream`: the hipError_t of the launch
+int launch_tiles_mfma(const Args& a, int count, hipStream_t stream);
 // its workgroup cap: one workgroup per CU
 constexpr int MFMA_MAX_WG = 256;
 

@@ -28,6 +28,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "pbg_ppograd_dev.h"
 
 namespace {
@@ -36,6 +38,16 @@ using namespace pbg::policy;
 using namespace pbg::ppograd;
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+// The kernel's Args where they lie, in the kernarg segment.  The tile loops read wg0 and G through it (the values of
+// a.wg0 and a.G), as they once read gridDim.x through the implicit arguments behind the same segment: a loop that uses
+// the segment's base keeps it in scalar registers, and with it there the compiler reads an argument again where it would
+// otherwise spill it to a lane and read that back.  The cast holds
+// because Args, passed by value, is the kernel's first and only explicit argument, so it lies at offset 0 of the segment
+// in its own layout: the static_asserts behind the kernel pin the signature and the layout
+__device__ __forceinline__ const __attribute__((address_space(4))) Args* karg() {
+  return (const __attribute__((address_space(4))) Args*)__builtin_amdgcn_kernarg_segment_ptr();
+}
 
 constexpr int BE = 16;  // a block's edge
 
@@ -326,7 +338,7 @@ __device__ __forceinline__ void net_pass(const Args& a, const Weights& P, const 
 
   const int ntiles = (a.Bm + PT - 1) / PT;
   bool first = true;
-  for (int t = blockIdx.x; t < ntiles; t += gridDim.x, first = false) {
+  for (int t = karg()->wg0 + (int)blockIdx.x; t < ntiles; t += karg()->G, first = false) {
     const int row0 = t * PT, rows = min(PT, a.Bm - row0);
     __syncthreads();  // the previous tile's (or network's) last readers of the planes
     gather_tile(K0, a.idx, row0, rows, a.obs, a.nm, L.X);
@@ -417,7 +429,7 @@ __device__ __forceinline__ void stats_pass(const Args& a, const Weights& P, cons
   const int tid = threadIdx.x, A = a.A;
   const int ntiles = (a.Bm + PT - 1) / PT;
   double* mu64 = reinterpret_cast<double*>(L.D);
-  for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
+  for (int t = karg()->wg0 + (int)blockIdx.x; t < ntiles; t += karg()->G) {
     const int row0 = t * PT, rows = min(PT, a.Bm - row0);
     __syncthreads();  // the previous tile's rows read mu64; the actor's last tile read every plane
     if (a.obs_dim <= PD / 2 && a.h1 <= PD / 2 && a.h2 <= PD / 2)
@@ -437,7 +449,7 @@ __device__ __forceinline__ void stats_pass(const Args& a, const Weights& P, cons
   }
 }
 
-// Workgroup b: the tiles b, b + gridDim.x, ... of the minibatch into partial b.  LDS: five [256][16] planes and two
+// Workgroup b = a.wg0 + blockIdx.x of a.G: the tiles b, b + a.G, ... of the minibatch into row blockIdx.x of a.part.  LDS: five [256][16] planes and two
 // [64][16] ones, 88 KiB, plus the row lanes' doubles.
 template <bool CHIP>
 __global__ __launch_bounds__(PB) void ppograd_mfma_kernel(const Args a) {
@@ -479,17 +491,25 @@ __global__ __launch_bounds__(PB) void ppograd_mfma_kernel(const Args a) {
   }
 }
 
+// what karg() relies on: one explicit argument, an Args by value (a function type drops the const), copied into the
+// kernarg segment byte for byte
+static_assert(std::is_same<decltype(&ppograd_mfma_kernel<true>), void (*)(Args)>::value &&
+                  std::is_same<decltype(&ppograd_mfma_kernel<false>), void (*)(Args)>::value,
+              "karg(): Args must be the kernel's only explicit argument");
+static_assert(std::is_trivially_copyable<Args>::value && std::is_standard_layout<Args>::value,
+              "karg(): Args must lie in the kernarg segment as it lies in memory");
+
 }  // namespace
 
 namespace pbg {
 namespace ppograd {
 
-int launch_tiles_mfma(const Args& a, int G, hipStream_t stream) {
+int launch_tiles_mfma(const Args& a, int count, hipStream_t stream) {
   // the critic's third layer has one block of columns, so what holds the actor's patches holds the critic's
   if (on_chip(a.obs_dim, a.h1, a.h2, a.A))
-    hipLaunchKernelGGL(ppograd_mfma_kernel<true>, dim3((unsigned)G), dim3(PB), 0, stream, a);
+    hipLaunchKernelGGL(ppograd_mfma_kernel<true>, dim3((unsigned)count), dim3(PB), 0, stream, a);
   else
-    hipLaunchKernelGGL(ppograd_mfma_kernel<false>, dim3((unsigned)G), dim3(PB), 0, stream, a);
+    hipLaunchKernelGGL(ppograd_mfma_kernel<false>, dim3((unsigned)count), dim3(PB), 0, stream, a);
   return (int)hipGetLastError();
 }
 

@@ -72,6 +72,34 @@ def gather_step(obs: torch.Tensor, reward: torch.Tensor, done: torch.Tensor, num
     return flat[:, :D], flat[:, D].contiguous(), flat[:, D + 1].to(done.dtype)
 
 
+def all_gather_blocks(send: torch.Tensor, group=None) -> torch.Tensor:
+    """[world, *send.shape]: every rank's ``send`` (the same shape and dtype on every rank) in rank order, ONE
+    collective.  Under gloo a device tensor is staged through the host and the result handed back on its device, as in
+    gather_flat."""
+    world = dist.get_world_size(group)
+    host = send.is_cuda and dist.get_backend(group) == "gloo"
+    src = (send.cpu() if host else send).contiguous()
+    out = torch.empty((world * src.shape[0],) + tuple(src.shape[1:]), dtype=src.dtype, device=src.device)   # rank-major
+    dist.all_gather_into_tensor(out, src, group=group)
+    out = out.view((world,) + tuple(src.shape))
+    return out.to(send.device) if host else out
+
+
+def gather_traj(local: torch.Tensor, num_global: int, group=None) -> torch.Tensor:
+    """All-gather per-rank trajectories [T, n_rank, C] into [T, num_global, C] with ONE collective: rank r's envs
+    land at the global columns [r * n_rank, (r + 1) * n_rank), so row t * num_global + e of the flattened result is
+    step t of global env e on every rank.  Shards must be equal (num_global = world * n_rank): ValueError otherwise.
+    Under gloo a device tensor is staged through the host, as in gather_flat."""
+    world = dist.get_world_size(group)
+    if local.dim() != 3:
+        raise ValueError(f"gather_traj: local must be [T, n_rank, C], got shape {tuple(local.shape)}")
+    T, n_local, C = local.shape
+    if num_global % world != 0 or n_local * world != num_global:
+        raise ValueError(f"gather_traj: {num_global} global envs over {world} ranks with {n_local} here: the shards must "
+                         "be equal")
+    return all_gather_blocks(local, group).permute(1, 0, 2, 3).reshape(T, num_global, C)
+
+
 class ShardedVecEnv:
     """This rank's share of a global batch of envs, plus the optional flat gather.
 
@@ -83,6 +111,7 @@ class ShardedVecEnv:
     def __init__(self, env_id: str, num_global: int, rank: int, world: int, device, seed: int = 0,
                  autoreset: bool = True, env_factory: Optional[Callable] = None, precision: int = 64):
         self.num_global = num_global
+        self.rank, self.world = rank, world
         self.offset, self.count = shard_range(num_global, rank, world)
         if env_factory is None:
             from .vec_env import VecEnv

@@ -127,6 +127,39 @@ class ObsStats(_NativeObject):
                                                            self._stream()), "pbg_obs_stats_finalize")
         return self.mean, self.inv_std
 
+    def _slot_range(self, what, first, count):
+        first, count = int(first), int(count)
+        if first < 0 or count < 0 or first + count > self.n_slots:
+            raise _native.PbgError(f"ObsStats.{what}: slots {first} .. {first} + {count} are outside the object's 0 .. "
+                                   f"{self.n_slots}")
+        return first, count
+
+    def get_slots(self, first: int, count: int):
+        """``(counts int64 [count], sums float64 [count, 2 obs_dim])`` of the slots ``first .. first + count - 1``,
+        per slot ``sum | sumsq``: fresh device tensors, one launch (pbg_obs_stats_get_slots); the slots stay as
+        they are."""
+        import torch
+        first, count = self._slot_range("get_slots", first, count)
+        s = self._open("get_slots")
+        counts = torch.empty(count, dtype=torch.int64, device=self.device)
+        sums = torch.empty((count, 2 * self.obs_dim), dtype=torch.float64, device=self.device)
+        _native.check(_need("pbg_obs_stats_get_slots")(s, first, count, counts.data_ptr(), sums.data_ptr(), self._stream()),
+                      "pbg_obs_stats_get_slots")
+        return counts, sums
+
+    def set_slots(self, first: int, counts, sums):
+        """Overwrite the slots ``first .. first + len(counts) - 1`` with ``counts`` (int64 ``[count]``) and ``sums``
+        (float64 ``[count, 2 obs_dim]``), ``get_slots``' layout: one launch (pbg_obs_stats_set_slots).  Slots
+        gathered from equal shards in shard order and finalized here give the unsharded object's bits."""
+        import torch
+        count = counts.shape[0] if isinstance(counts, torch.Tensor) and counts.dim() == 1 else -1
+        first, count = self._slot_range("set_slots", first, count)
+        s = self._open("set_slots")
+        self._vec(counts, "set_slots", "counts", (count,), torch.int64)
+        self._vec(sums, "set_slots", "sums", (count, 2 * self.obs_dim), torch.float64)
+        _native.check(_need("pbg_obs_stats_set_slots")(s, first, count, counts.data_ptr(), sums.data_ptr(), self._stream()),
+                      "pbg_obs_stats_set_slots")
+
     @property
     def totals(self):
         """``[1 + 2 obs_dim]`` float64 on the device: count, sum, sumsq (a fresh tensor; what the slots hold

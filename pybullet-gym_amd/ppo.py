@@ -131,6 +131,50 @@ class PPOGrad:
         return isinstance(t, torch.Tensor) and t.is_contiguous() and t.device == self.device and \
             tuple(t.shape) == shape and t.dtype == dt
 
+    def _io(self, who, theta_actor, theta_critic, log_std, obs, act, logp_old, adv, ret, idx, rows, adv_norm, obs_norm, clip_eps,
+            vf_coef, ent_coef, grad_actor, grad_critic, grad_log_std, stats, logp_out, v_out, outputs=True):
+        """The checked pbg_ppo_grad_io_t of ``run``, ``run_part`` (``outputs=False``: no gradient tensors) and ``reduce``,
+        and the four output tensors (new ones where none were given)."""
+        o, h1, h2, A = self.dims
+        f32, f64, i64 = (np.float32, np.float64, np.int64) if self.host else (torch.float32, torch.float64, torch.int64)
+        if getattr(obs, "ndim", 0) != 2:
+            raise _native.PbgError(f"PPOGrad.{who}: obs must be [B, obs_dim]")
+        B = int(obs.shape[0])
+        Bm = int(idx.shape[0]) if idx is not None and getattr(idx, "ndim", 0) == 1 else (B if rows is None else int(rows))
+        new = (lambda n, dt: np.empty(n, dt)) if self.host else (lambda n, dt: torch.empty(n, dtype=dt, device=self.device))
+        if outputs:
+            grad_actor = new(self.Da, f32) if grad_actor is None else grad_actor
+            grad_critic = new(self.Dc, f32) if grad_critic is None else grad_critic
+            grad_log_std = new(A, f32) if grad_log_std is None else grad_log_std
+            stats = new(4, f64) if stats is None else stats
+        mean, inv_std, clip = obs_norm if obs_norm is not None else (None, None, 0.0)
+        checks = [("theta_actor", theta_actor, (self.Da,), f32), ("theta_critic", theta_critic, (self.Dc,), f32),
+                  ("log_std", log_std, (A,), f32), ("obs", obs, (B, o), f32), ("act", act, (B, A), f32),
+                  ("logp_old", logp_old, (B,), f32), ("adv", adv, (B,), f32), ("ret", ret, (B,), f32)]
+        if outputs:
+            checks += [("grad_actor", grad_actor, (self.Da,), f32), ("grad_critic", grad_critic, (self.Dc,), f32),
+                       ("grad_log_std", grad_log_std, (A,), f32), ("stats", stats, (4,), f64)]
+        checks += [(n, t, s, d) for n, t, s, d in (("idx", idx, (Bm,), i64), ("adv_norm", adv_norm, (2,), f32),
+                                                   ("mean", mean, (o,), f32), ("inv_std", inv_std, (o,), f32),
+                                                   ("logp_out", logp_out, (Bm,), f32), ("v_out", v_out, (Bm,), f32))
+                   if t is not None]
+        for name, t, shape, dt in checks:
+            if not self._ok(t, shape, dt):
+                raise _native.PbgError(f"PPOGrad.{who}: {name} must be a contiguous {dt} "
+                                       f"{'array' if self.host else f'tensor on {self.device}'} of shape {shape}")
+        if Bm < 1 or Bm > self.max_rows or (idx is None and Bm > B):
+            raise _native.PbgError(f"PPOGrad.{who}: {Bm} minibatch rows outside 1 .. max_rows = {self.max_rows} (or the batch's {B})")
+        if (mean is None) != (inv_std is None):
+            raise _native.PbgError(f"PPOGrad.{who}: obs_norm needs both mean and inv_std")
+        ptr = (lambda t: None if t is None else t.ctypes.data) if self.host else (lambda t: None if t is None else t.data_ptr())
+        io = _native.PPOGradIO(batch_rows=B, mb_rows=Bm, theta_actor=ptr(theta_actor), theta_critic=ptr(theta_critic),
+                               log_std=ptr(log_std), mean=ptr(mean), inv_std=ptr(inv_std), clip=float(clip),
+                               clip_eps=float(clip_eps), vf_coef=float(vf_coef), ent_coef=float(ent_coef), obs=ptr(obs),
+                               act=ptr(act), logp_old=ptr(logp_old), adv=ptr(adv), ret=ptr(ret), idx=ptr(idx),
+                               adv_norm=ptr(adv_norm), grad_actor=ptr(grad_actor), grad_critic=ptr(grad_critic),
+                               grad_log_std=ptr(grad_log_std), stats=ptr(stats), logp_out=ptr(logp_out), v_out=ptr(v_out))
+        return io, (grad_actor, grad_critic, grad_log_std, stats)
+
     def run(self, theta_actor, theta_critic, log_std, obs, act, logp_old, adv, ret, idx=None, rows=None, adv_norm=None,
             obs_norm=None, clip_eps: float = 0.2, vf_coef: float = 0.5, ent_coef: float = 0.0, grad_actor=None,
             grad_critic=None, grad_log_std=None, stats=None, logp_out=None, v_out=None):
@@ -142,41 +186,8 @@ class PPOGrad:
         loss, clipped fraction, mean(logp_old - logp).  ``logp_out``, ``v_out``: optional float32 ``[Bm]``.  The indices
         are not validated on a GPU."""
         o, h1, h2, A = self.dims
-        f32, f64, i64 = (np.float32, np.float64, np.int64) if self.host else (torch.float32, torch.float64, torch.int64)
-        if getattr(obs, "ndim", 0) != 2:
-            raise _native.PbgError("PPOGrad.run: obs must be [B, obs_dim]")
-        B = int(obs.shape[0])
-        Bm = int(idx.shape[0]) if idx is not None and getattr(idx, "ndim", 0) == 1 else (B if rows is None else int(rows))
-        new = (lambda n, dt: np.empty(n, dt)) if self.host else (lambda n, dt: torch.empty(n, dtype=dt, device=self.device))
-        grad_actor = new(self.Da, f32) if grad_actor is None else grad_actor
-        grad_critic = new(self.Dc, f32) if grad_critic is None else grad_critic
-        grad_log_std = new(A, f32) if grad_log_std is None else grad_log_std
-        stats = new(4, f64) if stats is None else stats
-        mean, inv_std, clip = obs_norm if obs_norm is not None else (None, None, 0.0)
-        checks = [("theta_actor", theta_actor, (self.Da,), f32), ("theta_critic", theta_critic, (self.Dc,), f32),
-                  ("log_std", log_std, (A,), f32), ("obs", obs, (B, o), f32), ("act", act, (B, A), f32),
-                  ("logp_old", logp_old, (B,), f32), ("adv", adv, (B,), f32), ("ret", ret, (B,), f32),
-                  ("grad_actor", grad_actor, (self.Da,), f32), ("grad_critic", grad_critic, (self.Dc,), f32),
-                  ("grad_log_std", grad_log_std, (A,), f32), ("stats", stats, (4,), f64)]
-        checks += [(n, t, s, d) for n, t, s, d in (("idx", idx, (Bm,), i64), ("adv_norm", adv_norm, (2,), f32),
-                                                   ("mean", mean, (o,), f32), ("inv_std", inv_std, (o,), f32),
-                                                   ("logp_out", logp_out, (Bm,), f32), ("v_out", v_out, (Bm,), f32))
-                   if t is not None]
-        for name, t, shape, dt in checks:
-            if not self._ok(t, shape, dt):
-                raise _native.PbgError(f"PPOGrad.run: {name} must be a contiguous {dt} "
-                                       f"{'array' if self.host else f'tensor on {self.device}'} of shape {shape}")
-        if Bm < 1 or Bm > self.max_rows or (idx is None and Bm > B):
-            raise _native.PbgError(f"PPOGrad.run: {Bm} minibatch rows outside 1 .. max_rows = {self.max_rows} (or the batch's {B})")
-        if (mean is None) != (inv_std is None):
-            raise _native.PbgError("PPOGrad.run: obs_norm needs both mean and inv_std")
-        ptr = (lambda t: None if t is None else t.ctypes.data) if self.host else (lambda t: None if t is None else t.data_ptr())
-        io = _native.PPOGradIO(batch_rows=B, mb_rows=Bm, theta_actor=ptr(theta_actor), theta_critic=ptr(theta_critic),
-                               log_std=ptr(log_std), mean=ptr(mean), inv_std=ptr(inv_std), clip=float(clip),
-                               clip_eps=float(clip_eps), vf_coef=float(vf_coef), ent_coef=float(ent_coef), obs=ptr(obs),
-                               act=ptr(act), logp_old=ptr(logp_old), adv=ptr(adv), ret=ptr(ret), idx=ptr(idx),
-                               adv_norm=ptr(adv_norm), grad_actor=ptr(grad_actor), grad_critic=ptr(grad_critic),
-                               grad_log_std=ptr(grad_log_std), stats=ptr(stats), logp_out=ptr(logp_out), v_out=ptr(v_out))
+        io, out = self._io("run", theta_actor, theta_critic, log_std, obs, act, logp_old, adv, ret, idx, rows, adv_norm, obs_norm,
+                           clip_eps, vf_coef, ent_coef, grad_actor, grad_critic, grad_log_std, stats, logp_out, v_out)
         if self.host:
             _native.check(_native.lib().pbg_ppo_grad_host(o, h1, h2, A, ctypes.byref(io)), "pbg_ppo_grad_host")
         else:
@@ -185,7 +196,69 @@ class PPOGrad:
             with torch.cuda.device(self.device):
                 stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
                 _native.check(_native.lib().pbg_ppo_grad_run(self._h, ctypes.byref(io), stream), "pbg_ppo_grad_run")
-        return grad_actor, grad_critic, grad_log_std, stats
+        return out
+
+    def _parts(self, who):
+        if not hasattr(_native.lib(), "pbg_ppo_grad_run_part"):
+            raise _native.PbgError(f"{_native.LIB_PATH} has no pbg_ppo_grad_run_part: a build without the gradient as parts")
+        if self.host or not self._h:
+            raise _native.PbgError(f"PPOGrad.{who}: needs an open object on a GPU")
+        return _native.lib()
+
+    def geometry(self, mb_rows: int):
+        """``(G, Dtot)``: the workgroups ``run`` launches for a minibatch of ``mb_rows`` rows and the floats of one
+        workgroup's partial (pbg_ppo_grad_geometry, no GPU work)."""
+        L = self._parts("geometry")
+        G, dtot = ctypes.c_int(), ctypes.c_int64()
+        _native.check(L.pbg_ppo_grad_geometry(self._h, int(mb_rows), ctypes.byref(G), ctypes.byref(dtot)), "pbg_ppo_grad_geometry")
+        return G.value, dtot.value
+
+    def run_part(self, theta_actor, theta_critic, log_std, obs, act, logp_old, adv, ret, wg_first, wg_count, part_out,
+                 part_stats_out, idx=None, rows=None, adv_norm=None, obs_norm=None, clip_eps: float = 0.2, vf_coef: float = 0.5,
+                 ent_coef: float = 0.0, logp_out=None, v_out=None):
+        """``run``'s tile launch for the workgroups ``wg_first .. wg_first + wg_count - 1`` of the minibatch's ``G``
+        (``geometry``): their partials into ``part_out`` (float32 ``[wg_count, Dtot]``) and ``part_stats_out`` (float64
+        ``[wg_count, 4]``), contiguous tensors (or row ranges of ones) on the object's GPU.  No gradient is written;
+        ``logp_out`` / ``v_out`` get the rows of these workgroups' tiles.  ``wg_count = 0`` launches nothing.  The other
+        arguments and their checks are ``run``'s."""
+        L = self._parts("run_part")
+        io, _ = self._io("run_part", theta_actor, theta_critic, log_std, obs, act, logp_old, adv, ret, idx, rows, adv_norm, obs_norm,
+                         clip_eps, vf_coef, ent_coef, None, None, None, None, logp_out, v_out, outputs=False)
+        wg_first, wg_count = int(wg_first), int(wg_count)
+        G, dtot = self.geometry(io.mb_rows)
+        if wg_first < 0 or wg_count < 0 or wg_first + wg_count > G:
+            raise _native.PbgError(f"PPOGrad.run_part: workgroups {wg_first} .. {wg_first} + {wg_count} outside 0 .. {G}")
+        for name, t, shape, dt in (("part_out", part_out, (wg_count, dtot), torch.float32),
+                                   ("part_stats_out", part_stats_out, (wg_count, 4), torch.float64)):
+            if not self._ok(t, shape, dt):
+                raise _native.PbgError(f"PPOGrad.run_part: {name} must be a contiguous {dt} tensor on {self.device} of shape {shape}")
+        with torch.cuda.device(self.device):
+            stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            _native.check(L.pbg_ppo_grad_run_part(self._h, ctypes.byref(io), wg_first, wg_count, part_out.data_ptr(),
+                                                  part_stats_out.data_ptr(), stream), "pbg_ppo_grad_run_part")
+
+    def reduce(self, theta_actor, theta_critic, log_std, obs, act, logp_old, adv, ret, G, part, part_stats, idx=None, rows=None,
+               adv_norm=None, obs_norm=None, clip_eps: float = 0.2, vf_coef: float = 0.5, ent_coef: float = 0.0, grad_actor=None,
+               grad_critic=None, grad_log_std=None, stats=None, logp_out=None, v_out=None):
+        """``run``'s reduction over the ``G`` partials of ``part`` (float32 ``[G, Dtot]``) and ``part_stats`` (float64
+        ``[G, 4]``): ``(grad_actor, grad_critic, grad_log_std, stats)`` as ``run`` returns them.  ``G`` must be
+        ``geometry``'s for the minibatch; the other arguments and their checks are ``run``'s (of them the launch reads
+        the minibatch's size and ``ent_coef``)."""
+        L = self._parts("reduce")
+        io, out = self._io("reduce", theta_actor, theta_critic, log_std, obs, act, logp_old, adv, ret, idx, rows, adv_norm, obs_norm,
+                           clip_eps, vf_coef, ent_coef, grad_actor, grad_critic, grad_log_std, stats, logp_out, v_out)
+        G = int(G)
+        Gq, dtot = self.geometry(io.mb_rows)
+        if G != Gq:
+            raise _native.PbgError(f"PPOGrad.reduce: G = {G} is not the {Gq} workgroups of {io.mb_rows} minibatch rows")
+        for name, t, shape, dt in (("part", part, (G, dtot), torch.float32), ("part_stats", part_stats, (G, 4), torch.float64)):
+            if not self._ok(t, shape, dt):
+                raise _native.PbgError(f"PPOGrad.reduce: {name} must be a contiguous {dt} tensor on {self.device} of shape {shape}")
+        with torch.cuda.device(self.device):
+            stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            _native.check(L.pbg_ppo_grad_reduce(self._h, ctypes.byref(io), G, part.data_ptr(), part_stats.data_ptr(), stream),
+                          "pbg_ppo_grad_reduce")
+        return out
 
     def close(self):
         if self._h:
@@ -532,6 +605,7 @@ class PPO:
                  graph=False, permutation: str = "torch", lr_schedule=None, schedule_iterations=None,
                  grad_path: str = "fma"):
         n, dev = env.num_envs, env.device
+        nb = self._batch_envs(env)   # the envs whose rows make one update's batch: the env's own
         if backward not in ("torch", "hip"):
             raise _native.PbgError(f"PPO: backward must be 'torch' or 'hip', got {backward!r}")
         if optimizer not in ("torch", "hip"):
@@ -564,7 +638,7 @@ class PPO:
         if n % 2 != 0 or not env.autoreset:
             raise _native.PbgError("PPO: the env must have an even number of envs (the actors are populations of one "
                                    "pair) and autoreset=True")
-        if int(steps) < 1 or int(epochs) < 1 or int(minibatches) < 1 or (int(steps) * n) % int(minibatches) != 0:
+        if int(steps) < 1 or int(epochs) < 1 or int(minibatches) < 1 or (int(steps) * nb) % int(minibatches) != 0:
             raise _native.PbgError("PPO: steps, epochs, minibatches must be >= 1 and steps * num_envs a multiple of minibatches")
         self.env, self.steps, self.seed = env, int(steps), int(seed)
         self.gamma, self.lam, self.clip, self.epochs, self.minibatches = float(gamma), float(lam), float(clip), int(epochs), \
@@ -589,7 +663,7 @@ class PPO:
         self.iteration = 0
         self.obs_stats, self.obs_clip = None, float(obs_clip)
         if obs_norm:
-            self.obs_stats = ObsStats(obs_dim, n, group=n // 2, device=dev)
+            self.obs_stats = ObsStats(obs_dim, nb, group=nb // 2, device=dev)
             self._set_norm()  # the initial totals' normaliser
         T = self.steps
         kw = dict(dtype=torch.float32, device=dev)
@@ -600,14 +674,14 @@ class PPO:
         self.grad = None
         if backward == "hip":
             # the gradient tensors pbg_ppo_grad writes, bound once to the parameters' .grad
-            self.grad = PPOGrad(self.actor_dims, (T * n) // self.minibatches, dev, path=grad_path)
+            self.grad = PPOGrad(self.actor_dims, (T * nb) // self.minibatches, dev, path=grad_path)
             for p in (self.actor_theta, self.critic_theta, self.log_std):
                 p.grad = torch.zeros_like(p.data)
             self._grad_stats = torch.zeros(4, dtype=torch.float64, device=dev)
         self.adam = self._graph = self.perm = self._it_dev = self._iter_graph = None
         self.permutation, self.lr_schedule, self.graph_iteration = permutation, lr_schedule, graph == "iteration"
         if optimizer == "hip":
-            if norm_adv and (T * n) // self.minibatches < 2:
+            if norm_adv and (T * nb) // self.minibatches < 2:
                 raise _native.PbgError("PPO: optimizer='hip' with norm_adv needs minibatches of at least 2 rows")
             self._params = [self.actor_theta.data, self.critic_theta.data, self.log_std.data]
             self._grads = [self.actor_theta.grad, self.critic_theta.grad, self.log_std.grad]
@@ -627,9 +701,12 @@ class PPO:
                 self.perm = Permutation(self.seed, dev)
             if graph or permutation == "device":
                 # what a replay reads and a new iteration must refill in place
-                self._perm = torch.zeros((self.epochs, self.minibatches, (T * n) // self.minibatches), dtype=torch.int64, device=dev)
-                self._logp_old = torch.zeros(T * n, **kw)
+                self._perm = torch.zeros((self.epochs, self.minibatches, (T * nb) // self.minibatches), dtype=torch.int64, device=dev)
+                self._logp_old = torch.zeros(T * nb, **kw)
         env.reset()
+
+    def _batch_envs(self, env) -> int:
+        return env.num_envs
 
     def _set_norm(self):
         mean, inv_std = self.obs_stats.finalize()
@@ -877,3 +954,154 @@ class PPO:
         for o in (self.actor, self.critic, self.noise, self.obs_stats, self.grad, self.adam, self.perm):
             if o is not None:
                 o.close()
+
+
+def share_block_bytes(share: int, dtot: int) -> int:
+    """The bytes of one rank's block of the partial all-gather: ``share`` rows of 4 float64 stats, then ``share`` rows of
+    ``dtot`` float32 partials, rounded up to a multiple of 8 so that in the gathered ``[world, bytes]`` array every
+    rank's doubles start 8-byte aligned whatever ``share`` and ``dtot`` are."""
+    return 32 * share + 8 * ((share * dtot + 1) // 2)
+
+
+def share_views(block, share: int, dtot: int):
+    """A block of ``share_block_bytes`` uint8 as ``(stats float64 [share, 4], part float32 [share, dtot])``, views of
+    its memory."""
+    return block[:32 * share].view(torch.float64).view(share, 4), \
+        block[32 * share:32 * share + 4 * share * dtot].view(torch.float32).view(share, dtot)
+
+
+class ShardedPPO(PPO):
+    """Data-parallel ``PPO`` over a ``ShardedVecEnv`` (one process per rank, ``torch.distributed`` initialised by the
+    caller; ``group``: its process group, ``None`` the default one) that holds, on every rank, the bits of the
+    one-process ``PPO(VecEnv(num_global), backward="hip", optimizer="hip", permutation="device")`` (DESIGN.md section
+    18).  Each rank collects on its shard as ``PPO.collect`` does -- the reset noise, the action noise and the
+    networks do not depend on the shard -- one ``distributed.gather_traj`` gives every rank the global batch in the
+    global row order, every rank draws the same permutations and the same ``adv_norm``, runs the workgroups
+    ``shard_range(G, rank, world)`` of each minibatch's gradient (``PPOGrad.run_part``), all-gathers the float32
+    partials and the float64 stats, and runs the unchanged reduction and ``AdamClip.step`` on them.  With
+    ``obs_norm=True`` the ranks' statistics slots are gathered in rank order into every rank's object before
+    ``finalize``.  Needs ``backward="hip"``, ``optimizer="hip"``, ``permutation="device"`` and ``graph=False`` (the
+    defaults here), equal shards of an even number of envs (a multiple of 32 with ``obs_norm``).  With no process
+    group initialised it runs as world 1: every workgroup as one part, no collective.  Under gloo the collectives
+    are staged through the host."""
+
+    _REQUIRED = dict(backward="hip", optimizer="hip", permutation="device", graph=False)
+
+    def __init__(self, sharded_env, group=None, **ppo_kwargs):
+        import torch.distributed as dist
+        from .distributed import shard_range
+        for name, want in self._REQUIRED.items():
+            got = ppo_kwargs.setdefault(name, want)
+            if got != want or type(got) is not type(want):
+                raise _native.PbgError(f"ShardedPPO: {name} must be {want!r}, got {got!r}")
+        self._group = group
+        self._dist = dist.is_available() and dist.is_initialized()
+        self.world = dist.get_world_size(group) if self._dist else 1
+        self.rank = dist.get_rank(group) if self._dist else 0
+        self.sharded_env, self.num_global = sharded_env, int(sharded_env.num_global)
+        if (sharded_env.world, sharded_env.rank) != (self.world, self.rank):
+            raise _native.PbgError(f"ShardedPPO: the env is shard {sharded_env.rank} of {sharded_env.world}, the process group "
+                                   f"says rank {self.rank} of {self.world}")
+        if self.num_global % self.world != 0:
+            raise _native.PbgError(f"ShardedPPO: {self.num_global} global envs are no multiple of world = {self.world}: the "
+                                   "shards must be equal")
+        n_rank = self.num_global // self.world
+        if n_rank % 2 != 0:
+            raise _native.PbgError(f"ShardedPPO: {n_rank} envs per rank is odd (the actors are populations of one pair)")
+        if ppo_kwargs.get("obs_norm", False) and n_rank % 32 != 0:
+            raise _native.PbgError(f"ShardedPPO: obs_norm needs the {n_rank} envs per rank to be a multiple of 32, so that every "
+                                   "rank's statistics tiles are tiles of the global trainer")
+        self._shard_range = shard_range
+        super().__init__(sharded_env.env, **ppo_kwargs)
+        dev, T = self.env.device, self.steps
+        o, A = self.actor_dims[0], self.actor_dims[3]
+        B = T * self.num_global
+        self._mb_rows = B // self.minibatches
+        self._G, self._dtot = self.grad.geometry(self._mb_rows)
+        if self._G < 1:
+            raise _native.PbgError(f"ShardedPPO: a minibatch of {self._mb_rows} rows has no workgroup")
+        self._wg0, self._wgn = shard_range(self._G, self.rank, self.world)
+        share = -(-self._G // self.world)
+        # one rank's share as one block of bytes (share_block_bytes): what one all-gather moves
+        self._send = torch.zeros(share_block_bytes(share, self._dtot), dtype=torch.uint8, device=dev)
+        self._share = share
+        self._part = torch.zeros((self._G, self._dtot), dtype=torch.float32, device=dev)
+        self._part_stats = torch.zeros((self._G, 4), dtype=torch.float64, device=dev)
+        kw = dict(dtype=torch.float32, device=dev)
+        self._packed = torch.zeros((T, self.env.num_envs, o + A + 3), **kw)
+        self._g_obs, self._g_act = torch.zeros((B, o), **kw), torch.zeros((B, A), **kw)
+        self._g_adv, self._g_ret = torch.zeros(B, **kw), torch.zeros(B, **kw)
+
+    def _batch_envs(self, env) -> int:
+        return self.num_global
+
+    def _all_gather(self, send):
+        from .distributed import all_gather_blocks
+        return all_gather_blocks(send, self._group)
+
+    def _share_views(self, block):
+        return share_views(block, self._share, self._dtot)
+
+    def _minibatch_opt(self, obs, act, logp_old, adv, ret, idx):
+        """``PPO._minibatch_opt`` with the gradient as parts: this rank's workgroups, one all-gather, the reduction."""
+        norm = adv_norm(adv, idx, out=self._adv_norm) if self.norm_adv else None
+        kw = dict(idx=idx, adv_norm=norm, obs_norm=self.actor.obs_norm, clip_eps=self.clip, vf_coef=self.vf_coef,
+                  ent_coef=self.ent_coef)
+        args = (self._params[0], self._params[1], self._params[2], obs, act, logp_old, adv, ret)
+        if self.world == 1:
+            self.grad.run_part(*args, 0, self._G, self._part, self._part_stats, **kw)
+        else:
+            st, pt = self._share_views(self._send)
+            self.grad.run_part(*args, self._wg0, self._wgn, pt[:self._wgn], st[:self._wgn], **kw)
+            got = self._all_gather(self._send)
+            for r in range(self.world):   # the pad rows of the narrower shares are dropped
+                off, cnt = self._shard_range(self._G, r, self.world)
+                st, pt = self._share_views(got[r])
+                self._part_stats[off:off + cnt].copy_(st[:cnt])
+                self._part[off:off + cnt].copy_(pt[:cnt])
+        self.grad.reduce(*args, self._G, self._part, self._part_stats, grad_actor=self._grads[0], grad_critic=self._grads[1],
+                         grad_log_std=self._grads[2], stats=self._grad_stats, **kw)
+        self.adam.step(self._params, self._grads, self._lr_now, (0.9, 0.999), 1e-5, self.max_grad_norm, info=self._opt_info)
+
+    def update(self, b: Batch) -> dict:
+        """One gather of the shard's packed ``(obs | act | logp_old | adv | ret)`` columns, then ``PPO``'s
+        ``epochs x minibatches`` steps on the global batch in the global row order ``t * num_global + e``."""
+        from .distributed import gather_traj
+        T, o, A = self.steps, self.actor_dims[0], self.actor_dims[3]
+        B, p = T * self.num_global, self._packed
+        p[:, :, :o].copy_(b.obs)
+        p[:, :, o:o + A].copy_(b.act)
+        p[:, :, o + A].copy_(b.logp)   # float64 -> float32, the rounding of PPO's own copy
+        p[:, :, o + A + 1].copy_(b.adv)
+        p[:, :, o + A + 2].copy_(b.ret)
+        g = (p if self.world == 1 else gather_traj(p, self.num_global, self._group)).view(B, o + A + 3)
+        self._g_obs.copy_(g[:, :o])
+        self._g_act.copy_(g[:, o:o + A])
+        self._logp_old.copy_(g[:, o + A])
+        self._g_adv.copy_(g[:, o + A + 1])
+        self._g_ret.copy_(g[:, o + A + 2])
+        self._schedule()
+        self._draw(B)
+        for e in range(self.epochs):
+            for idx in self._perm[e]:
+                self._minibatch_opt(self._g_obs, self._g_act, self._logp_old, self._g_adv, self._g_ret, idx)
+        return self._stats_now()
+
+    def _merge_slots(self):
+        """Every rank's used slots, gathered in rank order into this rank's object: the global trainer's slots."""
+        n = self.env.num_envs // 16
+        counts, sums = self.obs_stats.get_slots(0, n)
+        got = self._all_gather(torch.cat((counts.view(n, 1), sums.view(torch.int64)), dim=1))   # 8-byte words, bits kept
+        got = got.view(self.world * n, -1)
+        self.obs_stats.set_slots(0, got[:, 0].contiguous(), got[:, 1:].contiguous().view(torch.float64))
+
+    def _iterate_once(self) -> dict:
+        b = self.collect()
+        stats = self.update(b)
+        if self.obs_stats is not None:
+            if self.world > 1:
+                self._merge_slots()
+            self._set_norm()
+        if self._it_dev is not None:
+            self._it_dev.add_(1)
+        return stats

@@ -1,0 +1,141 @@
+"""The gradient as parts and the statistics' slots without a GPU (include/pbg.h "The PPO gradient as parts, and the
+statistics' slots"): the five entry points exist and are declared, every PBG_E_ARG that needs no device, the
+wrappers' refusals, and the cut of a gradient's workgroups over ranks."""
+import ctypes
+import types
+
+import numpy as np
+import pytest
+
+import pybulletgym_amd  # noqa: F401
+from pybulletgym_amd import _native
+from pybulletgym_amd.distributed import shard_range
+from pybulletgym_amd.policy import ObsStats
+from pybulletgym_amd.ppo import PPOGrad, ShardedPPO, share_block_bytes, share_views
+
+PARTS = ("pbg_ppo_grad_geometry", "pbg_ppo_grad_run_part", "pbg_ppo_grad_reduce", "pbg_obs_stats_get_slots",
+         "pbg_obs_stats_set_slots")
+
+
+def test_the_entry_points_exist_and_are_declared():
+    L = _native.lib()
+    assert set(_native.PPO_PARTS_EXPORTED) == set(PARTS) <= set(_native.EXPORTED)
+    for f in PARTS:
+        assert hasattr(L, f), f
+        assert getattr(L, f).restype is ctypes.c_int and getattr(L, f).argtypes is not None, f
+
+
+def _io():
+    """A pbg_ppo_grad_io_t whose pointers are host arrays: no call below reaches a launch."""
+    keep = [np.zeros(64, np.float32) for _ in range(11)] + [np.zeros(4, np.float64)]
+    p = [a.ctypes.data for a in keep]
+    io = _native.PPOGradIO(batch_rows=4, mb_rows=4, theta_actor=p[0], theta_critic=p[1], log_std=p[2], clip_eps=0.2, vf_coef=0.5,
+                           obs=p[3], act=p[4], logp_old=p[5], adv=p[6], ret=p[7], grad_actor=p[8], grad_critic=p[9],
+                           grad_log_std=p[10], stats=p[11])
+    return io, keep
+
+
+def _refused(rc, what):
+    assert rc == -1, (what, rc)   # PBG_E_ARG
+    assert what.encode() in _native.lib().pbg_last_error(), (what, _native.lib().pbg_last_error())
+
+
+def test_a_null_object_is_refused_before_any_device_call():
+    L = _native.lib()
+    io, keep = _io()
+    buf = np.zeros(64, np.float64)
+    G, dtot = ctypes.c_int(-5), ctypes.c_int64(-5)
+    _refused(L.pbg_ppo_grad_geometry(None, 16, ctypes.byref(G), ctypes.byref(dtot)), "pbg_ppo_grad_geometry")
+    assert (G.value, dtot.value) == (-5, -5)
+    _refused(L.pbg_ppo_grad_run_part(None, ctypes.byref(io), 0, 1, buf.ctypes.data, buf.ctypes.data, None), "pbg_ppo_grad_run_part")
+    _refused(L.pbg_ppo_grad_run_part(None, ctypes.byref(io), 0, -1, buf.ctypes.data, buf.ctypes.data, None), "pbg_ppo_grad_run_part")
+    _refused(L.pbg_ppo_grad_reduce(None, ctypes.byref(io), 1, buf.ctypes.data, buf.ctypes.data, None), "pbg_ppo_grad_reduce")
+    for first, count in ((0, 1), (-1, 1), (0, -1)):
+        _refused(L.pbg_obs_stats_get_slots(None, first, count, buf.ctypes.data, buf.ctypes.data, None), "pbg_obs_stats_get_slots")
+        _refused(L.pbg_obs_stats_set_slots(None, first, count, buf.ctypes.data, buf.ctypes.data, None), "pbg_obs_stats_set_slots")
+
+
+class _Stats(ObsStats):
+    """An ObsStats with no native object behind it: the range check comes before the handle is used."""
+
+    def __init__(self, obs_dim, n_slots):
+        self.obs_dim, self.n_slots, self._h = obs_dim, n_slots, None
+
+
+@pytest.mark.parametrize("first,count", [(-1, 1), (0, -1), (0, 5), (4, 1), (3, 2), (5, 0)])
+def test_obs_stats_slot_calls_refuse_bad_ranges(first, count):
+    import torch
+    s = _Stats(3, 4)
+    with pytest.raises(_native.PbgError, match="outside the object's 0 .. 4"):
+        s.get_slots(first, count)
+    if count >= 0:
+        with pytest.raises(_native.PbgError, match="outside the object's 0 .. 4"):
+            s.set_slots(first, torch.zeros(count, dtype=torch.int64), torch.zeros((count, 6), dtype=torch.float64))
+    with pytest.raises(_native.PbgError, match="outside the object's"):
+        s.set_slots(0, [1, 2], None)   # no tensor of counts: no count
+    with pytest.raises(_native.PbgError, match="closed"):
+        s.get_slots(0, 4)               # a good range reaches the handle
+
+
+def test_the_host_twin_has_no_parts():
+    g = PPOGrad((3, 4, 4, 1), 16)
+    for call in (lambda: g.geometry(16), lambda: g.run_part(*[None] * 12), lambda: g.reduce(*[None] * 11)):
+        with pytest.raises(_native.PbgError, match="needs an open object on a GPU"):
+            call()
+
+
+@pytest.mark.parametrize("W", (1, 2, 3))
+@pytest.mark.parametrize("G", (1, 2, 16, 17))
+def test_shard_range_cuts_the_workgroups_into_consecutive_ranges(G, W):
+    at = 0
+    counts = []
+    for r in range(W):
+        off, cnt = shard_range(G, r, W)
+        assert off == at and cnt >= 0
+        at += cnt
+        counts.append(cnt)
+    assert at == G and max(counts) - min(counts) <= 1 and max(counts) == -(-G // W)
+    assert (0 in counts) == (G < W)
+
+
+@pytest.mark.parametrize("kw,word", [(dict(backward="torch"), "backward"), (dict(optimizer="torch"), "optimizer"),
+                                     (dict(permutation="torch"), "permutation"), (dict(graph=True), "graph"),
+                                     (dict(graph="iteration"), "graph"), (dict(n=7), "odd"),
+                                     (dict(n=48, obs_norm=True), "multiple of 32")])
+def test_sharded_ppo_names_the_option_it_refuses(kw, word):
+    """Before anything is built: the fake shard has no env behind it."""
+    kw = dict(kw)
+    shard = types.SimpleNamespace(num_global=kw.pop("n", 64), world=1, rank=0, env=None)
+    with pytest.raises(_native.PbgError, match=f"ShardedPPO: .*{word}"):
+        ShardedPPO(shard, **kw)
+
+
+@pytest.mark.parametrize("G,W,dtot", [(17, 2, 483), (17, 3, 483), (16, 3, 483), (5, 3, 7), (1, 2, 1), (16, 2, 482)])
+def test_the_gathered_blocks_unpack_at_every_rank_whatever_share_and_dtot_are(G, W, dtot):
+    """What ShardedPPO packs, gathers and unpacks per minibatch, on host tensors: each rank writes its workgroups' rows
+    through the views of its block, the blocks lie rank-major in one array as the all-gather lays them, and every
+    rank's views of that array give the rows back.  An odd share with an odd Dtot (G = 17 over 2 ranks of the
+    pendulum net's 483) puts rank 1's block at an odd multiple of 4 bytes unless the block is padded."""
+    import torch
+    share = -(-G // W)
+    nbytes = share_block_bytes(share, dtot)
+    assert nbytes % 8 == 0 and 0 <= nbytes - share * (32 + 4 * dtot) < 8
+    r = np.random.default_rng(G * 1000 + W)
+    part = r.standard_normal((G, dtot)).astype(np.float32)
+    stats = r.standard_normal((G, 4))
+    gathered = torch.zeros((W, nbytes), dtype=torch.uint8)
+    for rank in range(W):
+        off, cnt = shard_range(G, rank, W)
+        send = torch.zeros(nbytes, dtype=torch.uint8)
+        st, pt = share_views(send, share, dtot)
+        assert st.shape == (share, 4) and pt.shape == (share, dtot) and st.is_contiguous() and pt.is_contiguous()
+        st[:cnt] = torch.from_numpy(stats[off:off + cnt])
+        pt[:cnt] = torch.from_numpy(part[off:off + cnt])
+        gathered[rank] = send
+    got_part, got_stats = torch.zeros((G, dtot)), torch.zeros((G, 4), dtype=torch.float64)
+    for rank in range(W):
+        off, cnt = shard_range(G, rank, W)
+        st, pt = share_views(gathered[rank], share, dtot)
+        got_stats[off:off + cnt] = st[:cnt]
+        got_part[off:off + cnt] = pt[:cnt]
+    assert got_part.numpy().tobytes() == part.tobytes() and got_stats.numpy().tobytes() == stats.tobytes()

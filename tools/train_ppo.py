@@ -8,7 +8,7 @@ as an npz that tools/enjoy.py and MLPPolicy.from_npz load.
          [--ent-coef 0.0] [--vf-coef 0.5] [--seed 0] [--precision 64] [--hidden 64 64] [--out ppo_policy.npz]
          [--obs-norm] [--obs-clip 5.0] [--eval-envs 256] [--eval-steps 200] [--eval-every 1] [--curve curve.json]
          [--backward hip] [--optimizer hip] [--graph [iteration]] [--permutation device]
-         [--lr-schedule linear --schedule-iterations N] [--grad-path mfma]
+         [--lr-schedule linear --schedule-iterations N] [--grad-path mfma] [--sharded]
 
 --obs-norm trains under running observation normalisation (PPO(obs_norm=True)) and saves the final normaliser
 in the npz (obs_mean, obs_inv_std, obs_clip); --curve writes the per-iteration evaluation as JSON.  --optimizer hip
@@ -19,6 +19,12 @@ linear anneals the learning rate to zero over --schedule-iterations iterations f
 --graph iteration (needs --permutation device) replays a whole iteration, rollout included, as one captured graph.
 --grad-path mfma (with --backward hip) takes the gradient from the matrix-core path of pbg_ppo_grad, the one for hidden
 layers wider than 64.
+
+--sharded trains data-parallel (ppo.ShardedPPO: --envs is the global count; --backward, --optimizer and --permutation
+default to hip, hip and device, any other choice is refused by ShardedPPO, and it takes no --graph): one process per
+rank, started with RANK, WORLD_SIZE, MASTER_ADDR and MASTER_PORT in the environment (the env:// convention, e.g. by torchrun); "nccl" with one device per rank when the
+machine has as many GPUs as ranks, else gloo with every rank on cuda:0.  Every rank holds the one-process trainer's
+bits; rank 0 prints and writes the npz.
 
 Per evaluated iteration it prints the noise-free mean policy's mean first-episode return and length over
 --eval-envs envs of a separate batch without auto-reset."""
@@ -56,9 +62,9 @@ def main():
     ap.add_argument("--out", default="ppo_policy.npz")
     ap.add_argument("--obs-norm", action="store_true", help="running observation normalisation")
     ap.add_argument("--obs-clip", type=float, default=5.0)
-    ap.add_argument("--backward", choices=("torch", "hip"), default="torch",
+    ap.add_argument("--backward", choices=("torch", "hip"), default=None,
                     help="the update's gradient: torch autograd, or the HIP backward pass (pbg_ppo_grad)")
-    ap.add_argument("--optimizer", choices=("torch", "hip"), default="torch",
+    ap.add_argument("--optimizer", choices=("torch", "hip"), default=None,
                     help="gradient clipping and Adam: torch, or the HIP step (pbg_ppo_opt; needs --backward hip)")
     def graph_arg(s):
         if s != "iteration":
@@ -68,7 +74,7 @@ def main():
     ap.add_argument("--graph", nargs="?", const=True, default=False, type=graph_arg,
                     help="capture the update as one graph (needs --optimizer hip); --graph iteration: the whole "
                          "iteration (needs --permutation device)")
-    ap.add_argument("--permutation", choices=("torch", "device"), default="torch",
+    ap.add_argument("--permutation", choices=("torch", "device"), default=None,
                     help="the minibatch permutations: torch.randperm, or pbg_perm_fill (needs --optimizer hip)")
     ap.add_argument("--lr-schedule", choices=("linear",), default=None,
                     help="anneal the learning rate on the device (needs --optimizer hip and --schedule-iterations)")
@@ -76,6 +82,8 @@ def main():
     ap.add_argument("--grad-path", choices=("fma", "mfma"), default="fma",
                     help="the path of pbg_ppo_grad: vector FMA, or the matrix cores for wide networks (needs --backward hip)")
     ap.add_argument("--curve", default=None, help="write the per-iteration evaluation here (JSON)")
+    ap.add_argument("--sharded", action="store_true",
+                    help="data-parallel over the ranks of RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT (ShardedPPO)")
     args = ap.parse_args()
 
     import json
@@ -85,25 +93,51 @@ def main():
     from pybulletgym_amd.ppo import PPO
     from pybulletgym_amd.vec_env import VecEnv
 
-    env = VecEnv(args.env_id, args.envs, device="cuda:0", seed=args.seed, autoreset=True, precision=args.precision)
-    test = VecEnv(args.env_id, args.eval_envs, device="cuda:0", seed=args.seed + 1, autoreset=False, precision=args.precision)
-    ppo = PPO(env, hidden=args.hidden, steps=args.steps, seed=args.seed, gamma=args.gamma, lam=args.lam, clip=args.clip,
+    rank, device, say = 0, "cuda:0", print
+    if not args.sharded:   # the defaults
+        args.backward, args.optimizer = args.backward or "torch", args.optimizer or "torch"
+        args.permutation = args.permutation or "torch"
+    if args.sharded:
+        import torch.distributed as dist
+        from pybulletgym_amd.distributed import ShardedVecEnv
+        from pybulletgym_amd.ppo import ShardedPPO
+        if args.graph:
+            ap.error("--sharded takes no --graph")
+        # what ShardedPPO needs where nothing was asked for; an explicit other choice reaches it and is refused by name
+        args.backward, args.optimizer = args.backward or "hip", args.optimizer or "hip"
+        args.permutation = args.permutation or "device"
+        rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
+        one_each = torch.cuda.device_count() >= world
+        device = f"cuda:{rank}" if one_each else "cuda:0"
+        if one_each:
+            torch.cuda.set_device(rank)
+        dist.init_process_group("nccl" if one_each else "gloo", init_method="env://", rank=rank, world_size=world)
+        if rank != 0:
+            say = lambda *a, **k: None  # noqa: E731
+        env = ShardedVecEnv(args.env_id, args.envs, rank, world, device, seed=args.seed, autoreset=True, precision=args.precision)
+        trainer = lambda e, **kw: ShardedPPO(e, graph=False, **kw)  # noqa: E731
+    else:
+        env = VecEnv(args.env_id, args.envs, device=device, seed=args.seed, autoreset=True, precision=args.precision)
+        trainer = lambda e, **kw: PPO(e, graph=args.graph, **kw)  # noqa: E731
+    test = VecEnv(args.env_id, args.eval_envs, device=device, seed=args.seed + 1, autoreset=False, precision=args.precision)
+    ppo = trainer(env, hidden=args.hidden, steps=args.steps, seed=args.seed, gamma=args.gamma, lam=args.lam, clip=args.clip,
               lr=args.lr, epochs=args.epochs, minibatches=args.minibatches, vf_coef=args.vf_coef, ent_coef=args.ent_coef,
               log_std=args.log_std, obs_norm=args.obs_norm, obs_clip=args.obs_clip, backward=args.backward,
-              optimizer=args.optimizer, graph=args.graph, permutation=args.permutation, lr_schedule=args.lr_schedule,
+              optimizer=args.optimizer, permutation=args.permutation, lr_schedule=args.lr_schedule,
               schedule_iterations=args.schedule_iterations, grad_path=args.grad_path)
-    print(f"{args.env_id} (float{args.precision}): {args.envs} envs x {args.steps} steps per iteration, actor MLP "
+    say(f"{args.env_id} (float{args.precision}): {args.envs} envs x {args.steps} steps per iteration, actor MLP "
           f"{ppo.actor_dims}, lr {args.lr}, {args.epochs} epochs x {args.minibatches} minibatches, observation "
           f"normalisation {'on' if args.obs_norm else 'off'}, backward pass {args.backward}, optimizer "
           f"{args.optimizer}{' (one graph per iteration)' if args.graph == 'iteration' else ' (one graph)' if args.graph else ''}, "
-          f"permutation {args.permutation}, lr schedule {args.lr_schedule}, gradient path {args.grad_path}")
+          f"permutation {args.permutation}, lr schedule {args.lr_schedule}, gradient path {args.grad_path}" +
+        (f", {ppo.world} ranks" if args.sharded else ""))
     curve = []
 
     def report(it):
         ret, length = ppo.evaluate(test, args.eval_steps)
         curve.append(dict(iteration=it, return_mean=ret.mean().item(), return_min=ret.min().item(),
                           length_mean=length.double().mean().item(), std_mean=ppo.log_std.data.exp().mean().item()))
-        print(f"iteration {it:4d}: mean policy return mean {ret.mean().item():9.2f} min {ret.min().item():9.2f}  "
+        say(f"iteration {it:4d}: mean policy return mean {ret.mean().item():9.2f} min {ret.min().item():9.2f}  "
               f"first-episode length mean {length.double().mean().item():6.1f} of {args.eval_steps}  "
               f"action std {curve[-1]['std_mean']:.3f}", flush=True)
 
@@ -113,15 +147,18 @@ def main():
         if it % args.eval_every == 0 or it == args.iterations:
             report(it)
     torch.cuda.synchronize()
-    ppo.save_npz(args.out)
-    print(f"wrote {args.out}")
-    if args.curve:
+    if rank == 0:
+        ppo.save_npz(args.out)
+        print(f"wrote {args.out}")
+    if args.curve and rank == 0:
         with open(args.curve, "w") as f:
             json.dump(dict(vars(args), curve=curve), f, indent=1)
         print(f"wrote {args.curve}")
     ppo.close()
     test.close()
-    env.close()
+    (env.env if args.sharded else env).close()
+    if args.sharded:
+        dist.destroy_process_group()
 
 
 if __name__ == "__main__":
