@@ -277,8 +277,17 @@ int pbg_policy_act_host(const pbg_policy* p, int n, const float* obs, float* act
  * handle's n_envs, T = n_steps.  Versioned by struct_size like pbg_create_opts_t: set it to
  * sizeof(pbg_rollout_io_t) of the header the caller was built with; the library reads only the
  * fields that size covers (fields appended after done_traj, the end of the first version, take zero),
- * so a caller built with an older header keeps working.  PBG_E_ARG for a size below the first
- * version's, above the library's, or not a multiple of 4. */
+ * so a caller built with an older header keeps working.  Two sizes exist: the first version's, which ends
+ * with done_traj, and version 2's, which appends trunc_traj and term_obs_traj.  PBG_E_ARG for any other
+ * size.
+ *
+ * Version 2, truncation records.  trunc_traj and term_obs_traj are given both or
+ * neither, and only with autoreset != 0: any other combination is PBG_E_ARG before any launch.  In step t
+ * the handle's step gets row t of the two arrays as pbg_step_io_t.trunc / .term_obs and writes them as it
+ * does there: trunc_traj[t][e] for every env (truncated by the TimeLimit and not terminated), and row
+ * (t, e) of term_obs_traj, the observation before env e's reset, ONLY where done_traj[t][e] (or done[e]
+ * without trajectories) is set.  Every other row of term_obs_traj is never written and must never be
+ * read.  The launches stay 2 T + 1 and nothing else the rollout produces changes. */
 typedef struct {
   uint32_t struct_size;
   int n_steps;            /* T >= 1 */
@@ -305,6 +314,9 @@ typedef struct {
   float* act_traj;        /* [T, n, act_dim] */
   float* rew_traj;        /* [T, n] float32 reward */
   uint8_t* done_traj;     /* [T, n] */
+  /* version 2: nullable, both or neither, autoreset != 0 only */
+  uint8_t* trunc_traj;    /* [T, n] truncated and not terminated */
+  float* term_obs_traj;   /* [T, n, obs_dim] the observation before the reset, rows where done is set */
 } pbg_rollout_io_t;
 
 /* T closed-loop steps: per step act = pi(obs), then the handle's step (pbg_step_ex) with `autoreset`,
@@ -514,9 +526,10 @@ int pbg_population_attach_action_noise(pbg_population* p, pbg_action_noise* z);
  *   delta = (r + (gamma * v[t+1]) * nd) - v[t]
  *   A     = delta + (gl * nd) * A
  *   adv[t][e] = (float)A;  ret[t][e] = (float)(A + v[t])
- * done includes the TimeLimit truncation (the trajectories carry no separate flag): a truncated episode is
- * treated as terminal, nothing bootstraps through it.  PBG_E_ARG (before any HIP call) for T < 1, n < 1 or
- * a NULL array.  pbg_gae_host: the same loop on HOST pointers, the same bits; needs no GPU. */
+ * done includes the TimeLimit truncation, and pbg_gae alone treats a truncated episode as terminal: nothing
+ * bootstraps through it.  pbg_gae_trunc ("Truncation bootstrapping" below) takes the rollout's trunc_traj and
+ * the values of the terminal observations and bootstraps through it.  PBG_E_ARG (before any HIP call) for
+ * T < 1, n < 1 or a NULL array.  pbg_gae_host: the same loop on HOST pointers, the same bits; needs no GPU. */
 int pbg_gae(int T, int n, const float* rew_traj, const uint8_t* done_traj, const float* value, double gamma,
             double lambda, float* adv_out, float* ret_out, void* stream);
 int pbg_gae_host(int T, int n, const float* rew_traj, const uint8_t* done_traj, const float* value, double gamma,
@@ -879,6 +892,46 @@ int pbg_ppo_grad_reduce(pbg_ppo_grad* g, const pbg_ppo_grad_io_t* io, int G, con
  * the object that saw the whole launch, bit for bit.  A slot that was never written adds +0.0 and 0. */
 int pbg_obs_stats_get_slots(const pbg_obs_stats* s, int first, int count, int64_t* counts_out, double* sums_out, void* stream);
 int pbg_obs_stats_set_slots(pbg_obs_stats* s, int first, int count, const int64_t* counts, const double* sums, void* stream);
+
+/* ---- Truncation bootstrapping (appended; nothing above changes) ----
+ * Every env sits under gym's TimeLimit, and a time limit is not a death: the return goes on past it.  A learner
+ * that separates `terminated` from `truncated` bootstraps the value of the observation the episode was cut at,
+ * V(terminal_obs), through a truncation.  The rollout records what that needs (pbg_rollout_io_t version 2:
+ * trunc_traj, term_obs_traj), pbg_population_act_where values the flagged rows alone, and pbg_gae_trunc uses them.
+ *
+ * pbg_population_act_where: out[T, n, act_dim] from obs[T, n, obs_dim] under flags[T, n] (DEVICE arrays).  n is a
+ * positive multiple of the P members; row (t, e) belongs to member e / (n / P), the rollout's mapping.  Where
+ * flags[t][e] != 0, out's row is the row's output, through the population's normaliser when one is set: the bits
+ * pbg_population_act gives for that row (the same k-ascending fmaf chain, which no other row enters).  Where the
+ * flag is 0, out's row is +0.0f in every component and the obs row is NOT read from memory (it is zero-filled in
+ * LDS, like the rows past a member's last).  Every element of out is written by the launch.  One launch of
+ * T * P * ceil(n / P / 16) workgroups, tiles that never straddle a member or a time step; no atomics, no host
+ * work, any stream, capturable.  A tile with no flag set writes its zeros and returns before it touches the
+ * weights: the decision is one ballot over the tile's flag bytes, uniform over the workgroup.  Attached statistics
+ * and action noise are ignored, as by pbg_population_act.  PBG_E_ARG (before any HIP call) for a NULL pointer,
+ * T < 1, n < 1, n % P != 0, a host-only population, or T * tiles beyond the grid limit (2^31 - 1). */
+int pbg_population_act_where(const pbg_population* p, int T, int n, const uint8_t* flags, const float* obs, float* out,
+                             void* stream);
+
+/* pbg_gae with a truncation flag: trunc_traj uint8 [T, n] and term_value float32 [T, n] (pbg_population_act_where's
+ * output for the critic over term_obs_traj under trunc_traj) next to pbg_gae's arrays.  One launch, a lane per env,
+ * t descending, float64, nothing contracted, in this order (A = 0 before t = T - 1; gl = gamma * lambda):
+ *   tr    = trunc[t][e] != 0
+ *   nd    = done[t][e] ? 0.0 : 1.0
+ *   vn    = tr ? (double)term_value[t][e] : (double)value[t+1][e]
+ *   nb    = tr ? 1.0 : nd
+ *   delta = (r + (gamma * vn) * nb) - v[t]
+ *   A     = delta + (gl * nd) * A
+ *   adv[t][e] = (float)A;  ret[t][e] = (float)(A + v[t])
+ * term_value is read only where trunc is set.  With trunc all zero this is pbg_gae's loop and gives its bits.  The
+ * step kernels set trunc only together with done; a trunc flag without done is still defined by the lines above (the
+ * step bootstraps term_value and the accumulation runs on through it).  PBG_E_ARG (before any HIP call) for T < 1,
+ * n < 1 or a NULL array.  pbg_gae_trunc_host: the same loop on HOST pointers, the same bits; needs no GPU. */
+int pbg_gae_trunc(int T, int n, const float* rew_traj, const uint8_t* done_traj, const uint8_t* trunc_traj, const float* value,
+                  const float* term_value, double gamma, double lambda, float* adv_out, float* ret_out, void* stream);
+int pbg_gae_trunc_host(int T, int n, const float* rew_traj, const uint8_t* done_traj, const uint8_t* trunc_traj,
+                       const float* value, const float* term_value, double gamma, double lambda, float* adv_out,
+                       float* ret_out);
 
 #ifdef __cplusplus
 }

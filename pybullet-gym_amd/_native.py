@@ -60,7 +60,8 @@ class SimParams(ctypes.Structure):
 
 
 class RolloutIO(ctypes.Structure):
-    """pbg_rollout_io_t (pbg_rollout): versioned by struct_size; device pointers of caller-owned buffers."""
+    """pbg_rollout_io_t (pbg_rollout): versioned by struct_size; device pointers of caller-owned buffers.  The
+    struct's first version, which ends with done_traj: the library keeps accepting it."""
     _fields_ = [("struct_size", ctypes.c_uint32), ("n_steps", ctypes.c_int), ("autoreset", ctypes.c_int),
                 ("reserved", ctypes.c_int), ("obs", ctypes.c_void_p), ("act", ctypes.c_void_p),
                 ("rew", ctypes.c_void_p), ("rew64", ctypes.c_void_p), ("done", ctypes.c_void_p),
@@ -69,7 +70,12 @@ class RolloutIO(ctypes.Structure):
                 ("act_traj", ctypes.c_void_p), ("rew_traj", ctypes.c_void_p), ("done_traj", ctypes.c_void_p)]
 
     def __init__(self, **kw):
-        super().__init__(struct_size=ctypes.sizeof(RolloutIO), **kw)
+        super().__init__(struct_size=ctypes.sizeof(type(self)), **kw)
+
+
+class RolloutIO2(RolloutIO):
+    """pbg_rollout_io_t version 2: the appended truncation records, both or neither (autoreset only)."""
+    _fields_ = [("trunc_traj", ctypes.c_void_p), ("term_obs_traj", ctypes.c_void_p)]
 
 
 PPO_GRAD_FMA, PPO_GRAD_MFMA = 0, 1  # PBG_PPO_GRAD_FMA, PBG_PPO_GRAD_MFMA
@@ -276,6 +282,13 @@ def lib():
         L.pbg_obs_stats_set_slots.argtypes = [H, I, I, P, P, P]
         for f in PPO_PARTS_EXPORTED:
             getattr(L, f).restype = I
+    if hasattr(L, "pbg_population_act_where"):  # truncation bootstrapping: the masked actor launch and its GAE
+        D = ctypes.c_double
+        L.pbg_population_act_where.argtypes = [H, I, I, P, P, P, P]
+        L.pbg_gae_trunc.argtypes = [I, I, P, P, P, P, P, D, D, P, P, P]
+        L.pbg_gae_trunc_host.argtypes = [I, I, P, P, P, P, P, D, D, P, P]
+        for f in TRUNC_EXPORTED:
+            getattr(L, f).restype = I
     for f in ("pbg_info", "pbg_reset", "pbg_step", "pbg_step_ex", "pbg_get_state", "pbg_set_state",
               "pbg_pack_record_sizes", "pbg_pack", "pbg_create_debug", "pbg_sample_actions", "pbg_create_ex",
               "pbg_default_sim_params", "pbg_get_sim_params", "pbg_create_v2", "pbg_precision"):
@@ -304,12 +317,14 @@ PERM_EXPORTED = ("pbg_perm_create", "pbg_perm_destroy", "pbg_perm_fill", "pbg_pe
                  "pbg_perm_host", "pbg_ppo_lr_linear", "pbg_ppo_lr_linear_host")
 PPO_PARTS_EXPORTED = ("pbg_ppo_grad_geometry", "pbg_ppo_grad_run_part", "pbg_ppo_grad_reduce", "pbg_obs_stats_get_slots",
                       "pbg_obs_stats_set_slots")
-EXPORTED = ("pbg_create", "pbg_create_debug", "pbg_create_ex", "pbg_create_v2", "pbg_precision",
+TRUNC_EXPORTED = ("pbg_population_act_where", "pbg_gae_trunc", "pbg_gae_trunc_host")
+EXPORTED =("pbg_create", "pbg_create_debug", "pbg_create_ex", "pbg_create_v2", "pbg_precision",
             "pbg_default_sim_params", "pbg_get_sim_params",
             "pbg_destroy", "pbg_info", "pbg_reset", "pbg_step", "pbg_step_ex",
             "pbg_get_state", "pbg_set_state", "pbg_pack_record_sizes", "pbg_pack", "pbg_sample_actions",
             "pbg_debug_poison", "pbg_last_error") + POLICY_EXPORTED + POPULATION_EXPORTED + OBS_NORM_EXPORTED + \
-    ACTION_NOISE_EXPORTED + PPO_GRAD_EXPORTED + PPO_OPT_EXPORTED + PERM_EXPORTED + PPO_GRAD_EX_EXPORTED + PPO_PARTS_EXPORTED
+    ACTION_NOISE_EXPORTED + PPO_GRAD_EXPORTED + PPO_OPT_EXPORTED + PERM_EXPORTED + PPO_GRAD_EX_EXPORTED + PPO_PARTS_EXPORTED + \
+    TRUNC_EXPORTED
 
 
 def check(rc: int, what: str):

@@ -34,31 +34,13 @@ __global__ __launch_bounds__(256) void action_noise_fill_kernel(int n, int act_d
     if (4 * b + t < act_dim) out[4 * b + t] = z[t];
 }
 
-// pbg.h's scan for env e, host and device: float64, nothing contracted; gl = gamma * lambda
-__host__ __device__ __forceinline__ void gae_env(int T, int n, int e, const float* __restrict__ rew,
-                                                 const uint8_t* __restrict__ done, const float* __restrict__ value, double gamma,
-                                                 double gl, float* __restrict__ adv, float* __restrict__ ret) {
-#pragma clang fp contract(off)
-  double A = 0.0;
-  double vnext = (double)value[(size_t)T * n + e];
-  for (int t = T - 1; t >= 0; t--) {
-    const size_t at = (size_t)t * n + e;
-    const double nd = done[at] ? 0.0 : 1.0;
-    const double v = (double)value[at];
-    const double delta = ((double)rew[at] + (gamma * vnext) * nd) - v;
-    A = delta + (gl * nd) * A;
-    adv[at] = (float)A;
-    ret[at] = (float)(A + v);
-    vnext = v;
-  }
-}
-
-// a lane per env: every row access is coalesced over the envs
+// a lane per env: every row access is coalesced over the envs; the scan is pbg_policy_dev.h's gae_env, without
+// the truncation lines (pbg_trunc.hip's kernel runs it with them)
 __global__ __launch_bounds__(256) void gae_kernel(int T, int n, const float* __restrict__ rew, const uint8_t* __restrict__ done,
                                                   const float* __restrict__ value, double gamma, double gl,
                                                   float* __restrict__ adv, float* __restrict__ ret) {
   const int e = blockIdx.x * 256 + threadIdx.x;
-  if (e < n) gae_env(T, n, e, rew, done, value, gamma, gl, adv, ret);
+  if (e < n) gae_env<false>(T, n, e, rew, done, nullptr, value, nullptr, gamma, gl, adv, ret);
 }
 
 int launched(const char* what) {
@@ -181,7 +163,7 @@ int pbg_gae_host(int T, int n, const float* rew_traj, const uint8_t* done_traj, 
   if (!gae_args_ok(T, n, rew_traj, done_traj, value, adv_out, ret_out))
     return pbg::capi_fail(PBG_E_ARG, "pbg_gae_host: T and n must be >= 1 and no array NULL");
   const double gl = gamma * lambda;
-  for (int e = 0; e < n; e++) gae_env(T, n, e, rew_traj, done_traj, value, gamma, gl, adv_out, ret_out);
+  for (int e = 0; e < n; e++) gae_env<false>(T, n, e, rew_traj, done_traj, nullptr, value, nullptr, gamma, gl, adv_out, ret_out);
   return PBG_OK;
 }
 

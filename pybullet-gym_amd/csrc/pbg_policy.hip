@@ -246,10 +246,12 @@ int pbg_rollout(pbg_handle* h, const pbg_policy* p, const pbg_rollout_io_t* uio,
 
 int pbg::policy::rollout_loop(const char* who, pbg_handle* h, const pbg_rollout_io_t* uio, void* stream, const Actor& a) {
   char msg[200];
-  // versioned like pbg_create_opts_t: the first version ends with done_traj; read only what the caller's
-  // struct holds, fields appended later take zero (their default) for an older caller
+  // versioned like pbg_create_opts_t: the first version ends with done_traj, the second with term_obs_traj; read
+  // only what the caller's struct holds, fields appended later take zero (their default) for an older caller
   constexpr uint32_t v1_size = (uint32_t)(offsetof(pbg_rollout_io_t, done_traj) + sizeof(uint8_t*));
-  if (uio->struct_size < v1_size || uio->struct_size > (uint32_t)sizeof(pbg_rollout_io_t) || uio->struct_size % 4u != 0u) {
+  constexpr uint32_t v2_size = (uint32_t)(offsetof(pbg_rollout_io_t, term_obs_traj) + sizeof(float*));
+  static_assert(v2_size == sizeof(pbg_rollout_io_t), "a field appended to pbg_rollout_io_t needs its version here");
+  if (uio->struct_size != v1_size && uio->struct_size != v2_size) {
     snprintf(msg, sizeof(msg), "%s: io->struct_size %u is not a pbg_rollout_io_t size", who, uio->struct_size);
     return pbg::capi_fail(PBG_E_ARG, msg);
   }
@@ -297,6 +299,10 @@ int pbg::policy::rollout_loop(const char* who, pbg_handle* h, const pbg_rollout_
     snprintf(msg, sizeof(msg), "%s: NULL required buffer", who);
     return pbg::capi_fail(PBG_E_ARG, msg);
   }
+  if ((io->trunc_traj != nullptr) != (io->term_obs_traj != nullptr) || (io->trunc_traj && !io->autoreset)) {
+    snprintf(msg, sizeof(msg), "%s: trunc_traj and term_obs_traj go together (both or neither) and need autoreset != 0", who);
+    return pbg::capi_fail(PBG_E_ARG, msg);
+  }
   DeviceGuard dg(dev);
   hipStream_t s = (hipStream_t)stream;
   const int n = info.n_envs;
@@ -325,6 +331,9 @@ int pbg::policy::rollout_loop(const char* who, pbg_handle* h, const pbg_rollout_
     // the step writes reward and done straight into the trajectory rows when there are any
     st.rew = io->rew_traj ? io->rew_traj + (size_t)t * n : io->rew;
     st.done = io->done_traj ? io->done_traj + (size_t)t * n : io->done;
+    // version 2: the step writes the truncation flags and, for the envs it resets, the observation before the reset
+    st.trunc = io->trunc_traj ? io->trunc_traj + (size_t)t * n : nullptr;
+    st.term_obs = io->term_obs_traj ? io->term_obs_traj + (size_t)t * no : nullptr;
     const int rc = pbg_step_ex(h, &st, stream);
     if (rc) return rc;
     bk.rew64 = io->rew64;

@@ -431,6 +431,34 @@ __host__ __device__ __forceinline__ float ppo_critic_row(float v, float ret, dou
   return (float)(vf_coef * d * inv_bm);
 }
 
+// pbg.h's advantage scan for env e, host and device (pbg_actnoise.hip: pbg_gae; pbg_trunc.hip: pbg_gae_trunc): float64,
+// nothing contracted; gl = gamma * lambda.  TRUNC: pbg_gae_trunc's lines (trunc, term_value: its arrays); without it
+// neither is looked at, so pbg_gae's instantiation is the loop it was before truncations were recorded.
+template <bool TRUNC>
+__host__ __device__ __forceinline__ void gae_env(int T, int n, int e, const float* __restrict__ rew,
+                                                 const uint8_t* __restrict__ done, const uint8_t* __restrict__ trunc,
+                                                 const float* __restrict__ value, const float* __restrict__ term_value,
+                                                 double gamma, double gl, float* __restrict__ adv, float* __restrict__ ret) {
+#pragma clang fp contract(off)
+  double A = 0.0;
+  double vnext = (double)value[(size_t)T * n + e];
+  for (int t = T - 1; t >= 0; t--) {
+    const size_t at = (size_t)t * n + e;
+    const double nd = done[at] ? 0.0 : 1.0;
+    const double v = (double)value[at];
+    double vn = vnext, nb = nd;
+    if (TRUNC && trunc[at] != 0) {
+      vn = (double)term_value[at];
+      nb = 1.0;
+    }
+    const double delta = ((double)rew[at] + (gamma * vn) * nb) - v;
+    A = delta + (gl * nd) * A;
+    adv[at] = (float)A;
+    ret[at] = (float)(A + v);
+    vnext = v;
+  }
+}
+
 // workgroups (= slots) of an actor launch over n rows in groups of G (n a multiple of G > 0)
 inline long long tiles_of(int n, int G) { return (long long)(n / G) * ((G + PT - 1) / PT); }
 
@@ -510,6 +538,13 @@ struct pbg_obs_stats {
   int64_t* slot_count;
 
   pbg::policy::Slot slot0() const { return pbg::policy::Slot{slot_count, slot_sum, slot_sumsq}; }
+};
+
+// pbg.h pbg_population: an Actor of 2 n_pairs members (a.params: member m's vector at m D) and the global index of
+// its first pair (pbg_population.hip owns it; pbg_trunc.hip's masked launch reads the actor)
+struct pbg_population {
+  pbg::policy::Actor a;
+  int n_pairs, pair0;
 };
 
 // pbg.h pbg_action_noise: one device allocation, std [act_dim] float32 then the uint32 step counter

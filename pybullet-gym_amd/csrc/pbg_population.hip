@@ -24,12 +24,6 @@
 #include "pbg_es_noise.h"
 #include "pbg_policy_dev.h"
 
-// an Actor of 2 n_pairs members (a.params: member m's vector at m D) and the global index of its first pair
-struct pbg_population {
-  pbg::policy::Actor a;
-  int n_pairs, pair0;
-};
-
 namespace {
 
 using namespace pbg::policy;

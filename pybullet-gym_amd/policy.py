@@ -588,3 +588,29 @@ class MLPPopulation(_NativeObject):
         _native.check(_native.lib().pbg_population_act(p, n, x.data_ptr(), y.data_ptr(), self._stream()),
                       "pbg_population_act")
         return y
+
+    def act_where(self, flags, obs, out=None):
+        """``act`` for the flagged rows of a trajectory alone (pbg_population_act_where, one launch): ``flags`` uint8
+        ``[T, n]``, ``obs`` float32 ``[T, n, obs_dim]`` -> ``out`` float32 ``[T, n, act_dim]``, contiguous tensors on
+        the device, ``n`` a positive multiple of ``n_members`` (row ``(t, e)`` through member ``e // (n //
+        n_members)``, the rollout's mapping).  Where the flag is set the row holds ``act``'s bits for it; elsewhere it
+        is ``+0.0`` and the ``obs`` row is never read (it may be uninitialised memory, as the unwritten rows of
+        ``RolloutResult.term_obs_traj`` are).  A 16-row tile without a flag returns before it touches the weights."""
+        import torch
+        p = self._open("act_where")
+        if not hasattr(_native.lib(), "pbg_population_act_where"):
+            raise _native.PbgError(f"{_native.LIB_PATH} has no pbg_population_act_where: a build without truncation "
+                                   "bootstrapping")
+        if not isinstance(flags, torch.Tensor) or flags.dim() != 2:
+            raise _native.PbgError("MLPPopulation.act_where: flags must be a uint8 [T, n] tensor")
+        T, n = (int(d) for d in flags.shape)
+        if T < 1 or n < 1 or n % self.n_members != 0:
+            raise _native.PbgError(f"MLPPopulation.act_where: T = {T} must be >= 1 and n = {n} a positive multiple of the "
+                                   f"{self.n_members} members")
+        flags = self._vec(flags, "act_where", "flags", (T, n), torch.uint8)
+        obs = self._vec(obs, "act_where", "obs", (T, n, self.obs_dim))
+        out = torch.empty((T, n, self.act_dim), dtype=torch.float32, device=self.device) if out is None else out
+        out = self._vec(out, "act_where", "out", (T, n, self.act_dim))
+        _native.check(_native.lib().pbg_population_act_where(p, T, n, flags.data_ptr(), obs.data_ptr(), out.data_ptr(),
+                                                             self._stream()), "pbg_population_act_where")
+        return out

@@ -25,14 +25,24 @@ from . import _native
 from .policy import ActionNoise, MLPPopulation, ObsStats
 
 
-def gae(rew_traj, done_traj, value, gamma: float = 0.99, lam: float = 0.95, adv=None, ret=None):
+def gae(rew_traj, done_traj, value, gamma: float = 0.99, lam: float = 0.95, adv=None, ret=None, trunc_traj=None,
+        term_value=None):
     """``(adv, ret)``, float32 ``[T, n]``: pbg_gae, one launch, a lane per env, float64 arithmetic in the order
     include/pbg.h states.  ``rew_traj`` float32 ``[T, n]``, ``done_traj`` uint8 ``[T, n]``, ``value`` float32
     ``[T + 1, n]`` (row T: the value of the observation after the last step), contiguous tensors on one GPU.
-    ``done`` includes the TimeLimit truncation: a truncated episode is treated as terminal, nothing bootstraps
-    through it.  numpy arrays instead of tensors run the same loop on the host (pbg_gae_host, the same bits)."""
+    ``done`` includes the TimeLimit truncation, and without the two arguments below a truncated episode is treated
+    as terminal: nothing bootstraps through it.  ``trunc_traj`` (uint8 ``[T, n]``) and ``term_value`` (float32
+    ``[T, n]``: the critic's value of the observation the episode was cut at, read only where ``trunc_traj`` is
+    set), both or neither: pbg_gae_trunc, which bootstraps ``term_value`` through a truncated step; with
+    ``trunc_traj`` all zero it gives pbg_gae's bits.  numpy arrays instead of tensors run the same loop on the host
+    (pbg_gae_host, pbg_gae_trunc_host: the same bits)."""
     if not hasattr(_native.lib(), "pbg_gae"):
         raise _native.PbgError(f"{_native.LIB_PATH} has no pbg_gae: a build without advantage estimation")
+    if (trunc_traj is None) != (term_value is None):
+        raise _native.PbgError("gae: trunc_traj and term_value go together (both or neither)")
+    trunc = trunc_traj is not None
+    if trunc and not hasattr(_native.lib(), "pbg_gae_trunc"):
+        raise _native.PbgError(f"{_native.LIB_PATH} has no pbg_gae_trunc: a build without truncation bootstrapping")
     host = isinstance(rew_traj, np.ndarray)
     if rew_traj.ndim != 2:
         raise _native.PbgError(f"gae: rew_traj must be [T, n], got shape {tuple(rew_traj.shape)}")
@@ -42,19 +52,33 @@ def gae(rew_traj, done_traj, value, gamma: float = 0.99, lam: float = 0.95, adv=
         (lambda: torch.empty((T, n), dtype=torch.float32, device=rew_traj.device))
     adv = new() if adv is None else adv
     ret = new() if ret is None else ret
-    for name, t, shape, dt in (("rew_traj", rew_traj, (T, n), f32), ("done_traj", done_traj, (T, n), u8),
-                               ("value", value, (T + 1, n), f32), ("adv", adv, (T, n), f32), ("ret", ret, (T, n), f32)):
+    arrays = [("rew_traj", rew_traj, (T, n), f32), ("done_traj", done_traj, (T, n), u8), ("value", value, (T + 1, n), f32),
+              ("adv", adv, (T, n), f32), ("ret", ret, (T, n), f32)]
+    if trunc:
+        arrays += [("trunc_traj", trunc_traj, (T, n), u8), ("term_value", term_value, (T, n), f32)]
+    for name, t, shape, dt in arrays:
         ok = isinstance(t, np.ndarray) and t.flags.c_contiguous if host else \
             isinstance(t, torch.Tensor) and t.is_contiguous() and t.device == rew_traj.device and t.is_cuda
         if not ok or tuple(t.shape) != shape or t.dtype != dt or T < 1 or n < 1:
             raise _native.PbgError(f"gae: {name} must be a contiguous {dt} {'array' if host else 'GPU tensor'} of shape "
                                    f"{shape} (T, n >= 1), all on one device")
     if host:
+        if trunc:
+            _native.check(_native.lib().pbg_gae_trunc_host(T, n, rew_traj.ctypes.data, done_traj.ctypes.data,
+                                                           trunc_traj.ctypes.data, value.ctypes.data, term_value.ctypes.data,
+                                                           float(gamma), float(lam), adv.ctypes.data, ret.ctypes.data),
+                          "pbg_gae_trunc_host")
+            return adv, ret
         _native.check(_native.lib().pbg_gae_host(T, n, rew_traj.ctypes.data, done_traj.ctypes.data, value.ctypes.data,
                                                  float(gamma), float(lam), adv.ctypes.data, ret.ctypes.data), "pbg_gae_host")
         return adv, ret
     with torch.cuda.device(rew_traj.device):
         stream = ctypes.c_void_p(torch.cuda.current_stream(rew_traj.device).cuda_stream)
+        if trunc:
+            _native.check(_native.lib().pbg_gae_trunc(T, n, rew_traj.data_ptr(), done_traj.data_ptr(), trunc_traj.data_ptr(),
+                                                      value.data_ptr(), term_value.data_ptr(), float(gamma), float(lam),
+                                                      adv.data_ptr(), ret.data_ptr(), stream), "pbg_gae_trunc")
+            return adv, ret
         _native.check(_native.lib().pbg_gae(T, n, rew_traj.data_ptr(), done_traj.data_ptr(), value.data_ptr(), float(gamma),
                                             float(lam), adv.data_ptr(), ret.data_ptr(), stream), "pbg_gae")
     return adv, ret
@@ -558,6 +582,10 @@ class Batch:
     value: torch.Tensor     # [T + 1, n]
     adv: torch.Tensor
     ret: torch.Tensor
+    # truncation="bootstrap" sets these two on the batch; in terminal mode they are the class's None and no field, so
+    # that ``vars(batch)`` stays the nine tensors it was
+    trunc = None        # uint8 [T, n]: truncated and not terminated
+    term_value = None   # float32 [T, n]: the critic on the terminal observations, +0.0 where trunc is 0
 
 
 class PPO:
@@ -596,16 +624,26 @@ class PPO:
     graph baked are compared before each replay; a moved one raises ``PbgError``.
 
     ``grad_path="mfma"`` (needs ``backward="hip"``): the gradient object is ``PPOGrad(path="mfma")``, the matrix-core
-    path for networks wider than 64; it works with every optimizer, graph and permutation setting above."""
+    path for networks wider than 64; it works with every optimizer, graph and permutation setting above.
+
+    ``truncation="terminal"`` (the default): ``done`` includes the TimeLimit truncation and ``gae`` treats it as a
+    death.  ``truncation="bootstrap"``: the rollout also records ``trunc_traj`` and
+    ``term_obs_traj``, one more launch (``critic.act_where``) values the terminal observations of the truncated rows
+    under the normaliser the batch was collected under, and ``gae`` bootstraps them through the truncation; the
+    observation statistics do not see the terminal observations.  It works with every setting above, a captured
+    iteration included."""
 
     def __init__(self, env, hidden=(64, 64), steps: int = 64, seed: int = 0, gamma: float = 0.99, lam: float = 0.95,
                  clip: float = 0.2, lr: float = 3e-4, epochs: int = 4, minibatches: int = 4, vf_coef: float = 0.5,
                  ent_coef: float = 0.0, log_std: float = -0.5, max_grad_norm: float = 0.5, norm_adv: bool = True,
                  obs_norm: bool = False, obs_clip: float = 5.0, backward: str = "torch", optimizer: str = "torch",
                  graph=False, permutation: str = "torch", lr_schedule=None, schedule_iterations=None,
-                 grad_path: str = "fma"):
+                 grad_path: str = "fma", truncation: str = "terminal"):
         n, dev = env.num_envs, env.device
         nb = self._batch_envs(env)   # the envs whose rows make one update's batch: the env's own
+        if truncation not in ("terminal", "bootstrap"):
+            raise _native.PbgError(f"PPO: truncation must be 'terminal' or 'bootstrap', got {truncation!r}")
+        self.truncation = truncation
         if backward not in ("torch", "hip"):
             raise _native.PbgError(f"PPO: backward must be 'torch' or 'hip', got {backward!r}")
         if optimizer not in ("torch", "hip"):
@@ -671,6 +709,8 @@ class PPO:
         self._adv, self._ret = torch.zeros((T, n), **kw), torch.zeros((T, n), **kw)
         self._obs_all = torch.zeros(((T + 1) * n, obs_dim), **kw)
         self._std = torch.zeros(act_dim, **kw)
+        # truncation="bootstrap": the critic's values of the terminal observations, written whole by every act_where
+        self._term_value = torch.zeros((T, n), **kw) if truncation == "bootstrap" else None
         self.grad = None
         if backward == "hip":
             # the gradient tensors pbg_ppo_grad writes, bound once to the parameters' .grad
@@ -724,15 +764,25 @@ class PPO:
         self.noise.set_std(self._std)
         if self.obs_stats is not None:
             self.actor.attach_obs_stats(self.obs_stats)
-        res = env.rollout(self.actor, T, trajectory=True)
+        boot = self.truncation == "bootstrap"
+        res = env.rollout(self.actor, T, trajectory=True, truncation=boot)
         if self.obs_stats is not None:
             self.actor.attach_obs_stats(None)
         self._obs_all[:T * n].copy_(res.obs_traj.view(T * n, -1))
         self._obs_all[T * n:].copy_(env.obs)
         self.critic.act(self._obs_all, out=self._value.view((T + 1) * n, 1))
-        gae(res.rew_traj, res.done_traj, self._value, self.gamma, self.lam, adv=self._adv, ret=self._ret)
-        return Batch(obs=res.obs_traj, act=res.act_traj, rew=res.rew_traj, done=res.done_traj, eps2=res.eps2_traj,
-                     logp=res.logp_traj(self._std), value=self._value, adv=self._adv, ret=self._ret)
+        if boot:
+            # one launch more: the truncated rows' terminal observations through the critic, zeros elsewhere
+            self.critic.act_where(res.trunc_traj, res.term_obs_traj, out=self._term_value.view(T, n, 1))
+            gae(res.rew_traj, res.done_traj, self._value, self.gamma, self.lam, adv=self._adv, ret=self._ret,
+                trunc_traj=res.trunc_traj, term_value=self._term_value)
+        else:
+            gae(res.rew_traj, res.done_traj, self._value, self.gamma, self.lam, adv=self._adv, ret=self._ret)
+        b = Batch(obs=res.obs_traj, act=res.act_traj, rew=res.rew_traj, done=res.done_traj, eps2=res.eps2_traj,
+                  logp=res.logp_traj(self._std), value=self._value, adv=self._adv, ret=self._ret)
+        if boot:
+            b.trunc, b.term_value = res.trunc_traj, self._term_value
+        return b
 
     def update(self, b: Batch) -> dict:
         """``epochs`` passes of ``minibatches`` clipped-surrogate steps over the batch (Adam; the gradient by torch
@@ -900,7 +950,8 @@ class PPO:
         """The addresses an iteration's launches take that the trainer does not own alone: the env's observation and
         rollout buffers, and the normaliser's copies."""
         env, T = self.env, self.steps
-        io, traj = env._ro_io[(T, True)]
+        # truncation="bootstrap": its own key, whose trajectories include trunc_traj and term_obs_traj
+        io, traj = env._ro_io[(T, True, True) if self.truncation == "bootstrap" else (T, True)]
         ts = [env.obs] + list(env._ro_work.values()) + list(env._ro_acc.values()) + [traj[k] for k in sorted(traj)]
         norm = self.actor.obs_norm
         return tuple(t.data_ptr() for t in ts + ([] if norm is None else list(norm[:2]))) + \

@@ -53,6 +53,8 @@ class RolloutResult:
     rew_traj: torch.Tensor = None   # [steps, n] float32
     done_traj: torch.Tensor = None  # [steps, n] uint8
     eps2_traj: torch.Tensor = None  # [steps, n] float64: sum_j eps[e][j] ** 2 of each step's action noise
+    trunc_traj: torch.Tensor = None     # [steps, n] uint8: truncated by the TimeLimit and not terminated
+    term_obs_traj: torch.Tensor = None  # [steps, n, obs_dim]: the observation before the reset, where done_traj is set
 
     def logp_traj(self, std) -> torch.Tensor:
         """``[steps, n]`` float64 log-probability of each recorded action under the diagonal Gaussian it was
@@ -210,7 +212,8 @@ class VecEnv:
         return g
 
     # ---------------------------------------------------------------- closed loop
-    def rollout(self, policy, steps: int, trajectory: bool = False, fresh: bool = False) -> RolloutResult:
+    def rollout(self, policy, steps: int, trajectory: bool = False, fresh: bool = False,
+                truncation: bool = False) -> RolloutResult:
         """``steps`` closed-loop env steps of every env, ``env.step(policy.act(obs))`` (the loop of the
         reference's enjoy_TF_*.py scripts), entirely on the device: pbg_rollout, two kernel launches
         per step plus one per call, no host work in between.  ``policy``: an ``MLPPolicy`` on this
@@ -231,6 +234,15 @@ class VecEnv:
         from), ``act_traj``, ``rew_traj`` and ``done_traj``, ``[steps, n, ...]``.  With an ``ActionNoise``
         attached to the policy every action is ``mu + std * eps`` (what ``act_traj`` then records), and
         ``trajectory=True`` also records ``eps2_traj`` (``RolloutResult.logp_traj``).
+
+        ``truncation=True`` (needs ``trajectory=True`` and an env with ``autoreset=True``, ``PbgError`` otherwise)
+        also records what bootstrapping through a TimeLimit needs (pbg_rollout_io_t version 2): ``trunc_traj``
+        (uint8 ``[steps, n]``: truncated and not terminated) and ``term_obs_traj`` (float32 ``[steps, n, obs_dim]``:
+        the observation before the env's reset).  Row ``(t, e)`` of ``term_obs_traj`` is written only where
+        ``done_traj[t, e]`` is set; every other row keeps whatever it held and means nothing
+        (``MLPPopulation.act_where`` never reads it).  The buffer is ``steps * n * obs_dim * 4`` bytes, 59 MB for
+        Ant's 32 x 16,384, and is allocated only when asked for; its buffers have the key ``(steps, True, True)``,
+        calls without the argument keep theirs.
 
         All buffers are allocated once per ``(steps, trajectory)`` and reused, and the returned
         tensors are views of them (``clone()`` what must survive the next call), so after one
@@ -254,9 +266,13 @@ class VecEnv:
                                 done_episodes=torch.zeros(n, dtype=torch.int32, **kw))
             self._ro_work = dict(act=torch.zeros((n, info.action_dim), dtype=torch.float32, **kw),
                                  rew64=torch.zeros(n, dtype=torch.float64, **kw))
+        if truncation and (not trajectory or not self.autoreset):
+            raise _native.PbgError("rollout: truncation=True records next to the trajectories (trajectory=True) what an "
+                                   "auto-reset overwrites (an env with autoreset=True)")
         if fresh:
             self.reset_rollout()
-        key = (steps, bool(trajectory))
+        # calls without `truncation` keep their (steps, trajectory) key, buffers and first-version struct
+        key = (steps, True, True) if truncation else (steps, bool(trajectory))
         if key not in self._ro_io:
             traj = {}
             if trajectory:
@@ -264,8 +280,12 @@ class VecEnv:
                             act_traj=torch.zeros((steps, n, info.action_dim), dtype=torch.float32, **kw),
                             rew_traj=torch.zeros((steps, n), dtype=torch.float32, **kw),
                             done_traj=torch.zeros((steps, n), dtype=torch.uint8, **kw))
+            if truncation:
+                traj.update(trunc_traj=torch.zeros((steps, n), dtype=torch.uint8, **kw),
+                            term_obs_traj=torch.zeros((steps, n, info.obs_dim), dtype=torch.float32, **kw))
             bufs = dict(obs=self.obs, rew=self.reward, done=self.done, **self._ro_work, **self._ro_acc, **traj)
-            io = _native.RolloutIO(n_steps=steps, **{k: v.data_ptr() for k, v in bufs.items()})
+            IO = _native.RolloutIO2 if truncation else _native.RolloutIO
+            io = IO(n_steps=steps, **{k: v.data_ptr() for k, v in bufs.items()})
             self._ro_io[key] = (io, traj)
         io, traj = self._ro_io[key]
         io.autoreset = 1 if self.autoreset else 0
@@ -280,7 +300,8 @@ class VecEnv:
                                                               _stream(self.device)), policy._ROLLOUT)
         return RolloutResult(obs=self.obs, **self._ro_acc, obs_traj=traj.get("obs_traj"),
                              act_traj=traj.get("act_traj"), rew_traj=traj.get("rew_traj"),
-                             done_traj=traj.get("done_traj"), eps2_traj=eps2)
+                             done_traj=traj.get("done_traj"), eps2_traj=eps2, trunc_traj=traj.get("trunc_traj"),
+                             term_obs_traj=traj.get("term_obs_traj"))
 
     def reset_rollout(self):
         """Zero the rollout accumulators (stream-ordered, no allocation)."""

@@ -8,7 +8,7 @@ as an npz that tools/enjoy.py and MLPPolicy.from_npz load.
          [--ent-coef 0.0] [--vf-coef 0.5] [--seed 0] [--precision 64] [--hidden 64 64] [--out ppo_policy.npz]
          [--obs-norm] [--obs-clip 5.0] [--eval-envs 256] [--eval-steps 200] [--eval-every 1] [--curve curve.json]
          [--backward hip] [--optimizer hip] [--graph [iteration]] [--permutation device]
-         [--lr-schedule linear --schedule-iterations N] [--grad-path mfma] [--sharded]
+         [--lr-schedule linear --schedule-iterations N] [--grad-path mfma] [--truncation bootstrap] [--sharded]
 
 --obs-norm trains under running observation normalisation (PPO(obs_norm=True)) and saves the final normaliser
 in the npz (obs_mean, obs_inv_std, obs_clip); --curve writes the per-iteration evaluation as JSON.  --optimizer hip
@@ -18,7 +18,8 @@ the minibatch permutations on the device (pbg_perm_fill, a function of the seed 
 linear anneals the learning rate to zero over --schedule-iterations iterations from a device-side iteration count, and
 --graph iteration (needs --permutation device) replays a whole iteration, rollout included, as one captured graph.
 --grad-path mfma (with --backward hip) takes the gradient from the matrix-core path of pbg_ppo_grad, the one for hidden
-layers wider than 64.
+layers wider than 64.  --truncation bootstrap (PPO(truncation="bootstrap")) bootstraps the critic's value of the terminal
+observation through a TimeLimit truncation instead of treating it as a death; the default, terminal, is the trainer as it was.
 
 --sharded trains data-parallel (ppo.ShardedPPO: --envs is the global count; --backward, --optimizer and --permutation
 default to hip, hip and device, any other choice is refused by ShardedPPO, and it takes no --graph): one process per
@@ -81,6 +82,8 @@ def main():
     ap.add_argument("--schedule-iterations", type=int, default=None, help="iterations over which lr reaches zero")
     ap.add_argument("--grad-path", choices=("fma", "mfma"), default="fma",
                     help="the path of pbg_ppo_grad: vector FMA, or the matrix cores for wide networks (needs --backward hip)")
+    ap.add_argument("--truncation", choices=("terminal", "bootstrap"), default="terminal",
+                    help="a TimeLimit truncation in the advantages: a death, or bootstrapped through with V(terminal obs)")
     ap.add_argument("--curve", default=None, help="write the per-iteration evaluation here (JSON)")
     ap.add_argument("--sharded", action="store_true",
                     help="data-parallel over the ranks of RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT (ShardedPPO)")
@@ -124,26 +127,29 @@ def main():
               lr=args.lr, epochs=args.epochs, minibatches=args.minibatches, vf_coef=args.vf_coef, ent_coef=args.ent_coef,
               log_std=args.log_std, obs_norm=args.obs_norm, obs_clip=args.obs_clip, backward=args.backward,
               optimizer=args.optimizer, permutation=args.permutation, lr_schedule=args.lr_schedule,
-              schedule_iterations=args.schedule_iterations, grad_path=args.grad_path)
+              schedule_iterations=args.schedule_iterations, grad_path=args.grad_path, truncation=args.truncation)
     say(f"{args.env_id} (float{args.precision}): {args.envs} envs x {args.steps} steps per iteration, actor MLP "
           f"{ppo.actor_dims}, lr {args.lr}, {args.epochs} epochs x {args.minibatches} minibatches, observation "
           f"normalisation {'on' if args.obs_norm else 'off'}, backward pass {args.backward}, optimizer "
           f"{args.optimizer}{' (one graph per iteration)' if args.graph == 'iteration' else ' (one graph)' if args.graph else ''}, "
-          f"permutation {args.permutation}, lr schedule {args.lr_schedule}, gradient path {args.grad_path}" +
+          f"permutation {args.permutation}, lr schedule {args.lr_schedule}, gradient path {args.grad_path}, truncation "
+          f"{args.truncation}" +
         (f", {ppo.world} ranks" if args.sharded else ""))
     curve = []
+    stats = {}   # the last iterate()'s: the last minibatch's losses
 
     def report(it):
         ret, length = ppo.evaluate(test, args.eval_steps)
         curve.append(dict(iteration=it, return_mean=ret.mean().item(), return_min=ret.min().item(),
-                          length_mean=length.double().mean().item(), std_mean=ppo.log_std.data.exp().mean().item()))
+                          length_mean=length.double().mean().item(), std_mean=ppo.log_std.data.exp().mean().item(),
+                          vf_loss=float(stats["vf"]) if "vf" in stats else None))
         say(f"iteration {it:4d}: mean policy return mean {ret.mean().item():9.2f} min {ret.min().item():9.2f}  "
               f"first-episode length mean {length.double().mean().item():6.1f} of {args.eval_steps}  "
               f"action std {curve[-1]['std_mean']:.3f}", flush=True)
 
     report(0)
     for it in range(1, args.iterations + 1):
-        ppo.iterate()
+        stats = ppo.iterate()
         if it % args.eval_every == 0 or it == args.iterations:
             report(it)
     torch.cuda.synchronize()
