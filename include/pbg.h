@@ -933,6 +933,78 @@ int pbg_gae_trunc_host(int T, int n, const float* rew_traj, const uint8_t* done_
                        const float* value, const float* term_value, double gamma, double lambda, float* adv_out,
                        float* ret_out);
 
+/* ---- Return statistics: reward scaling by a running std of the discounted return (appended; nothing above changes) ----
+ * What VecNormalize does to rewards, on the device: every env keeps a running discounted return
+ * R <- gamma R + r, reset where the episode ends and carried from one rollout to the next; the rewards the critic
+ * regresses are divided by the standard deviation of every R seen so far (no mean is subtracted) and clipped.
+ *
+ * A pbg_ret_stats lives on one device (device >= 0), or on the host (device == -1: the host twin, the same entry
+ * points on HOST pointers, `stream` ignored, no HIP call, the same bits).  It owns
+ *   carry   float64 [n_envs]      the running return of every env, +0.0 at creation
+ *   slots   n_slots x (count int64, s1 float64, s2 float64): one per tile of 32 consecutive envs, the LAST walk's
+ *           partials; n_slots >= ceil(n_envs / 32)
+ *   totals  (count int64, s1, s2)  over every finalized batch so far, (0, +0.0, +0.0) at creation
+ *   scale   float32 [1]            1.0f at creation
+ * All float64 arithmetic below is IEEE add, multiply, divide and square root in the stated order, nothing contracted.
+ * No launch uses atomics or reads anything back; each is a function of its inputs and of the object's state alone, the
+ * same bits on every stream and inside a replayed graph, and because the state lives on the device a captured
+ * walk -> finalize -> apply replayed twice leaves what two eager rounds leave.
+ *
+ * pbg_ret_stats_walk: rew_traj float32 [T, n], done_traj uint8 [T, n], n <= n_envs.  One launch of ceil(n / 64)
+ * workgroups of 64 lanes, a lane per env e, t ascending from R = carry[e], (c, s1, s2) = (0, +0.0, +0.0):
+ *   R = gamma * R + (double)r[t][e]                     (the product rounded, then the add)
+ *   if isfinite(R):  c += 1;  s1 += R;  s2 += R * R     (the product rounded, then the add)
+ *   if !isfinite(R) or done[t][e] != 0:  R = +0.0
+ * then carry[e] = R.  A non-finite reward never reaches the sums and does not survive in the carry.  The 32 lanes of
+ * tile b (envs 32 b .. 32 b + 31; a lane past n holds (0, +0.0, +0.0)) are added by the tree x[l] += x[l + s] for
+ * every l < s, s = 16, 8, 4, 2, 1, and lane 0 OVERWRITES slot slot_offset + b.  Slots of no tile of this walk are left
+ * as they are.  PBG_E_ARG (before any HIP call) for a NULL pointer, T < 1, n < 1, n > n_envs, slot_offset < 0 or
+ * slot_offset + ceil(n / 32) > n_slots.
+ *
+ * pbg_ret_stats_finalize: one launch of one workgroup; one lane does, in this order,
+ *   b = (0, +0.0, +0.0);  for g = 0 .. n_used_slots - 1 ascending:  b += slots[g]     (per field)
+ *   totals += b                                                                          (per field)
+ *   if totals.count == 0: scale is left as it is.  Otherwise
+ *   m = s1 / count;  var = s2 / count - m * m  (the product rounded first);  var = var > var_floor ? var : var_floor
+ *   scale = (float)(1.0 / sqrt(var))
+ * with count converted to float64 once.  The slots are left as they are: a second finalize adds them a second time.
+ * PBG_E_ARG (before any HIP call) for a NULL object, n_used_slots outside 0 .. n_slots or a var_floor that is not > 0.
+ *
+ * pbg_ret_stats_apply: rew_out[i] = clamp(rew_in[i] * scale) for i < count: v = r * scale in float32 (one rounding),
+ * then v < -clip ? -clip : (v > clip ? clip : v), so a NaN passes.  One launch; float4 loads and stores where both
+ * pointers are 16-byte aligned (the last count % 4 elements one by one), element by element otherwise: the same bits.
+ * PBG_E_ARG (before any HIP call) for a NULL pointer, count < 1, a clip that is not > 0, or rew_out overlapping
+ * rew_in.
+ *
+ * Slots compose like pbg_obs_stats': equal shards of a multiple of 32 envs, each walked at slot_offset = its first
+ * global env / 32 (in any object with enough slots), their slots set into one object in shard order and finalized
+ * there, give the totals and the scale of the object that walked all envs at once, bit for bit. */
+typedef struct pbg_ret_stats pbg_ret_stats;
+
+/* PBG_E_ARG (before any HIP call) for n_envs < 1, n_slots < ceil(n_envs / 32), gamma outside [0, 1] (a NaN included),
+ * device < -1 or out NULL; PBG_E_HIP for a device that does not exist.  *out is NULL after every failure. */
+int pbg_ret_stats_create(int device, int n_envs, int n_slots, double gamma, pbg_ret_stats** out);
+void pbg_ret_stats_destroy(pbg_ret_stats* s);
+int pbg_ret_stats_walk(pbg_ret_stats* s, int T, int n, int slot_offset, const float* rew_traj, const uint8_t* done_traj,
+                       void* stream);
+int pbg_ret_stats_finalize(pbg_ret_stats* s, int n_used_slots, double var_floor, void* stream);
+int pbg_ret_stats_apply(const pbg_ret_stats* s, int count, float clip, const float* rew_in, float* rew_out, void* stream);
+/* carry, slots and totals to zero, scale to 1: one launch on `stream`. */
+int pbg_ret_stats_reset(pbg_ret_stats* s, void* stream);
+/* The state as arrays on the object's side (DEVICE arrays of its GPU; HOST arrays for device -1), each a launch on
+ * `stream` that copies the words as they are (two for slots and totals; none for count == 0).  Slots: `count` of them
+ * from `first`, counts int64 [count], sums float64 [count, 2] (s1, s2 per slot).  Totals: count int64 [1], sums
+ * float64 [2].  Carry: float64 [n_envs].  Scale: float32 [1].  PBG_E_ARG (before any HIP call) for a NULL pointer or a
+ * range outside the object's slots. */
+int pbg_ret_stats_get_slots(const pbg_ret_stats* s, int first, int count, int64_t* counts_out, double* sums_out, void* stream);
+int pbg_ret_stats_set_slots(pbg_ret_stats* s, int first, int count, const int64_t* counts, const double* sums, void* stream);
+int pbg_ret_stats_get_totals(const pbg_ret_stats* s, int64_t* count_out, double* sums_out, void* stream);
+int pbg_ret_stats_set_totals(pbg_ret_stats* s, const int64_t* count, const double* sums, void* stream);
+int pbg_ret_stats_get_carry(const pbg_ret_stats* s, double* carry_out, void* stream);
+int pbg_ret_stats_set_carry(pbg_ret_stats* s, const double* carry, void* stream);
+int pbg_ret_stats_get_scale(const pbg_ret_stats* s, float* scale_out, void* stream);
+int pbg_ret_stats_set_scale(pbg_ret_stats* s, const float* scale, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

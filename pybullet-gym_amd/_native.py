@@ -289,6 +289,25 @@ def lib():
         L.pbg_gae_trunc_host.argtypes = [I, I, P, P, P, P, P, D, D, P, P]
         for f in TRUNC_EXPORTED:
             getattr(L, f).restype = I
+    if hasattr(L, "pbg_ret_stats_create"):  # reward scaling by a running std of the discounted return
+        D, F = ctypes.c_double, ctypes.c_float
+        L.pbg_ret_stats_create.argtypes = [I, I, I, D, ctypes.POINTER(H)]
+        L.pbg_ret_stats_destroy.argtypes = [H]
+        L.pbg_ret_stats_destroy.restype = None
+        L.pbg_ret_stats_walk.argtypes = [H, I, I, I, P, P, P]
+        L.pbg_ret_stats_finalize.argtypes = [H, I, D, P]
+        L.pbg_ret_stats_apply.argtypes = [H, I, F, P, P, P]
+        L.pbg_ret_stats_reset.argtypes = [H, P]
+        L.pbg_ret_stats_get_slots.argtypes = [H, I, I, P, P, P]
+        L.pbg_ret_stats_set_slots.argtypes = [H, I, I, P, P, P]
+        L.pbg_ret_stats_get_totals.argtypes = [H, P, P, P]
+        L.pbg_ret_stats_set_totals.argtypes = [H, P, P, P]
+        for f in ("carry", "scale"):
+            getattr(L, f"pbg_ret_stats_get_{f}").argtypes = [H, P, P]
+            getattr(L, f"pbg_ret_stats_set_{f}").argtypes = [H, P, P]
+        for f in RET_STATS_EXPORTED:
+            if f != "pbg_ret_stats_destroy":
+                getattr(L, f).restype = I
     for f in ("pbg_info", "pbg_reset", "pbg_step", "pbg_step_ex", "pbg_get_state", "pbg_set_state",
               "pbg_pack_record_sizes", "pbg_pack", "pbg_create_debug", "pbg_sample_actions", "pbg_create_ex",
               "pbg_default_sim_params", "pbg_get_sim_params", "pbg_create_v2", "pbg_precision"):
@@ -318,13 +337,17 @@ PERM_EXPORTED = ("pbg_perm_create", "pbg_perm_destroy", "pbg_perm_fill", "pbg_pe
 PPO_PARTS_EXPORTED = ("pbg_ppo_grad_geometry", "pbg_ppo_grad_run_part", "pbg_ppo_grad_reduce", "pbg_obs_stats_get_slots",
                       "pbg_obs_stats_set_slots")
 TRUNC_EXPORTED = ("pbg_population_act_where", "pbg_gae_trunc", "pbg_gae_trunc_host")
+RET_STATS_EXPORTED = ("pbg_ret_stats_create", "pbg_ret_stats_destroy", "pbg_ret_stats_walk", "pbg_ret_stats_finalize",
+                      "pbg_ret_stats_apply", "pbg_ret_stats_reset", "pbg_ret_stats_get_slots", "pbg_ret_stats_set_slots",
+                      "pbg_ret_stats_get_totals", "pbg_ret_stats_set_totals", "pbg_ret_stats_get_carry",
+                      "pbg_ret_stats_set_carry", "pbg_ret_stats_get_scale", "pbg_ret_stats_set_scale")
 EXPORTED =("pbg_create", "pbg_create_debug", "pbg_create_ex", "pbg_create_v2", "pbg_precision",
             "pbg_default_sim_params", "pbg_get_sim_params",
             "pbg_destroy", "pbg_info", "pbg_reset", "pbg_step", "pbg_step_ex",
             "pbg_get_state", "pbg_set_state", "pbg_pack_record_sizes", "pbg_pack", "pbg_sample_actions",
             "pbg_debug_poison", "pbg_last_error") + POLICY_EXPORTED + POPULATION_EXPORTED + OBS_NORM_EXPORTED + \
     ACTION_NOISE_EXPORTED + PPO_GRAD_EXPORTED + PPO_OPT_EXPORTED + PERM_EXPORTED + PPO_GRAD_EX_EXPORTED + PPO_PARTS_EXPORTED + \
-    TRUNC_EXPORTED
+    TRUNC_EXPORTED + RET_STATS_EXPORTED
 
 
 def check(rc: int, what: str):

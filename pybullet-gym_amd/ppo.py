@@ -11,7 +11,9 @@ gradient"), and with ``optimizer="hip"`` the advantage normaliser, the gradient 
 the whole update as one captured graph.  The collection half of an iteration has no host work between its launches.
 ``Permutation`` (pbg_perm, include/pbg.h "Counter-based permutations") draws the minibatch permutations on the device,
 ``lr_linear`` (pbg_ppo_lr_linear) writes a scheduled learning rate that ``AdamClip.step`` reads from device memory, and
-with both an iteration can be one captured graph (``PPO(graph="iteration")``)."""
+with both an iteration can be one captured graph (``PPO(graph="iteration")``).  ``RetStats`` (pbg_ret_stats, include/pbg.h
+"Return statistics") keeps a running standard deviation of the discounted return on the device and scales the rewards
+``gae`` sees by it (``PPO(reward_norm=True)``): three launches more, inside the captured iteration too."""
 from __future__ import annotations
 
 import ctypes
@@ -570,6 +572,167 @@ def lr_linear(it, n_total: int, lr0: float, out=None):
     return out
 
 
+class RetStats:
+    """Reward scaling by a running standard deviation of the discounted return (include/pbg.h "Return statistics",
+    pbg_ret_stats), what VecNormalize does to rewards.  ``n_envs`` envs each keep a running return
+    ``R <- gamma R + r``, reset where ``done`` is set and carried from one ``update`` to the next; ``finalize`` folds the
+    walk's per-tile partials (one slot per 32 consecutive envs) into the running totals and sets ``scale = 1 /
+    sqrt(max(var, var_floor))``; ``apply`` multiplies rewards by it and clips.  ``device``: a GPU, whose object owns all
+    of that on the device (three launches, no atomics, nothing read back: a captured round that is replayed advances
+    like an eager one), or ``None`` / ``"cpu"`` for the host twin (the same entry points on numpy arrays, no GPU, the
+    same bits).  ``n_slots``: default ``ceil(n_envs / 32)``; more when the object also finalizes other shards' slots."""
+
+    TILE = 32
+
+    def __init__(self, n_envs: int, gamma: float, device=None, n_slots=None):
+        if not hasattr(_native.lib(), "pbg_ret_stats_create"):
+            raise _native.PbgError(f"{_native.LIB_PATH} has no pbg_ret_stats_create: a build without return statistics")
+        self.n_envs, self.gamma = int(n_envs), float(gamma)
+        self.n_slots = -(-self.n_envs // self.TILE) if n_slots is None else int(n_slots)
+        self.host = device is None or str(device) == "cpu"
+        self.device = None if self.host else torch.device(device)
+        self._h = ctypes.c_void_p()
+        index = -1
+        if not self.host:
+            if self.device.type != "cuda":
+                raise _native.PbgError(f"RetStats: device must be a GPU or None, got {device!r}")
+            index = self.device.index if self.device.index is not None else torch.cuda.current_device()
+            self.device = torch.device("cuda", index)
+        _native.check(_native.lib().pbg_ret_stats_create(index, self.n_envs, self.n_slots, self.gamma, ctypes.byref(self._h)),
+                      "pbg_ret_stats_create")
+
+    def _open(self, what):
+        if not self._h:
+            raise _native.PbgError(f"RetStats.{what}: the object is closed")
+        return self._h
+
+    def _call(self, name, *args):
+        """``pbg_ret_stats_<name>(handle, *args, stream)`` on the current stream of the object's GPU."""
+        h, f = self._open(name), getattr(_native.lib(), "pbg_ret_stats_" + name)
+        if self.host:
+            _native.check(f(h, *args, None), "pbg_ret_stats_" + name)
+            return
+        with torch.cuda.device(self.device):
+            stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            _native.check(f(h, *args, stream), "pbg_ret_stats_" + name)
+
+    def _ptr(self, t, what, name, shape, dt):
+        """The pointer of ``t``, which must already be a contiguous array (host) or tensor on the object's GPU of
+        ``shape`` and of the numpy dtype ``dt``: nothing is converted silently."""
+        if self.host:
+            ok = isinstance(t, np.ndarray) and t.flags.c_contiguous and t.dtype == dt
+        else:
+            ok = isinstance(t, torch.Tensor) and t.is_contiguous() and t.device == self.device and \
+                t.dtype == getattr(torch, np.dtype(dt).name)
+        if not ok or tuple(t.shape) != tuple(shape):
+            raise _native.PbgError(f"RetStats.{what}: {name} must be a contiguous {np.dtype(dt).name} "
+                                   f"{'array' if self.host else f'tensor on {self.device}'} of shape {tuple(shape)}")
+        return t.ctypes.data if self.host else t.data_ptr()
+
+    def _new(self, shape, dt):
+        return np.empty(shape, dt) if self.host else torch.empty(shape, dtype=getattr(torch, np.dtype(dt).name), device=self.device)
+
+    def update(self, rew_traj, done_traj, slot_offset: int = 0):
+        """Walk ``rew_traj`` (float32 ``[T, n]``) and ``done_traj`` (uint8 ``[T, n]``), ``n <= n_envs``: every env's
+        return advances ``T`` steps from its carry, and the tiles' partials overwrite the slots ``slot_offset ..``."""
+        if getattr(rew_traj, "ndim", 0) != 2:
+            raise _native.PbgError("RetStats.update: rew_traj must be [T, n]")
+        T, n = (int(d) for d in rew_traj.shape)
+        self._call("walk", T, n, int(slot_offset), self._ptr(rew_traj, "update", "rew_traj", (T, n), np.float32),
+                   self._ptr(done_traj, "update", "done_traj", (T, n), np.uint8))
+
+    def finalize(self, n_used_slots=None, var_floor: float = 1e-2):
+        """Add the slots ``0 .. n_used_slots - 1`` (default: all) in ascending order, then that sum onto the totals, and
+        set the scale from them (left as it is while the totals are empty)."""
+        self._call("finalize", self.n_slots if n_used_slots is None else int(n_used_slots), float(var_floor))
+
+    def apply(self, rew, out=None, clip: float = 10.0):
+        """``out = clamp(rew * scale, -clip, clip)`` (float32, any shape, contiguous; a NaN passes); ``out`` may not
+        overlap ``rew``."""
+        shape = tuple(getattr(rew, "shape", ()))
+        count = int(np.prod(shape)) if shape else 0
+        if out is None:
+            out = self._new(shape, np.float32)
+        self._call("apply", count, float(clip), self._ptr(rew, "apply", "rew", shape, np.float32),
+                   self._ptr(out, "apply", "out", shape, np.float32))
+        return out
+
+    def _slot_range(self, what, first, count):
+        first, count = int(first), int(count)
+        if first < 0 or count < 0 or first + count > self.n_slots:
+            raise _native.PbgError(f"RetStats.{what}: slots {first} .. {first} + {count} are outside the object's 0 .. "
+                                   f"{self.n_slots}")
+        return first, count
+
+    def get_slots(self, first: int = 0, count=None):
+        """``(counts int64 [count], sums float64 [count, 2])`` of the slots ``first .. first + count - 1`` (default: to
+        the last), per slot ``s1, s2``: fresh arrays; the slots stay as they are."""
+        first, count = self._slot_range("get_slots", first, self.n_slots - int(first) if count is None else count)
+        counts, sums = self._new(count, np.int64), self._new((count, 2), np.float64)
+        self._call("get_slots", first, count, self._ptr(counts, "get_slots", "counts", (count,), np.int64),
+                   self._ptr(sums, "get_slots", "sums", (count, 2), np.float64))
+        return counts, sums
+
+    def set_slots(self, first: int, counts, sums):
+        """Overwrite the slots ``first .. first + len(counts) - 1`` (``get_slots``' layout).  Slots gathered from equal
+        shards of a multiple of 32 envs in shard order and finalized here give the unsharded object's bits."""
+        first, count = self._slot_range("set_slots", first, counts.shape[0] if getattr(counts, "ndim", 0) == 1 else -1)
+        self._call("set_slots", first, count, self._ptr(counts, "set_slots", "counts", (count,), np.int64),
+                   self._ptr(sums, "set_slots", "sums", (count, 2), np.float64))
+        self._src = (counts, sums)   # alive until the stream has copied them
+
+    def _get(self, name, *shapes_dts):
+        outs = [self._new(s, d) for s, d in shapes_dts]
+        self._call("get_" + name, *(self._ptr(o, name, name, s, d) for o, (s, d) in zip(outs, shapes_dts)))
+        return outs
+
+    @property
+    def totals(self):
+        """``(count int64 [1], sums float64 [2])`` over every finalized batch: fresh arrays (device tensors on a GPU)."""
+        return tuple(self._get("totals", ((1,), np.int64), ((2,), np.float64)))
+
+    @property
+    def carry(self):
+        """float64 ``[n_envs]``: every env's running return (a fresh array)."""
+        return self._get("carry", ((self.n_envs,), np.float64))[0]
+
+    @property
+    def scale(self):
+        """float32 ``[1]``: what ``apply`` multiplies by (a fresh array; a device tensor on a GPU, nothing is read back)."""
+        return self._get("scale", ((1,), np.float32))[0]
+
+    def reset(self):
+        """Carry, slots and totals to zero, the scale to 1."""
+        self._call("reset")
+
+    def state(self) -> dict:
+        """Everything a checkpoint needs, as fresh arrays: ``count``, ``sums``, ``carry``, ``scale`` (the slots are one
+        walk's scratch)."""
+        count, sums = self.totals
+        return dict(count=count, sums=sums, carry=self.carry, scale=self.scale)
+
+    def load_state(self, state: dict):
+        """``state()``'s dict back into the object (arrays on its side, of ``state()``'s shapes and dtypes)."""
+        shapes = dict(count=((1,), np.int64), sums=((2,), np.float64), carry=((self.n_envs,), np.float64),
+                      scale=((1,), np.float32))
+        p = {k: self._ptr(state[k], "load_state", k, *shapes[k]) for k in shapes}
+        self._call("set_totals", p["count"], p["sums"])
+        self._call("set_carry", p["carry"])
+        self._call("set_scale", p["scale"])
+        self._src = dict(state)   # alive until the stream has copied them
+
+    def close(self):
+        if self._h:
+            _native.lib().pbg_ret_stats_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 @dataclass
 class Batch:
     """One iteration's data (views of the env's rollout buffers and this object's own): ``[T, n, ...]``."""
@@ -586,6 +749,8 @@ class Batch:
     # that ``vars(batch)`` stays the nine tensors it was
     trunc = None        # uint8 [T, n]: truncated and not terminated
     term_value = None   # float32 [T, n]: the critic on the terminal observations, +0.0 where trunc is 0
+    # reward_norm=True sets this one the same way; ``rew`` stays the raw rewards
+    rew_scaled = None   # float32 [T, n]: the rewards ``adv`` and ``ret`` were computed from
 
 
 class PPO:
@@ -631,6 +796,14 @@ class PPO:
     ``term_obs_traj``, one more launch (``critic.act_where``) values the terminal observations of the truncated rows
     under the normaliser the batch was collected under, and ``gae`` bootstraps them through the truncation; the
     observation statistics do not see the terminal observations.  It works with every setting above, a captured
+    iteration included.
+
+    ``reward_norm=True``: the rewards ``gae`` sees are the rollout's divided by a running
+    standard deviation of the discounted return and clipped to ``+-reward_clip``: ``collect`` runs ``RetStats.update ->
+    finalize -> apply`` (three launches) on the rollout's ``rew_traj`` / ``done_traj`` into a buffer of its own, so the
+    batch of iteration i is scaled by the statistics of iterations 0 .. i.  ``Batch.rew`` and ``evaluate()`` stay in the
+    robot's units, ``Batch.rew_scaled`` is what the advantages were computed from, and the value loss is then in scaled
+    units.  ``iterate()``'s stats gain ``rew_scale`` (a device tensor).  It works with every setting above, a captured
     iteration included."""
 
     def __init__(self, env, hidden=(64, 64), steps: int = 64, seed: int = 0, gamma: float = 0.99, lam: float = 0.95,
@@ -638,7 +811,8 @@ class PPO:
                  ent_coef: float = 0.0, log_std: float = -0.5, max_grad_norm: float = 0.5, norm_adv: bool = True,
                  obs_norm: bool = False, obs_clip: float = 5.0, backward: str = "torch", optimizer: str = "torch",
                  graph=False, permutation: str = "torch", lr_schedule=None, schedule_iterations=None,
-                 grad_path: str = "fma", truncation: str = "terminal"):
+                 grad_path: str = "fma", truncation: str = "terminal", reward_norm: bool = False,
+                 reward_clip: float = 10.0):
         n, dev = env.num_envs, env.device
         nb = self._batch_envs(env)   # the envs whose rows make one update's batch: the env's own
         if truncation not in ("terminal", "bootstrap"):
@@ -711,6 +885,13 @@ class PPO:
         self._std = torch.zeros(act_dim, **kw)
         # truncation="bootstrap": the critic's values of the terminal observations, written whole by every act_where
         self._term_value = torch.zeros((T, n), **kw) if truncation == "bootstrap" else None
+        self.ret_stats, self.reward_clip = None, float(reward_clip)
+        if reward_norm:
+            if not self.reward_clip > 0.0:
+                raise _native.PbgError(f"PPO: reward_clip must be > 0, got {reward_clip!r}")
+            self.ret_stats = self._make_ret_stats(n, dev)
+            # what gae reads in place of the rollout's rew_traj, written whole by every apply
+            self._rew_scaled = torch.zeros((T, n), **kw)
         self.grad = None
         if backward == "hip":
             # the gradient tensors pbg_ppo_grad writes, bound once to the parameters' .grad
@@ -748,6 +929,15 @@ class PPO:
     def _batch_envs(self, env) -> int:
         return env.num_envs
 
+    def _make_ret_stats(self, n, dev):
+        return RetStats(n, self.gamma, dev)
+
+    def _scale_rewards(self, rew_traj, done_traj):
+        """``reward_norm``'s three launches: the returns' walk, the totals and the scale, the scaled rewards."""
+        self.ret_stats.update(rew_traj, done_traj)
+        self.ret_stats.finalize()
+        return self.ret_stats.apply(rew_traj, out=self._rew_scaled, clip=self.reward_clip)
+
     def _set_norm(self):
         mean, inv_std = self.obs_stats.finalize()
         self.actor.set_obs_norm(mean, inv_std, clip=self.obs_clip)
@@ -771,17 +961,20 @@ class PPO:
         self._obs_all[:T * n].copy_(res.obs_traj.view(T * n, -1))
         self._obs_all[T * n:].copy_(env.obs)
         self.critic.act(self._obs_all, out=self._value.view((T + 1) * n, 1))
+        rew = res.rew_traj if self.ret_stats is None else self._scale_rewards(res.rew_traj, res.done_traj)
         if boot:
             # one launch more: the truncated rows' terminal observations through the critic, zeros elsewhere
             self.critic.act_where(res.trunc_traj, res.term_obs_traj, out=self._term_value.view(T, n, 1))
-            gae(res.rew_traj, res.done_traj, self._value, self.gamma, self.lam, adv=self._adv, ret=self._ret,
+            gae(rew, res.done_traj, self._value, self.gamma, self.lam, adv=self._adv, ret=self._ret,
                 trunc_traj=res.trunc_traj, term_value=self._term_value)
         else:
-            gae(res.rew_traj, res.done_traj, self._value, self.gamma, self.lam, adv=self._adv, ret=self._ret)
+            gae(rew, res.done_traj, self._value, self.gamma, self.lam, adv=self._adv, ret=self._ret)
         b = Batch(obs=res.obs_traj, act=res.act_traj, rew=res.rew_traj, done=res.done_traj, eps2=res.eps2_traj,
                   logp=res.logp_traj(self._std), value=self._value, adv=self._adv, ret=self._ret)
         if boot:
             b.trunc, b.term_value = res.trunc_traj, self._term_value
+        if self.ret_stats is not None:
+            b.rew_scaled = rew
         return b
 
     def update(self, b: Batch) -> dict:
@@ -958,6 +1151,12 @@ class PPO:
             (None if norm is None else norm[2],)
 
     def iterate(self) -> dict:
+        stats = self._iterate()
+        if self.ret_stats is not None:
+            stats["rew_scale"] = self.ret_stats.scale   # a copy on the stream, after the iteration (or its replay)
+        return stats
+
+    def _iterate(self) -> dict:
         if not self.graph_iteration:
             stats = self._iterate_once()
             self.iteration += 1
@@ -1002,7 +1201,7 @@ class PPO:
     def close(self):
         self.actor.attach_action_noise(None)
         self._graph = self._iter_graph = None
-        for o in (self.actor, self.critic, self.noise, self.obs_stats, self.grad, self.adam, self.perm):
+        for o in (self.actor, self.critic, self.noise, self.obs_stats, self.grad, self.adam, self.perm, self.ret_stats):
             if o is not None:
                 o.close()
 
@@ -1032,9 +1231,11 @@ class ShardedPPO(PPO):
     partials and the float64 stats, and runs the unchanged reduction and ``AdamClip.step`` on them.  With
     ``obs_norm=True`` the ranks' statistics slots are gathered in rank order into every rank's object before
     ``finalize``.  Needs ``backward="hip"``, ``optimizer="hip"``, ``permutation="device"`` and ``graph=False`` (the
-    defaults here), equal shards of an even number of envs (a multiple of 32 with ``obs_norm``).  With no process
-    group initialised it runs as world 1: every workgroup as one part, no collective.  Under gloo the collectives
-    are staged through the host."""
+    defaults here), equal shards of an even number of envs (a multiple of 32 with ``obs_norm`` or ``reward_norm``).
+    With ``reward_norm=True`` each rank walks its shard's returns at the slots of its global envs, the ranks' slots are
+    gathered in rank order before ``finalize``, and every rank holds the one-process trainer's totals and scale.
+    With no process group initialised it runs as world 1: every workgroup as one part, no collective.  Under gloo the
+    collectives are staged through the host."""
 
     _REQUIRED = dict(backward="hip", optimizer="hip", permutation="device", graph=False)
 
@@ -1062,6 +1263,9 @@ class ShardedPPO(PPO):
         if ppo_kwargs.get("obs_norm", False) and n_rank % 32 != 0:
             raise _native.PbgError(f"ShardedPPO: obs_norm needs the {n_rank} envs per rank to be a multiple of 32, so that every "
                                    "rank's statistics tiles are tiles of the global trainer")
+        if ppo_kwargs.get("reward_norm", False) and n_rank % 32 != 0:
+            raise _native.PbgError(f"ShardedPPO: reward_norm needs the {n_rank} envs per rank to be a multiple of 32, so that "
+                                   "every rank's return-statistics tiles are tiles of the global trainer")
         self._shard_range = shard_range
         super().__init__(sharded_env.env, **ppo_kwargs)
         dev, T = self.env.device, self.steps
@@ -1085,6 +1289,21 @@ class ShardedPPO(PPO):
 
     def _batch_envs(self, env) -> int:
         return self.num_global
+
+    def _make_ret_stats(self, n, dev):
+        return RetStats(n, self.gamma, dev, n_slots=self.num_global // RetStats.TILE)
+
+    def _scale_rewards(self, rew_traj, done_traj):
+        """``PPO._scale_rewards`` over the global envs: this rank's tiles at their global slots, one all-gather of the
+        ranks' slots (8-byte words, bits kept), then the finalize over all of them."""
+        rs, k = self.ret_stats, self.env.num_envs // RetStats.TILE
+        rs.update(rew_traj, done_traj, slot_offset=self.rank * k)
+        if self.world > 1:
+            counts, sums = rs.get_slots(self.rank * k, k)
+            got = self._all_gather(torch.cat((counts.view(k, 1), sums.view(torch.int64)), dim=1)).view(self.world * k, 3)
+            rs.set_slots(0, got[:, 0].contiguous(), got[:, 1:].contiguous().view(torch.float64))
+        rs.finalize()
+        return rs.apply(rew_traj, out=self._rew_scaled, clip=self.reward_clip)
 
     def _all_gather(self, send):
         from .distributed import all_gather_blocks

@@ -9,6 +9,7 @@ as an npz that tools/enjoy.py and MLPPolicy.from_npz load.
          [--obs-norm] [--obs-clip 5.0] [--eval-envs 256] [--eval-steps 200] [--eval-every 1] [--curve curve.json]
          [--backward hip] [--optimizer hip] [--graph [iteration]] [--permutation device]
          [--lr-schedule linear --schedule-iterations N] [--grad-path mfma] [--truncation bootstrap] [--sharded]
+         [--reward-norm] [--reward-clip 10.0]
 
 --obs-norm trains under running observation normalisation (PPO(obs_norm=True)) and saves the final normaliser
 in the npz (obs_mean, obs_inv_std, obs_clip); --curve writes the per-iteration evaluation as JSON.  --optimizer hip
@@ -20,6 +21,9 @@ linear anneals the learning rate to zero over --schedule-iterations iterations f
 --grad-path mfma (with --backward hip) takes the gradient from the matrix-core path of pbg_ppo_grad, the one for hidden
 layers wider than 64.  --truncation bootstrap (PPO(truncation="bootstrap")) bootstraps the critic's value of the terminal
 observation through a TimeLimit truncation instead of treating it as a death; the default, terminal, is the trainer as it was.
+--reward-norm (PPO(reward_norm=True)) divides the rewards the critic regresses by a running standard deviation of the
+discounted return (ppo.RetStats, pbg_ret_stats) and clips them to +-reward-clip; the printed returns stay in the robot's
+units, the curve's vf_loss is then in scaled units and gains rew_scale.
 
 --sharded trains data-parallel (ppo.ShardedPPO: --envs is the global count; --backward, --optimizer and --permutation
 default to hip, hip and device, any other choice is refused by ShardedPPO, and it takes no --graph): one process per
@@ -84,6 +88,9 @@ def main():
                     help="the path of pbg_ppo_grad: vector FMA, or the matrix cores for wide networks (needs --backward hip)")
     ap.add_argument("--truncation", choices=("terminal", "bootstrap"), default="terminal",
                     help="a TimeLimit truncation in the advantages: a death, or bootstrapped through with V(terminal obs)")
+    ap.add_argument("--reward-norm", action="store_true",
+                    help="scale the rewards by a running std of the discounted return (pbg_ret_stats)")
+    ap.add_argument("--reward-clip", type=float, default=10.0, help="the scaled rewards' clip")
     ap.add_argument("--curve", default=None, help="write the per-iteration evaluation here (JSON)")
     ap.add_argument("--sharded", action="store_true",
                     help="data-parallel over the ranks of RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT (ShardedPPO)")
@@ -127,13 +134,14 @@ def main():
               lr=args.lr, epochs=args.epochs, minibatches=args.minibatches, vf_coef=args.vf_coef, ent_coef=args.ent_coef,
               log_std=args.log_std, obs_norm=args.obs_norm, obs_clip=args.obs_clip, backward=args.backward,
               optimizer=args.optimizer, permutation=args.permutation, lr_schedule=args.lr_schedule,
-              schedule_iterations=args.schedule_iterations, grad_path=args.grad_path, truncation=args.truncation)
+              schedule_iterations=args.schedule_iterations, grad_path=args.grad_path, truncation=args.truncation,
+              reward_norm=args.reward_norm, reward_clip=args.reward_clip)
     say(f"{args.env_id} (float{args.precision}): {args.envs} envs x {args.steps} steps per iteration, actor MLP "
           f"{ppo.actor_dims}, lr {args.lr}, {args.epochs} epochs x {args.minibatches} minibatches, observation "
           f"normalisation {'on' if args.obs_norm else 'off'}, backward pass {args.backward}, optimizer "
           f"{args.optimizer}{' (one graph per iteration)' if args.graph == 'iteration' else ' (one graph)' if args.graph else ''}, "
           f"permutation {args.permutation}, lr schedule {args.lr_schedule}, gradient path {args.grad_path}, truncation "
-          f"{args.truncation}" +
+          f"{args.truncation}, reward normalisation {'on' if args.reward_norm else 'off'}" +
         (f", {ppo.world} ranks" if args.sharded else ""))
     curve = []
     stats = {}   # the last iterate()'s: the last minibatch's losses
@@ -142,7 +150,9 @@ def main():
         ret, length = ppo.evaluate(test, args.eval_steps)
         curve.append(dict(iteration=it, return_mean=ret.mean().item(), return_min=ret.min().item(),
                           length_mean=length.double().mean().item(), std_mean=ppo.log_std.data.exp().mean().item(),
-                          vf_loss=float(stats["vf"]) if "vf" in stats else None))
+                          vf_loss=float(stats["vf"]) if "vf" in stats else None,
+                          grad_norm=float(stats["grad_norm"]) if "grad_norm" in stats else None,
+                          rew_scale=float(stats["rew_scale"]) if "rew_scale" in stats else None))
         say(f"iteration {it:4d}: mean policy return mean {ret.mean().item():9.2f} min {ret.min().item():9.2f}  "
               f"first-episode length mean {length.double().mean().item():6.1f} of {args.eval_steps}  "
               f"action std {curve[-1]['std_mean']:.3f}", flush=True)
