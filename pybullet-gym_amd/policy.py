@@ -24,17 +24,78 @@ def _need(name):
     return getattr(_native.lib(), name)
 
 
+def check_array(t, who, name, shape, dt, device):
+    """The one check of an array whose pointer goes to the library as it is, and that pointer: ``t`` must already
+    be a C-contiguous numpy array (``device`` None: the host) or a contiguous tensor on the GPU ``device``, of
+    ``shape`` and of the numpy dtype ``dt``, so nothing is converted (or written past) silently.  ``who`` is the
+    ``function`` the message starts with, or ``(object, method)`` for ``Class.method`` (put together only when the
+    check fails: this runs for every pointer of every launch); ``name`` is the argument's."""
+    shape = tuple(shape)
+    if device is None:
+        ok = isinstance(t, np.ndarray) and t.flags.c_contiguous and t.dtype == dt
+    else:
+        import torch
+        ok = isinstance(t, torch.Tensor) and t.is_cuda and t.device == device and t.is_contiguous() and \
+            t.dtype == (_TORCH_DTYPES.get(dt) or _torch_dtype(dt))
+    if not ok or tuple(t.shape) != shape:
+        who = who if isinstance(who, str) else f"{type(who[0]).__name__}.{who[1]}"
+        raise _native.PbgError(f"{who}: {name} must be a contiguous {np.dtype(dt).name} "
+                               f"{'array' if device is None else f'tensor on the GPU {device}'} of shape {shape}")
+    return t.ctypes.data if device is None else t.data_ptr()
+
+
+_TORCH_DTYPES = {}
+
+
+def _torch_dtype(dt):
+    """The torch dtype of the numpy dtype ``dt``, looked up once."""
+    if dt not in _TORCH_DTYPES:
+        import torch
+        _TORCH_DTYPES[dt] = getattr(torch, np.dtype(dt).name)
+    return _TORCH_DTYPES[dt]
+
+
+def new_array(shape, dt, device):
+    """An uninitialised array that passes ``check_array(..., shape, dt, device)``."""
+    if device is None:
+        return np.empty(shape, dt)
+    import torch
+    return torch.empty(shape, dtype=_torch_dtype(dt), device=device)
+
+
+def launch(device, fname, *args):
+    """The library's ``fname(*args, stream)`` on the current stream of the GPU ``device``, checked; ``device`` None:
+    ``fname(*args)``, a host entry point that takes no stream."""
+    f = getattr(_native.lib(), fname)
+    if device is None:
+        _native.check(f(*args), fname)
+        return
+    import torch
+    with torch.cuda.device(device):
+        _native.check(f(*args, torch.cuda.current_stream(device).cuda_stream), fname)
+
+
 class _NativeObject:
     """What the wrappers of a native object share: the handle ``_h`` and its destroy function, the guard
-    against use after ``close``, the device as ``cuda:<index>``, the current stream, and the check of a tensor
-    whose pointer goes to the library as it is."""
-    _DESTROY = None    # the library's destroy function
-    _NOUN = "object"   # what the closed guard calls the object
+    against use after ``close``, the device as ``cuda:<index>`` (``None``: a host object, ``host`` is then true),
+    the current stream, and the check (``_ptr``) and the allocator (``_new``) of an array whose pointer goes to
+    the library as it is: a tensor on the object's GPU, a numpy array on the host.  A class whose host twin
+    keeps its state in Python and owns no native object says so with ``_HOST_HANDLE = False``: the guard lets
+    that twin through, and its ``close`` has nothing to destroy."""
+    _DESTROY = None       # the library's destroy function
+    _NOUN = "object"      # what the closed guard calls the object
+    _HOST_HANDLE = True   # a host object owns a native object too
     _h = None
-    device = None      # torch.device("cuda", index); None: a host object
+    device = None         # torch.device("cuda", index); None: a host object
 
-    def _set_device(self, device, rule="a GPU") -> int:
-        """Store ``device`` as ``torch.device("cuda", index)`` and return the index."""
+    host = property(lambda self: self.device is None, doc="No GPU: numpy arrays in and out.")
+
+    def _set_device(self, device, rule="a GPU", host=False) -> int:
+        """Store ``device`` as ``torch.device("cuda", index)`` and return the index; with ``host``, ``None`` or
+        ``"cpu"`` is the host: ``device`` None, index -1."""
+        if host and (device is None or str(device) == "cpu"):
+            self.device = None
+            return -1
         import torch
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -56,7 +117,7 @@ class _NativeObject:
             pass
 
     def _open(self, what):
-        if not self._h:
+        if not self._h and (self._HOST_HANDLE or self.device is not None):
             raise _native.PbgError(f"{type(self).__name__}.{what}: the {self._NOUN} is closed")
         return self._h
 
@@ -64,16 +125,22 @@ class _NativeObject:
         import torch
         return torch.cuda.current_stream(self.device).cuda_stream
 
-    def _vec(self, t, what, name, shape, dtype=None):
-        """``t`` must already be a contiguous tensor of ``shape`` and ``dtype`` on the device: the native
-        call takes its pointer as is, so nothing is converted (or written past) silently."""
-        import torch
-        dtype = torch.float32 if dtype is None else dtype
-        if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.device != self.device or \
-                not t.is_contiguous() or tuple(t.shape) != tuple(shape):
-            raise _native.PbgError(f"{type(self).__name__}.{what}: {name} must be a contiguous {dtype} tensor of shape "
-                                   f"{tuple(shape)} on {self.device}")
+    def _launch(self, fname, *args):
+        """``launch`` on the object's side: ``fname(*args, stream)`` on its GPU, ``fname(*args)`` on the host."""
+        launch(self.device, fname, *args)
+
+    def _ptr(self, t, what, name, shape, dt=np.float32):
+        """``check_array`` on the object's side: the pointer of ``t``, a contiguous tensor on the object's GPU
+        (an array on the host) of ``shape`` and of the numpy dtype ``dt``."""
+        return check_array(t, (self, what), name, shape, dt, self.device)
+
+    def _vec(self, t, what, name, shape, dt=np.float32):
+        """``_ptr`` for a caller that goes on with the array: ``t`` itself, checked."""
+        self._ptr(t, what, name, shape, dt)
         return t
+
+    def _new(self, shape, dt=np.float32):
+        return new_array(shape, dt, self.device)
 
 
 class ObsStats(_NativeObject):
@@ -113,7 +180,7 @@ class ObsStats(_NativeObject):
         n = obs.shape[0] if isinstance(obs, torch.Tensor) and obs.dim() == 2 else -1
         self._vec(obs, "update", "obs", (n, self.obs_dim))
         if active is not None:
-            self._vec(active, "update", "active", (n,), torch.uint8)
+            self._vec(active, "update", "active", (n,), np.uint8)
         _native.check(_native.lib().pbg_obs_stats_update(s, n, self.group or 0, obs.data_ptr(),
                                                          None if active is None else active.data_ptr(), self._stream()),
                       "pbg_obs_stats_update")
@@ -155,8 +222,8 @@ class ObsStats(_NativeObject):
         count = counts.shape[0] if isinstance(counts, torch.Tensor) and counts.dim() == 1 else -1
         first, count = self._slot_range("set_slots", first, count)
         s = self._open("set_slots")
-        self._vec(counts, "set_slots", "counts", (count,), torch.int64)
-        self._vec(sums, "set_slots", "sums", (count, 2 * self.obs_dim), torch.float64)
+        self._vec(counts, "set_slots", "counts", (count,), np.int64)
+        self._vec(sums, "set_slots", "sums", (count, 2 * self.obs_dim), np.float64)
         _native.check(_need("pbg_obs_stats_set_slots")(s, first, count, counts.data_ptr(), sums.data_ptr(), self._stream()),
                       "pbg_obs_stats_set_slots")
 
@@ -232,7 +299,7 @@ class ActionNoise(_NativeObject):
         z = self._open("bind_eps2_traj")
         if eps2_traj is not None:
             shape = tuple(eps2_traj.shape) if isinstance(eps2_traj, torch.Tensor) and eps2_traj.dim() == 2 else (-1, -1)
-            self._vec(eps2_traj, "bind_eps2_traj", "eps2_traj", shape, torch.float64)
+            self._vec(eps2_traj, "bind_eps2_traj", "eps2_traj", shape, np.float64)
         _native.check(_native.lib().pbg_action_noise_set_eps2_traj(z, None if eps2_traj is None else eps2_traj.data_ptr()),
                       "pbg_action_noise_set_eps2_traj")
         self._eps2 = eps2_traj
@@ -519,10 +586,10 @@ class MLPPopulation(_NativeObject):
         if n < self.n_members or n % self.n_members != 0:
             raise _native.PbgError(f"MLPPopulation.fitness: {n} envs are not a positive multiple of the "
                                    f"{self.n_members} members")
-        cur = self._vec(cur, "fitness", "cur_return", (n,), torch.float64)
-        done = self._vec(done, "fitness", "done_return", (n,), torch.float64)
+        cur = self._vec(cur, "fitness", "cur_return", (n,), np.float64)
+        done = self._vec(done, "fitness", "done_return", (n,), np.float64)
         out = torch.empty(self.n_members, dtype=torch.float64, device=self.device) if out is None else out
-        out = self._vec(out, "fitness", "out", (self.n_members,), torch.float64)
+        out = self._vec(out, "fitness", "out", (self.n_members,), np.float64)
         _native.check(_native.lib().pbg_population_fitness(p, n, cur.data_ptr(), done.data_ptr(), out.data_ptr(),
                                                            self._stream()), "pbg_population_fitness")
         return out
@@ -607,7 +674,7 @@ class MLPPopulation(_NativeObject):
         if T < 1 or n < 1 or n % self.n_members != 0:
             raise _native.PbgError(f"MLPPopulation.act_where: T = {T} must be >= 1 and n = {n} a positive multiple of the "
                                    f"{self.n_members} members")
-        flags = self._vec(flags, "act_where", "flags", (T, n), torch.uint8)
+        flags = self._vec(flags, "act_where", "flags", (T, n), np.uint8)
         obs = self._vec(obs, "act_where", "obs", (T, n, self.obs_dim))
         out = torch.empty((T, n, self.act_dim), dtype=torch.float32, device=self.device) if out is None else out
         out = self._vec(out, "act_where", "out", (T, n, self.act_dim))

@@ -13,7 +13,16 @@ the whole update as one captured graph.  The collection half of an iteration has
 ``lr_linear`` (pbg_ppo_lr_linear) writes a scheduled learning rate that ``AdamClip.step`` reads from device memory, and
 with both an iteration can be one captured graph (``PPO(graph="iteration")``).  ``RetStats`` (pbg_ret_stats, include/pbg.h
 "Return statistics") keeps a running standard deviation of the discounted return on the device and scales the rewards
-``gae`` sees by it (``PPO(reward_norm=True)``): three launches more, inside the captured iteration too."""
+``gae`` sees by it (``PPO(reward_norm=True)``): three launches more, inside the captured iteration too.
+
+Who owns what.  ``policy._NativeObject`` is the base of every wrapper here (``PPOGrad``, ``AdamClip``, ``Permutation``,
+``RetStats``): the handle, ``close``, the closed guard, the device, and ``_ptr`` / ``_new`` / ``_launch``, which are
+``policy.check_array`` / ``new_array`` / ``launch`` on the object's side (its GPU, or the host twin's numpy arrays).  The
+free functions ``gae``, ``adv_norm`` and ``lr_linear`` call the same three directly.  In the trainer ``PPO._grad_args`` is
+the one place that knows what ``PPOGrad.run`` takes, ``PPO._gradient`` the one call of it (``ShardedPPO._gradient``: of
+``run_part`` and ``reduce``), and ``PPO._chain`` the one ``epochs x minibatches`` loop of ``optimizer="hip"``, called,
+captured or called after ``ShardedPPO``'s gather.  ``update`` (torch autograd) and ``_update_hip`` (torch optimiser) keep
+loops of their own: they are what the other paths are tested against."""
 from __future__ import annotations
 
 import ctypes
@@ -24,7 +33,17 @@ import numpy as np
 import torch
 
 from . import _native
-from .policy import ActionNoise, MLPPopulation, ObsStats
+from .policy import ActionNoise, MLPPopulation, ObsStats, _NativeObject, check_array, launch, new_array
+
+
+def _side(t, who, name):
+    """Where a free function runs, read off its first array: ``None`` (the host) for a numpy array, its GPU for a
+    tensor.  ``check_array`` then holds every array of the call, that one included, to this side."""
+    if isinstance(t, np.ndarray):
+        return None
+    if isinstance(t, torch.Tensor) and t.is_cuda:
+        return t.device
+    raise _native.PbgError(f"{who}: {name} must be a numpy array or a GPU tensor")
 
 
 def gae(rew_traj, done_traj, value, gamma: float = 0.99, lam: float = 0.95, adv=None, ret=None, trunc_traj=None,
@@ -45,44 +64,19 @@ def gae(rew_traj, done_traj, value, gamma: float = 0.99, lam: float = 0.95, adv=
     trunc = trunc_traj is not None
     if trunc and not hasattr(_native.lib(), "pbg_gae_trunc"):
         raise _native.PbgError(f"{_native.LIB_PATH} has no pbg_gae_trunc: a build without truncation bootstrapping")
-    host = isinstance(rew_traj, np.ndarray)
-    if rew_traj.ndim != 2:
-        raise _native.PbgError(f"gae: rew_traj must be [T, n], got shape {tuple(rew_traj.shape)}")
+    dev = _side(rew_traj, "gae", "rew_traj")
+    if rew_traj.ndim != 2 or min(rew_traj.shape) < 1:
+        raise _native.PbgError(f"gae: rew_traj must be [T, n] (T, n >= 1), got shape {tuple(rew_traj.shape)}")
     T, n = (int(d) for d in rew_traj.shape)
-    f32, u8 = (np.float32, np.uint8) if host else (torch.float32, torch.uint8)
-    new = (lambda: np.empty((T, n), np.float32)) if host else \
-        (lambda: torch.empty((T, n), dtype=torch.float32, device=rew_traj.device))
-    adv = new() if adv is None else adv
-    ret = new() if ret is None else ret
-    arrays = [("rew_traj", rew_traj, (T, n), f32), ("done_traj", done_traj, (T, n), u8), ("value", value, (T + 1, n), f32),
-              ("adv", adv, (T, n), f32), ("ret", ret, (T, n), f32)]
-    if trunc:
-        arrays += [("trunc_traj", trunc_traj, (T, n), u8), ("term_value", term_value, (T, n), f32)]
-    for name, t, shape, dt in arrays:
-        ok = isinstance(t, np.ndarray) and t.flags.c_contiguous if host else \
-            isinstance(t, torch.Tensor) and t.is_contiguous() and t.device == rew_traj.device and t.is_cuda
-        if not ok or tuple(t.shape) != shape or t.dtype != dt or T < 1 or n < 1:
-            raise _native.PbgError(f"gae: {name} must be a contiguous {dt} {'array' if host else 'GPU tensor'} of shape "
-                                   f"{shape} (T, n >= 1), all on one device")
-    if host:
-        if trunc:
-            _native.check(_native.lib().pbg_gae_trunc_host(T, n, rew_traj.ctypes.data, done_traj.ctypes.data,
-                                                           trunc_traj.ctypes.data, value.ctypes.data, term_value.ctypes.data,
-                                                           float(gamma), float(lam), adv.ctypes.data, ret.ctypes.data),
-                          "pbg_gae_trunc_host")
-            return adv, ret
-        _native.check(_native.lib().pbg_gae_host(T, n, rew_traj.ctypes.data, done_traj.ctypes.data, value.ctypes.data,
-                                                 float(gamma), float(lam), adv.ctypes.data, ret.ctypes.data), "pbg_gae_host")
-        return adv, ret
-    with torch.cuda.device(rew_traj.device):
-        stream = ctypes.c_void_p(torch.cuda.current_stream(rew_traj.device).cuda_stream)
-        if trunc:
-            _native.check(_native.lib().pbg_gae_trunc(T, n, rew_traj.data_ptr(), done_traj.data_ptr(), trunc_traj.data_ptr(),
-                                                      value.data_ptr(), term_value.data_ptr(), float(gamma), float(lam),
-                                                      adv.data_ptr(), ret.data_ptr(), stream), "pbg_gae_trunc")
-            return adv, ret
-        _native.check(_native.lib().pbg_gae(T, n, rew_traj.data_ptr(), done_traj.data_ptr(), value.data_ptr(), float(gamma),
-                                            float(lam), adv.data_ptr(), ret.data_ptr(), stream), "pbg_gae")
+    adv = new_array((T, n), np.float32, dev) if adv is None else adv
+    ret = new_array((T, n), np.float32, dev) if ret is None else ret
+    # the entry points' pointer order: the two truncation arrays follow done_traj and value
+    arrays = [("rew_traj", rew_traj, (T, n), np.float32), ("done_traj", done_traj, (T, n), np.uint8),
+              ("trunc_traj", trunc_traj, (T, n), np.uint8), ("value", value, (T + 1, n), np.float32),
+              ("term_value", term_value, (T, n), np.float32), ("adv", adv, (T, n), np.float32), ("ret", ret, (T, n), np.float32)]
+    p = [check_array(t, "gae", name, shape, dt, dev) for name, t, shape, dt in arrays if trunc or name not in
+         ("trunc_traj", "term_value")]
+    launch(dev, "pbg_gae" + "_trunc" * trunc + "_host" * (dev is None), T, n, *p[:-2], float(gamma), float(lam), *p[-2:])
     return adv, ret
 
 
@@ -105,7 +99,7 @@ def mlp_forward(theta, dims, x, obs_norm=None):
     return x
 
 
-class PPOGrad:
+class PPOGrad(_NativeObject):
     """The gradient of the clipped-surrogate loss of one minibatch as two HIP launches (include/pbg.h "PPO
     gradient", pbg_ppo_grad).  ``dims = (obs_dim, h1, h2, act_dim)``: the actor's; the critic is obs_dim -> h1 -> h2
     -> 1.  ``device``: a GPU, or ``None`` / ``"cpu"`` for the host twin (pbg_ppo_grad_host, numpy arrays, no GPU).
@@ -113,6 +107,7 @@ class PPOGrad:
     (pbg_ppo_grad_create) or ``"mfma"``, the matrix-core path for wide networks (pbg_ppo_grad_create_ex with
     PBG_PPO_GRAD_MFMA: the same forward bits, another order of the backward's sums); the host twin serves both and
     computes the same thing for either."""
+    _DESTROY, _HOST_HANDLE = "pbg_ppo_grad_destroy", False
 
     PATHS = {"fma": _native.PPO_GRAD_FMA, "mfma": _native.PPO_GRAD_MFMA}
 
@@ -129,77 +124,58 @@ class PPOGrad:
         self.Da = o * h1 + h1 + h1 * h2 + h2 + h2 * a + a
         self.Dc = o * h1 + h1 + h1 * h2 + h2 + h2 + 1
         self.max_rows = int(max_rows)
-        self.host = device is None or str(device) == "cpu"
-        self.device = None if self.host else torch.device(device)
-        self._h = ctypes.c_void_p()
+        index = self._set_device(device, "a GPU or None", host=True)
         if self.host:
             if self.max_rows < 1 or not (1 <= o <= _native.POLICY_MAX_DIM and 1 <= h1 <= _native.POLICY_MAX_DIM and
                                          1 <= h2 <= _native.POLICY_MAX_DIM and 1 <= a <= _native.POLICY_MAX_ACT):
                 raise _native.PbgError(f"PPOGrad: dims {self.dims} or max_rows {max_rows} out of range")
             return
-        if self.device.type != "cuda":
-            raise _native.PbgError(f"PPOGrad: device must be a GPU or None, got {device!r}")
-        index = self.device.index if self.device.index is not None else torch.cuda.current_device()
-        self.device = torch.device("cuda", index)
+        h = ctypes.c_void_p()
         if path == "fma":
-            _native.check(_native.lib().pbg_ppo_grad_create(index, o, h1, h2, a, self.max_rows, ctypes.byref(self._h)),
+            _native.check(_native.lib().pbg_ppo_grad_create(index, o, h1, h2, a, self.max_rows, ctypes.byref(h)),
                           "pbg_ppo_grad_create")
         else:
             if not hasattr(_native.lib(), "pbg_ppo_grad_create_ex"):
                 raise _native.PbgError(f"{_native.LIB_PATH} has no pbg_ppo_grad_create_ex: a build without the matrix-core path")
             opts = _native.PPOGradOpts(path=self.PATHS[path])
             _native.check(_native.lib().pbg_ppo_grad_create_ex(index, o, h1, h2, a, self.max_rows, ctypes.byref(opts),
-                                                               ctypes.byref(self._h)), "pbg_ppo_grad_create_ex")
+                                                               ctypes.byref(h)), "pbg_ppo_grad_create_ex")
+        self._h = h
 
-    def _ok(self, t, shape, dt):
-        if self.host:
-            return isinstance(t, np.ndarray) and t.flags.c_contiguous and tuple(t.shape) == shape and t.dtype == dt
-        return isinstance(t, torch.Tensor) and t.is_contiguous() and t.device == self.device and \
-            tuple(t.shape) == shape and t.dtype == dt
+    def _outputs(self, grad_actor, grad_critic, grad_log_std, stats):
+        """The four output arrays of ``run`` and ``reduce``: new ones where none were given."""
+        given = ((grad_actor, self.Da, np.float32), (grad_critic, self.Dc, np.float32), (grad_log_std, self.dims[3], np.float32),
+                 (stats, 4, np.float64))
+        return tuple(self._new(n, dt) if t is None else t for t, n, dt in given)
 
     def _io(self, who, theta_actor, theta_critic, log_std, obs, act, logp_old, adv, ret, idx, rows, adv_norm, obs_norm, clip_eps,
-            vf_coef, ent_coef, grad_actor, grad_critic, grad_log_std, stats, logp_out, v_out, outputs=True):
-        """The checked pbg_ppo_grad_io_t of ``run``, ``run_part`` (``outputs=False``: no gradient tensors) and ``reduce``,
-        and the four output tensors (new ones where none were given)."""
+            vf_coef, ent_coef, out, logp_out, v_out):
+        """The checked pbg_ppo_grad_io_t of ``run``, ``run_part`` and ``reduce``.  ``out``: the four output arrays
+        (``_outputs``), or four ``None`` for ``run_part``, which writes no gradient."""
         o, h1, h2, A = self.dims
-        f32, f64, i64 = (np.float32, np.float64, np.int64) if self.host else (torch.float32, torch.float64, torch.int64)
+        f32, f64 = np.float32, np.float64
         if getattr(obs, "ndim", 0) != 2:
             raise _native.PbgError(f"PPOGrad.{who}: obs must be [B, obs_dim]")
         B = int(obs.shape[0])
         Bm = int(idx.shape[0]) if idx is not None and getattr(idx, "ndim", 0) == 1 else (B if rows is None else int(rows))
-        new = (lambda n, dt: np.empty(n, dt)) if self.host else (lambda n, dt: torch.empty(n, dtype=dt, device=self.device))
-        if outputs:
-            grad_actor = new(self.Da, f32) if grad_actor is None else grad_actor
-            grad_critic = new(self.Dc, f32) if grad_critic is None else grad_critic
-            grad_log_std = new(A, f32) if grad_log_std is None else grad_log_std
-            stats = new(4, f64) if stats is None else stats
         mean, inv_std, clip = obs_norm if obs_norm is not None else (None, None, 0.0)
-        checks = [("theta_actor", theta_actor, (self.Da,), f32), ("theta_critic", theta_critic, (self.Dc,), f32),
-                  ("log_std", log_std, (A,), f32), ("obs", obs, (B, o), f32), ("act", act, (B, A), f32),
-                  ("logp_old", logp_old, (B,), f32), ("adv", adv, (B,), f32), ("ret", ret, (B,), f32)]
-        if outputs:
-            checks += [("grad_actor", grad_actor, (self.Da,), f32), ("grad_critic", grad_critic, (self.Dc,), f32),
-                       ("grad_log_std", grad_log_std, (A,), f32), ("stats", stats, (4,), f64)]
-        checks += [(n, t, s, d) for n, t, s, d in (("idx", idx, (Bm,), i64), ("adv_norm", adv_norm, (2,), f32),
-                                                   ("mean", mean, (o,), f32), ("inv_std", inv_std, (o,), f32),
-                                                   ("logp_out", logp_out, (Bm,), f32), ("v_out", v_out, (Bm,), f32))
-                   if t is not None]
-        for name, t, shape, dt in checks:
-            if not self._ok(t, shape, dt):
-                raise _native.PbgError(f"PPOGrad.{who}: {name} must be a contiguous {dt} "
-                                       f"{'array' if self.host else f'tensor on {self.device}'} of shape {shape}")
+        # (the struct's field, the array, its shape and dtype, whether it may be None: a null pointer then)
+        arrays = (("theta_actor", theta_actor, (self.Da,), f32, False), ("theta_critic", theta_critic, (self.Dc,), f32, False),
+                  ("log_std", log_std, (A,), f32, False), ("obs", obs, (B, o), f32, False), ("act", act, (B, A), f32, False),
+                  ("logp_old", logp_old, (B,), f32, False), ("adv", adv, (B,), f32, False), ("ret", ret, (B,), f32, False),
+                  ("grad_actor", out[0], (self.Da,), f32, True), ("grad_critic", out[1], (self.Dc,), f32, True),
+                  ("grad_log_std", out[2], (A,), f32, True), ("stats", out[3], (4,), f64, True),
+                  ("idx", idx, (Bm,), np.int64, True), ("adv_norm", adv_norm, (2,), f32, True), ("mean", mean, (o,), f32, True),
+                  ("inv_std", inv_std, (o,), f32, True), ("logp_out", logp_out, (Bm,), f32, True), ("v_out", v_out, (Bm,), f32, True))
+        at, dev = (self, who), self.device   # _ptr's check, without a call in between: eighteen pointers per minibatch
+        p = {name: None if t is None and optional else check_array(t, at, name, shape, dt, dev)
+             for name, t, shape, dt, optional in arrays}
         if Bm < 1 or Bm > self.max_rows or (idx is None and Bm > B):
             raise _native.PbgError(f"PPOGrad.{who}: {Bm} minibatch rows outside 1 .. max_rows = {self.max_rows} (or the batch's {B})")
         if (mean is None) != (inv_std is None):
             raise _native.PbgError(f"PPOGrad.{who}: obs_norm needs both mean and inv_std")
-        ptr = (lambda t: None if t is None else t.ctypes.data) if self.host else (lambda t: None if t is None else t.data_ptr())
-        io = _native.PPOGradIO(batch_rows=B, mb_rows=Bm, theta_actor=ptr(theta_actor), theta_critic=ptr(theta_critic),
-                               log_std=ptr(log_std), mean=ptr(mean), inv_std=ptr(inv_std), clip=float(clip),
-                               clip_eps=float(clip_eps), vf_coef=float(vf_coef), ent_coef=float(ent_coef), obs=ptr(obs),
-                               act=ptr(act), logp_old=ptr(logp_old), adv=ptr(adv), ret=ptr(ret), idx=ptr(idx),
-                               adv_norm=ptr(adv_norm), grad_actor=ptr(grad_actor), grad_critic=ptr(grad_critic),
-                               grad_log_std=ptr(grad_log_std), stats=ptr(stats), logp_out=ptr(logp_out), v_out=ptr(v_out))
-        return io, (grad_actor, grad_critic, grad_log_std, stats)
+        return _native.PPOGradIO(batch_rows=B, mb_rows=Bm, clip=float(clip), clip_eps=float(clip_eps), vf_coef=float(vf_coef),
+                                 ent_coef=float(ent_coef), **p)
 
     def run(self, theta_actor, theta_critic, log_std, obs, act, logp_old, adv, ret, idx=None, rows=None, adv_norm=None,
             obs_norm=None, clip_eps: float = 0.2, vf_coef: float = 0.5, ent_coef: float = 0.0, grad_actor=None,
@@ -211,32 +187,29 @@ class PPOGrad:
         clip)`` or ``None``.  The outputs are written into the given tensors, or into new ones.  ``stats``: pg loss, vf
         loss, clipped fraction, mean(logp_old - logp).  ``logp_out``, ``v_out``: optional float32 ``[Bm]``.  The indices
         are not validated on a GPU."""
-        o, h1, h2, A = self.dims
-        io, out = self._io("run", theta_actor, theta_critic, log_std, obs, act, logp_old, adv, ret, idx, rows, adv_norm, obs_norm,
-                           clip_eps, vf_coef, ent_coef, grad_actor, grad_critic, grad_log_std, stats, logp_out, v_out)
+        out = self._outputs(grad_actor, grad_critic, grad_log_std, stats)
+        io = self._io("run", theta_actor, theta_critic, log_std, obs, act, logp_old, adv, ret, idx, rows, adv_norm, obs_norm,
+                      clip_eps, vf_coef, ent_coef, out, logp_out, v_out)
         if self.host:
-            _native.check(_native.lib().pbg_ppo_grad_host(o, h1, h2, A, ctypes.byref(io)), "pbg_ppo_grad_host")
+            self._launch("pbg_ppo_grad_host", *self.dims, ctypes.byref(io))
         else:
-            if not self._h:
-                raise _native.PbgError("PPOGrad.run: the object is closed")
-            with torch.cuda.device(self.device):
-                stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-                _native.check(_native.lib().pbg_ppo_grad_run(self._h, ctypes.byref(io), stream), "pbg_ppo_grad_run")
+            self._launch("pbg_ppo_grad_run", self._open("run"), ctypes.byref(io))
         return out
 
     def _parts(self, who):
         if not hasattr(_native.lib(), "pbg_ppo_grad_run_part"):
             raise _native.PbgError(f"{_native.LIB_PATH} has no pbg_ppo_grad_run_part: a build without the gradient as parts")
-        if self.host or not self._h:
+        if self.host:
             raise _native.PbgError(f"PPOGrad.{who}: needs an open object on a GPU")
-        return _native.lib()
+        return self._open(who)
 
     def geometry(self, mb_rows: int):
         """``(G, Dtot)``: the workgroups ``run`` launches for a minibatch of ``mb_rows`` rows and the floats of one
         workgroup's partial (pbg_ppo_grad_geometry, no GPU work)."""
-        L = self._parts("geometry")
+        h = self._parts("geometry")
         G, dtot = ctypes.c_int(), ctypes.c_int64()
-        _native.check(L.pbg_ppo_grad_geometry(self._h, int(mb_rows), ctypes.byref(G), ctypes.byref(dtot)), "pbg_ppo_grad_geometry")
+        _native.check(_native.lib().pbg_ppo_grad_geometry(h, int(mb_rows), ctypes.byref(G), ctypes.byref(dtot)),
+                      "pbg_ppo_grad_geometry")
         return G.value, dtot.value
 
     def run_part(self, theta_actor, theta_critic, log_std, obs, act, logp_old, adv, ret, wg_first, wg_count, part_out,
@@ -247,21 +220,16 @@ class PPOGrad:
         ``[wg_count, 4]``), contiguous tensors (or row ranges of ones) on the object's GPU.  No gradient is written;
         ``logp_out`` / ``v_out`` get the rows of these workgroups' tiles.  ``wg_count = 0`` launches nothing.  The other
         arguments and their checks are ``run``'s."""
-        L = self._parts("run_part")
-        io, _ = self._io("run_part", theta_actor, theta_critic, log_std, obs, act, logp_old, adv, ret, idx, rows, adv_norm, obs_norm,
-                         clip_eps, vf_coef, ent_coef, None, None, None, None, logp_out, v_out, outputs=False)
+        h = self._parts("run_part")
+        io = self._io("run_part", theta_actor, theta_critic, log_std, obs, act, logp_old, adv, ret, idx, rows, adv_norm, obs_norm,
+                      clip_eps, vf_coef, ent_coef, (None,) * 4, logp_out, v_out)
         wg_first, wg_count = int(wg_first), int(wg_count)
         G, dtot = self.geometry(io.mb_rows)
         if wg_first < 0 or wg_count < 0 or wg_first + wg_count > G:
             raise _native.PbgError(f"PPOGrad.run_part: workgroups {wg_first} .. {wg_first} + {wg_count} outside 0 .. {G}")
-        for name, t, shape, dt in (("part_out", part_out, (wg_count, dtot), torch.float32),
-                                   ("part_stats_out", part_stats_out, (wg_count, 4), torch.float64)):
-            if not self._ok(t, shape, dt):
-                raise _native.PbgError(f"PPOGrad.run_part: {name} must be a contiguous {dt} tensor on {self.device} of shape {shape}")
-        with torch.cuda.device(self.device):
-            stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            _native.check(L.pbg_ppo_grad_run_part(self._h, ctypes.byref(io), wg_first, wg_count, part_out.data_ptr(),
-                                                  part_stats_out.data_ptr(), stream), "pbg_ppo_grad_run_part")
+        self._launch("pbg_ppo_grad_run_part", h, ctypes.byref(io), wg_first, wg_count,
+                     self._ptr(part_out, "run_part", "part_out", (wg_count, dtot)),
+                     self._ptr(part_stats_out, "run_part", "part_stats_out", (wg_count, 4), np.float64))
 
     def reduce(self, theta_actor, theta_critic, log_std, obs, act, logp_old, adv, ret, G, part, part_stats, idx=None, rows=None,
                adv_norm=None, obs_norm=None, clip_eps: float = 0.2, vf_coef: float = 0.5, ent_coef: float = 0.0, grad_actor=None,
@@ -270,32 +238,17 @@ class PPOGrad:
         ``[G, 4]``): ``(grad_actor, grad_critic, grad_log_std, stats)`` as ``run`` returns them.  ``G`` must be
         ``geometry``'s for the minibatch; the other arguments and their checks are ``run``'s (of them the launch reads
         the minibatch's size and ``ent_coef``)."""
-        L = self._parts("reduce")
-        io, out = self._io("reduce", theta_actor, theta_critic, log_std, obs, act, logp_old, adv, ret, idx, rows, adv_norm, obs_norm,
-                           clip_eps, vf_coef, ent_coef, grad_actor, grad_critic, grad_log_std, stats, logp_out, v_out)
+        h = self._parts("reduce")
+        out = self._outputs(grad_actor, grad_critic, grad_log_std, stats)
+        io = self._io("reduce", theta_actor, theta_critic, log_std, obs, act, logp_old, adv, ret, idx, rows, adv_norm, obs_norm,
+                      clip_eps, vf_coef, ent_coef, out, logp_out, v_out)
         G = int(G)
         Gq, dtot = self.geometry(io.mb_rows)
         if G != Gq:
             raise _native.PbgError(f"PPOGrad.reduce: G = {G} is not the {Gq} workgroups of {io.mb_rows} minibatch rows")
-        for name, t, shape, dt in (("part", part, (G, dtot), torch.float32), ("part_stats", part_stats, (G, 4), torch.float64)):
-            if not self._ok(t, shape, dt):
-                raise _native.PbgError(f"PPOGrad.reduce: {name} must be a contiguous {dt} tensor on {self.device} of shape {shape}")
-        with torch.cuda.device(self.device):
-            stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            _native.check(L.pbg_ppo_grad_reduce(self._h, ctypes.byref(io), G, part.data_ptr(), part_stats.data_ptr(), stream),
-                          "pbg_ppo_grad_reduce")
+        self._launch("pbg_ppo_grad_reduce", h, ctypes.byref(io), G, self._ptr(part, "reduce", "part", (G, dtot)),
+                     self._ptr(part_stats, "reduce", "part_stats", (G, 4), np.float64))
         return out
-
-    def close(self):
-        if self._h:
-            _native.lib().pbg_ppo_grad_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def _need_opt():
@@ -310,40 +263,26 @@ def adv_norm(adv, idx=None, out=None):
     that ``PPOGrad.run`` takes as ``adv_norm``: pbg_adv_norm, one launch, float64 sums in the order include/pbg.h
     states.  Contiguous tensors on one GPU run the launch (the indices are not validated there); numpy arrays run
     the same sums on the host (pbg_adv_norm_host, the same bits, the indices validated)."""
-    L = _need_opt()
-    host = isinstance(adv, np.ndarray)
-    f32, i64 = (np.float32, np.int64) if host else (torch.float32, torch.int64)
-    if getattr(adv, "ndim", 0) != 1:
+    _need_opt()
+    dev = _side(adv, "adv_norm", "adv")
+    if adv.ndim != 1:
         raise _native.PbgError("adv_norm: adv must be a float32 [B] array or GPU tensor")
     B = int(adv.shape[0])
     Bm = int(idx.shape[0]) if idx is not None and getattr(idx, "ndim", 0) == 1 else B
-    if out is None:
-        out = np.empty(2, np.float32) if host else torch.empty(2, dtype=torch.float32, device=adv.device)
-    for name, t, shape, dt in (("adv", adv, (B,), f32), ("idx", idx, (Bm,), i64), ("out", out, (2,), f32)):
-        if t is None and name == "idx":
-            continue
-        ok = isinstance(t, np.ndarray) and t.flags.c_contiguous if host else \
-            isinstance(t, torch.Tensor) and t.is_contiguous() and t.is_cuda and t.device == adv.device
-        if not ok or tuple(t.shape) != shape or t.dtype != dt:
-            raise _native.PbgError(f"adv_norm: {name} must be a contiguous {dt} {'array' if host else 'GPU tensor'} of shape "
-                                   f"{shape}, all on one device")
-    if host:
-        _native.check(L.pbg_adv_norm_host(B, Bm, adv.ctypes.data, None if idx is None else idx.ctypes.data, out.ctypes.data),
-                      "pbg_adv_norm_host")
-        return out
-    with torch.cuda.device(adv.device):
-        stream = ctypes.c_void_p(torch.cuda.current_stream(adv.device).cuda_stream)
-        _native.check(L.pbg_adv_norm(B, Bm, adv.data_ptr(), None if idx is None else idx.data_ptr(), out.data_ptr(), stream),
-                      "pbg_adv_norm")
+    out = new_array(2, np.float32, dev) if out is None else out
+    launch(dev, "pbg_adv_norm" + "_host" * (dev is None), B, Bm, check_array(adv, "adv_norm", "adv", (B,), np.float32, dev),
+           None if idx is None else check_array(idx, "adv_norm", "idx", (Bm,), np.int64, dev),
+           check_array(out, "adv_norm", "out", (2,), np.float32, dev))
     return out
 
 
-class AdamClip:
+class AdamClip(_NativeObject):
     """Adam with global-norm gradient clipping over up to 8 flat float32 blocks as two HIP launches (include/pbg.h
     "PPO optimiser step", pbg_ppo_opt).  ``sizes``: the blocks' element counts.  ``device``: a GPU, whose object then
     owns the moments, the step count and the running powers of the betas on the device (so a captured step that is
     replayed advances like an eager one), or ``None`` / ``"cpu"`` for the host twin (pbg_ppo_opt_host: numpy arrays,
     no GPU, the state kept here as numpy arrays; the same bits)."""
+    _DESTROY, _HOST_HANDLE = "pbg_ppo_opt_destroy", False
 
     def __init__(self, sizes, device=None):
         L = _need_opt()
@@ -351,24 +290,13 @@ class AdamClip:
         if not 1 <= len(self.sizes) <= _native.PPO_OPT_MAX_BLOCKS or min(self.sizes) < 1:
             raise _native.PbgError(f"AdamClip: 1 .. {_native.PPO_OPT_MAX_BLOCKS} blocks of at least one element, got {sizes!r}")
         self._sizes = (ctypes.c_int64 * len(self.sizes))(*self.sizes)
-        self.host = device is None or str(device) == "cpu"
-        self.device = None if self.host else torch.device(device)
-        self._h = ctypes.c_void_p()
+        index = self._set_device(device, "a GPU or None", host=True)
         if self.host:
             self.reset()
             return
-        if self.device.type != "cuda":
-            raise _native.PbgError(f"AdamClip: device must be a GPU or None, got {device!r}")
-        index = self.device.index if self.device.index is not None else torch.cuda.current_device()
-        self.device = torch.device("cuda", index)
-        _native.check(L.pbg_ppo_opt_create(index, len(self.sizes), self._sizes, ctypes.byref(self._h)), "pbg_ppo_opt_create")
-
-    def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
-    def _open(self, what):
-        if not self.host and not self._h:
-            raise _native.PbgError(f"AdamClip.{what}: the object is closed")
+        h = ctypes.c_void_p()
+        _native.check(L.pbg_ppo_opt_create(index, len(self.sizes), self._sizes, ctypes.byref(h)), "pbg_ppo_opt_create")
+        self._h = h
 
     def step(self, params, grads, lr, betas=(0.9, 0.999), eps: float = 1e-8, max_grad_norm: float = 0.0, info=None):
         """One step on ``params`` (updated in place) with ``grads``: sequences of contiguous float32 ``[sizes[b]]``
@@ -377,42 +305,29 @@ class AdamClip:
         float, a launch argument like the other scalars (a captured step keeps the value it was captured with), or a
         float64 ``[1]`` tensor on the object's GPU (a numpy ``[1]`` array on the host) that the step reads where it
         lies: the bits of the same value passed as a float, and a captured step follows the tensor."""
-        self._open("step")
-        f32, f64 = (np.float32, np.float64) if self.host else (torch.float32, torch.float64)
+        h = self._open("step")
         params, grads = list(params), list(grads)
         lr_t = lr if isinstance(lr, (np.ndarray, torch.Tensor)) else None
         if len(params) != len(self.sizes) or len(grads) != len(self.sizes):
             raise _native.PbgError(f"AdamClip.step: {len(self.sizes)} blocks expected, got {len(params)} params and "
                                    f"{len(grads)} grads")
-        checks = [(f"params[{b}]", t, (s,), f32) for b, (t, s) in enumerate(zip(params, self.sizes))]
-        checks += [(f"grads[{b}]", t, (s,), f32) for b, (t, s) in enumerate(zip(grads, self.sizes))]
-        if info is not None:
-            checks.append(("info", info, (2,), f64))
-        if lr_t is not None:
-            checks.append(("lr", lr_t, (1,), f64))
-        for name, t, shape, dt in checks:
-            ok = isinstance(t, np.ndarray) and t.flags.c_contiguous if self.host else \
-                isinstance(t, torch.Tensor) and t.is_contiguous() and t.device == self.device
-            if not ok or tuple(t.shape) != shape or t.dtype != dt:
-                raise _native.PbgError(f"AdamClip.step: {name} must be a contiguous {dt} "
-                                       f"{'array' if self.host else f'tensor on {self.device}'} of shape {shape}")
-        ptr = (lambda t: t.ctypes.data) if self.host else (lambda t: t.data_ptr())
-        kw = dict(param=[ptr(t) for t in params], grad=[ptr(t) for t in grads], lr=0.0 if lr_t is not None else float(lr),
-                  beta1=float(betas[0]), beta2=float(betas[1]), eps=float(eps), max_grad_norm=float(max_grad_norm or 0.0),
-                  info=None if info is None else ptr(info))
+        kw = dict(param=[self._ptr(t, "step", f"params[{b}]", (s,)) for b, (t, s) in enumerate(zip(params, self.sizes))],
+                  grad=[self._ptr(t, "step", f"grads[{b}]", (s,)) for b, (t, s) in enumerate(zip(grads, self.sizes))],
+                  lr=0.0 if lr_t is not None else float(lr), beta1=float(betas[0]), beta2=float(betas[1]), eps=float(eps),
+                  max_grad_norm=float(max_grad_norm or 0.0),
+                  info=None if info is None else self._ptr(info, "step", "info", (2,), np.float64))
         # the struct's first version while no lr tensor is given: a library from before lr_ptr keeps working
         IO = _native.PPOOptIO
         if lr_t is not None:
             _need_perm()
-            IO, kw["lr_ptr"] = _native.PPOOptIO2, ptr(lr_t)
+            IO, kw["lr_ptr"] = _native.PPOOptIO2, self._ptr(lr_t, "step", "lr", (1,), np.float64)
         if self.host:
-            io = IO(m=[ptr(t) for t in self._m], v=[ptr(t) for t in self._v], t=self._t.ctypes.data,
-                                  bpow=self._bpow.ctypes.data, **kw)
-            _native.check(_native.lib().pbg_ppo_opt_host(len(self.sizes), self._sizes, ctypes.byref(io)), "pbg_ppo_opt_host")
+            io = IO(m=[t.ctypes.data for t in self._m], v=[t.ctypes.data for t in self._v], t=self._t.ctypes.data,
+                    bpow=self._bpow.ctypes.data, **kw)
+            self._launch("pbg_ppo_opt_host", len(self.sizes), self._sizes, ctypes.byref(io))
             return
         io = IO(**kw)
-        with torch.cuda.device(self.device):
-            _native.check(_native.lib().pbg_ppo_opt_step(self._h, ctypes.byref(io), self._stream()), "pbg_ppo_opt_step")
+        self._launch("pbg_ppo_opt_step", h, ctypes.byref(io))
 
     def reset(self):
         """Zero moments, step count 0 (stream order on a GPU)."""
@@ -421,9 +336,7 @@ class AdamClip:
             self._v = [np.zeros(s, np.float32) for s in self.sizes]
             self._t, self._bpow = np.zeros(1, np.uint32), np.ones(2, np.float64)
             return
-        self._open("reset")
-        with torch.cuda.device(self.device):
-            _native.check(_native.lib().pbg_ppo_opt_reset(self._h, self._stream()), "pbg_ppo_opt_reset")
+        self._launch("pbg_ppo_opt_reset", self._open("reset"))
 
     def state(self):
         """``(m, v, t)``: the two moments as lists of float32 ``[sizes[b]]`` and the step count (``[1]``: int32 bits of
@@ -431,25 +344,11 @@ class AdamClip:
         the host)."""
         if self.host:
             return [a.copy() for a in self._m], [a.copy() for a in self._v], self._t.copy()
-        self._open("state")
-        n = sum(self.sizes)
-        m, v = (torch.empty(n, dtype=torch.float32, device=self.device) for _ in range(2))
+        h, n = self._open("state"), sum(self.sizes)
+        m, v = self._new(n), self._new(n)
         t = torch.zeros(1, dtype=torch.int32, device=self.device)
-        with torch.cuda.device(self.device):
-            _native.check(_native.lib().pbg_ppo_opt_get_state(self._h, m.data_ptr(), v.data_ptr(), t.data_ptr(), self._stream()),
-                          "pbg_ppo_opt_get_state")
+        self._launch("pbg_ppo_opt_get_state", h, m.data_ptr(), v.data_ptr(), t.data_ptr())
         return list(m.split(self.sizes)), list(v.split(self.sizes)), t
-
-    def close(self):
-        if self._h:
-            _native.lib().pbg_ppo_opt_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def _need_perm():
@@ -458,56 +357,39 @@ def _need_perm():
     return _native.lib()
 
 
-class Permutation:
+class Permutation(_NativeObject):
     """Counter-based permutations of ``0 .. B - 1`` (include/pbg.h "Counter-based permutations", pbg_perm): an
     eight-round Feistel network keyed by Philox words of ``(seed, counter)``, cycle-walked into range; ``rng.permutation``
     is the numpy mirror with the same bits.  ``device``: a GPU, whose object owns the counter on the device (so a
     captured fill that is replayed draws the next permutations like an eager one), or ``None`` / ``"cpu"`` for the host
     twin (pbg_perm_host on numpy arrays, the counter kept here)."""
+    _DESTROY, _HOST_HANDLE = "pbg_perm_destroy", False
 
     def __init__(self, seed: int, device=None):
         L = _need_perm()
         self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-        self.host = device is None or str(device) == "cpu"
-        self.device = None if self.host else torch.device(device)
-        self._h = ctypes.c_void_p()
         self._counter = 0
+        index = self._set_device(device, "a GPU or None", host=True)
         if self.host:
             return
-        if self.device.type != "cuda":
-            raise _native.PbgError(f"Permutation: device must be a GPU or None, got {device!r}")
-        index = self.device.index if self.device.index is not None else torch.cuda.current_device()
-        self.device = torch.device("cuda", index)
-        _native.check(L.pbg_perm_create(index, self.seed, ctypes.byref(self._h)), "pbg_perm_create")
-
-    def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
-    def _open(self, what):
-        if not self.host and not self._h:
-            raise _native.PbgError(f"Permutation.{what}: the object is closed")
+        h = ctypes.c_void_p()
+        _native.check(L.pbg_perm_create(index, self.seed, ctypes.byref(h)), "pbg_perm_create")
+        self._h = h
 
     def fill(self, B: int, n_perms: int = 1, out=None):
         """``out``, int64 ``[n_perms, B]``: row j is the permutation at ``counter + j``; the counter then advances by
         ``n_perms`` (uint32, it wraps).  On a GPU: two launches on the current stream, no host work."""
-        self._open("fill")
+        h = self._open("fill")
         B, n_perms = int(B), int(n_perms)
         if B < 1 or not 1 <= n_perms <= 65535:
             raise _native.PbgError(f"Permutation.fill: B = {B} must be >= 1 and n_perms = {n_perms} in 1 .. 65535")
-        if out is None:
-            out = np.empty((n_perms, B), np.int64) if self.host else \
-                torch.empty((n_perms, B), dtype=torch.int64, device=self.device)
-        ok = isinstance(out, np.ndarray) and out.flags.c_contiguous and out.dtype == np.int64 if self.host else \
-            isinstance(out, torch.Tensor) and out.is_contiguous() and out.device == self.device and out.dtype == torch.int64
-        if not ok or tuple(out.shape) != (n_perms, B):
-            raise _native.PbgError(f"Permutation.fill: out must be a contiguous int64 "
-                                   f"{'array' if self.host else f'tensor on {self.device}'} of shape {(n_perms, B)}")
+        out = self._new((n_perms, B), np.int64) if out is None else out
+        p = self._ptr(out, "fill", "out", (n_perms, B), np.int64)
         if self.host:
-            _native.check(_native.lib().pbg_perm_host(self.seed, self._counter, B, n_perms, out.ctypes.data), "pbg_perm_host")
+            self._launch("pbg_perm_host", self.seed, self._counter, B, n_perms, p)
             self._counter = (self._counter + n_perms) & 0xFFFFFFFF
-            return out
-        with torch.cuda.device(self.device):
-            _native.check(_native.lib().pbg_perm_fill(self._h, B, n_perms, out.data_ptr(), self._stream()), "pbg_perm_fill")
+        else:
+            self._launch("pbg_perm_fill", h, B, n_perms, p)
         return out
 
     @property
@@ -515,10 +397,9 @@ class Permutation:
         """Permutations drawn so far, modulo 2^32 (on a GPU it synchronises to read it); assignable."""
         if self.host:
             return self._counter
-        self._open("counter")
+        h = self._open("counter")
         out = torch.zeros(1, dtype=torch.int32, device=self.device)
-        with torch.cuda.device(self.device):
-            _native.check(_native.lib().pbg_perm_get_counter(self._h, out.data_ptr(), self._stream()), "pbg_perm_get_counter")
+        self._launch("pbg_perm_get_counter", h, out.data_ptr())
         return int(out.item()) & 0xFFFFFFFF
 
     @counter.setter
@@ -526,53 +407,26 @@ class Permutation:
         if self.host:
             self._counter = int(value) & 0xFFFFFFFF
             return
-        self._open("counter")
-        with torch.cuda.device(self.device):
-            _native.check(_native.lib().pbg_perm_set_counter(self._h, int(value) & 0xFFFFFFFF, self._stream()),
-                          "pbg_perm_set_counter")
-
-    def close(self):
-        if self._h:
-            _native.lib().pbg_perm_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._launch("pbg_perm_set_counter", self._open("counter"), int(value) & 0xFFFFFFFF)
 
 
 def lr_linear(it, n_total: int, lr0: float, out=None):
     """``out``, float64 ``[1]`` = ``lr0 * (1 - min(it, n_total) / n_total)``: pbg_ppo_lr_linear, one launch of one lane,
     float64 in that order (``rng.lr_linear`` gives the same bits).  ``it``: an int32 ``[1]`` tensor on a GPU (read as
     uint32), or a numpy uint32 ``[1]`` array for the host twin (pbg_ppo_lr_linear_host)."""
-    L = _need_perm()
-    host = isinstance(it, np.ndarray)
+    _need_perm()
     n_total = int(n_total)
     if not 1 <= n_total <= 0xFFFFFFFF:
         raise _native.PbgError(f"lr_linear: n_total = {n_total} outside 1 .. 2^32 - 1")
-    if out is None:
-        out = np.empty(1, np.float64) if host else torch.empty(1, dtype=torch.float64, device=it.device)
-    if host:
-        ok = it.dtype == np.uint32 and it.shape == (1,) and isinstance(out, np.ndarray) and out.dtype == np.float64 and \
-            out.shape == (1,)
-    else:
-        ok = isinstance(it, torch.Tensor) and it.is_cuda and it.dtype == torch.int32 and tuple(it.shape) == (1,) and \
-            isinstance(out, torch.Tensor) and out.device == it.device and out.dtype == torch.float64 and tuple(out.shape) == (1,)
-    if not ok:
-        raise _native.PbgError("lr_linear: it must be an int32 [1] GPU tensor (a uint32 [1] array on the host) and out a "
-                               "float64 [1] on the same device")
-    if host:
-        _native.check(L.pbg_ppo_lr_linear_host(it.ctypes.data, n_total, float(lr0), out.ctypes.data), "pbg_ppo_lr_linear_host")
-        return out
-    with torch.cuda.device(it.device):
-        stream = ctypes.c_void_p(torch.cuda.current_stream(it.device).cuda_stream)
-        _native.check(L.pbg_ppo_lr_linear(it.data_ptr(), n_total, float(lr0), out.data_ptr(), stream), "pbg_ppo_lr_linear")
+    dev = _side(it, "lr_linear", "it")
+    out = new_array(1, np.float64, dev) if out is None else out
+    launch(dev, "pbg_ppo_lr_linear" + "_host" * (dev is None),
+           check_array(it, "lr_linear", "it", (1,), np.uint32 if dev is None else np.int32, dev), n_total, float(lr0),
+           check_array(out, "lr_linear", "out", (1,), np.float64, dev))
     return out
 
 
-class RetStats:
+class RetStats(_NativeObject):
     """Reward scaling by a running standard deviation of the discounted return (include/pbg.h "Return statistics",
     pbg_ret_stats), what VecNormalize does to rewards.  ``n_envs`` envs each keep a running return
     ``R <- gamma R + r``, reset where ``done`` is set and carried from one ``update`` to the next; ``finalize`` folds the
@@ -581,6 +435,7 @@ class RetStats:
     of that on the device (three launches, no atomics, nothing read back: a captured round that is replayed advances
     like an eager one), or ``None`` / ``"cpu"`` for the host twin (the same entry points on numpy arrays, no GPU, the
     same bits).  ``n_slots``: default ``ceil(n_envs / 32)``; more when the object also finalizes other shards' slots."""
+    _DESTROY = "pbg_ret_stats_destroy"   # the host twin is a native object too
 
     TILE = 32
 
@@ -589,48 +444,16 @@ class RetStats:
             raise _native.PbgError(f"{_native.LIB_PATH} has no pbg_ret_stats_create: a build without return statistics")
         self.n_envs, self.gamma = int(n_envs), float(gamma)
         self.n_slots = -(-self.n_envs // self.TILE) if n_slots is None else int(n_slots)
-        self.host = device is None or str(device) == "cpu"
-        self.device = None if self.host else torch.device(device)
-        self._h = ctypes.c_void_p()
-        index = -1
-        if not self.host:
-            if self.device.type != "cuda":
-                raise _native.PbgError(f"RetStats: device must be a GPU or None, got {device!r}")
-            index = self.device.index if self.device.index is not None else torch.cuda.current_device()
-            self.device = torch.device("cuda", index)
-        _native.check(_native.lib().pbg_ret_stats_create(index, self.n_envs, self.n_slots, self.gamma, ctypes.byref(self._h)),
+        index = self._set_device(device, "a GPU or None", host=True)
+        h = ctypes.c_void_p()
+        _native.check(_native.lib().pbg_ret_stats_create(index, self.n_envs, self.n_slots, self.gamma, ctypes.byref(h)),
                       "pbg_ret_stats_create")
-
-    def _open(self, what):
-        if not self._h:
-            raise _native.PbgError(f"RetStats.{what}: the object is closed")
-        return self._h
+        self._h = h
 
     def _call(self, name, *args):
-        """``pbg_ret_stats_<name>(handle, *args, stream)`` on the current stream of the object's GPU."""
-        h, f = self._open(name), getattr(_native.lib(), "pbg_ret_stats_" + name)
-        if self.host:
-            _native.check(f(h, *args, None), "pbg_ret_stats_" + name)
-            return
-        with torch.cuda.device(self.device):
-            stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            _native.check(f(h, *args, stream), "pbg_ret_stats_" + name)
-
-    def _ptr(self, t, what, name, shape, dt):
-        """The pointer of ``t``, which must already be a contiguous array (host) or tensor on the object's GPU of
-        ``shape`` and of the numpy dtype ``dt``: nothing is converted silently."""
-        if self.host:
-            ok = isinstance(t, np.ndarray) and t.flags.c_contiguous and t.dtype == dt
-        else:
-            ok = isinstance(t, torch.Tensor) and t.is_contiguous() and t.device == self.device and \
-                t.dtype == getattr(torch, np.dtype(dt).name)
-        if not ok or tuple(t.shape) != tuple(shape):
-            raise _native.PbgError(f"RetStats.{what}: {name} must be a contiguous {np.dtype(dt).name} "
-                                   f"{'array' if self.host else f'tensor on {self.device}'} of shape {tuple(shape)}")
-        return t.ctypes.data if self.host else t.data_ptr()
-
-    def _new(self, shape, dt):
-        return np.empty(shape, dt) if self.host else torch.empty(shape, dtype=getattr(torch, np.dtype(dt).name), device=self.device)
+        """``pbg_ret_stats_<name>(handle, *args, stream)`` on the current stream of the object's GPU; the host twin
+        goes through the same entry points with no stream."""
+        self._launch("pbg_ret_stats_" + name, self._open(name), *args, *((None,) if self.host else ()))
 
     def update(self, rew_traj, done_traj, slot_offset: int = 0):
         """Walk ``rew_traj`` (float32 ``[T, n]``) and ``done_traj`` (uint8 ``[T, n]``), ``n <= n_envs``: every env's
@@ -720,17 +543,6 @@ class RetStats:
         self._call("set_carry", p["carry"])
         self._call("set_scale", p["scale"])
         self._src = dict(state)   # alive until the stream has copied them
-
-    def close(self):
-        if self._h:
-            _native.lib().pbg_ret_stats_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 @dataclass
@@ -899,13 +711,14 @@ class PPO:
             for p in (self.actor_theta, self.critic_theta, self.log_std):
                 p.grad = torch.zeros_like(p.data)
             self._grad_stats = torch.zeros(4, dtype=torch.float64, device=dev)
+            # the storage both optimisers move in place: what every launch of the update reads and writes
+            self._params = [self.actor_theta.data, self.critic_theta.data, self.log_std.data]
+            self._grads = [self.actor_theta.grad, self.critic_theta.grad, self.log_std.grad]
         self.adam = self._graph = self.perm = self._it_dev = self._iter_graph = None
         self.permutation, self.lr_schedule, self.graph_iteration = permutation, lr_schedule, graph == "iteration"
         if optimizer == "hip":
             if norm_adv and (T * nb) // self.minibatches < 2:
                 raise _native.PbgError("PPO: optimizer='hip' with norm_adv needs minibatches of at least 2 rows")
-            self._params = [self.actor_theta.data, self.critic_theta.data, self.log_std.data]
-            self._grads = [self.actor_theta.grad, self.critic_theta.grad, self.log_std.grad]
             self.adam = AdamClip([p.numel() for p in self._params], dev)
             self.lr, self.use_graph = float(lr), graph is True
             self._adv_norm = torch.zeros(2, **kw)
@@ -920,10 +733,9 @@ class PPO:
                 self._lr_now = self._lr_dev
             if permutation == "device":
                 self.perm = Permutation(self.seed, dev)
-            if graph or permutation == "device":
-                # what a replay reads and a new iteration must refill in place
-                self._perm = torch.zeros((self.epochs, self.minibatches, (T * nb) // self.minibatches), dtype=torch.int64, device=dev)
-                self._logp_old = torch.zeros(T * nb, **kw)
+            # what the chain (and a replay of it) reads and every update refills in place
+            self._perm = torch.zeros((self.epochs, self.minibatches, (T * nb) // self.minibatches), dtype=torch.int64, device=dev)
+            self._logp_old = torch.zeros(T * nb, **kw)
         env.reset()
 
     def _batch_envs(self, env) -> int:
@@ -1013,39 +825,48 @@ class PPO:
                 stats = dict(pg=pg.detach(), vf=vf.detach())
         return stats
 
+    def _grad_args(self, batch, idx, adv_norm):
+        """What ``PPOGrad.run`` takes from the trainer, in the one place that knows it: ``(args, inputs, outputs)``.
+        ``args``: the parameters' storage, read where it lies, then ``batch = (obs, act, logp_old, adv, ret)``;
+        ``inputs``: the minibatch's rows, the two normalisers and the loss's coefficients; ``outputs``: the three
+        ``.grad`` tensors and the stats, overwritten in place.  ``run`` and ``reduce`` take all three, ``run_part``
+        the first two."""
+        inputs = dict(idx=idx, adv_norm=adv_norm, obs_norm=self.actor.obs_norm, clip_eps=self.clip, vf_coef=self.vf_coef,
+                      ent_coef=self.ent_coef)
+        outputs = dict(grad_actor=self._grads[0], grad_critic=self._grads[1], grad_log_std=self._grads[2], stats=self._grad_stats)
+        return (*self._params, *batch), inputs, outputs
+
+    def _gradient(self, batch, idx, adv_norm):
+        """The minibatch's gradient into the parameters' ``.grad``: pbg_ppo_grad_run, two launches."""
+        args, inputs, outputs = self._grad_args(batch, idx, adv_norm)
+        self.grad.run(*args, **inputs, **outputs)
+
     def _update_hip(self, b: Batch) -> dict:
         """``update`` with the gradient from ``PPOGrad.run``: the same permutation, clipping and optimiser step; the
         parameters' storage is read where it lies and the three ``.grad`` tensors are overwritten in place."""
         T, n = self.steps, self.env.num_envs
         B, A = T * n, self.actor_dims[3]
-        obs, act = b.obs.reshape(B, -1), b.act.reshape(B, A)
-        logp_old, ret, adv = b.logp.reshape(B).float(), b.ret.reshape(B), b.adv.reshape(B)
+        adv = b.adv.reshape(B)
+        batch = (b.obs.reshape(B, -1), b.act.reshape(B, A), b.logp.reshape(B).float(), adv, b.ret.reshape(B))
         params = [self.actor_theta, self.critic_theta, self.log_std]
         for _ in range(self.epochs):
-            perm = torch.randperm(B, device=obs.device, generator=self._gen).view(self.minibatches, -1)
+            perm = torch.randperm(B, device=adv.device, generator=self._gen).view(self.minibatches, -1)
             for idx in perm:
                 adv_norm = None
                 if self.norm_adv:
                     a_mb = adv[idx]
                     adv_norm = torch.stack((a_mb.mean(), 1.0 / (a_mb.std() + 1e-8)))
-                self.grad.run(self.actor_theta.data, self.critic_theta.data, self.log_std.data, obs, act, logp_old, adv, ret,
-                              idx=idx, adv_norm=adv_norm, obs_norm=self.actor.obs_norm, clip_eps=self.clip,
-                              vf_coef=self.vf_coef, ent_coef=self.ent_coef, grad_actor=self.actor_theta.grad,
-                              grad_critic=self.critic_theta.grad, grad_log_std=self.log_std.grad, stats=self._grad_stats)
+                self._gradient(batch, idx, adv_norm)
                 if self.max_grad_norm:
                     torch.nn.utils.clip_grad_norm_(params, self.max_grad_norm)
                 self.opt.step()
         st = self._grad_stats.clone()   # the last minibatch's
         return dict(pg=st[0], vf=st[1], clipfrac=st[2], kl=st[3])
 
-    def _minibatch_opt(self, obs, act, logp_old, adv, ret, idx):
+    def _minibatch_opt(self, batch, idx):
         """One minibatch step as at most five launches of the library: pbg_adv_norm, pbg_ppo_grad_run (two),
         pbg_ppo_opt_step (two)."""
-        norm = adv_norm(adv, idx, out=self._adv_norm) if self.norm_adv else None
-        self.grad.run(self._params[0], self._params[1], self._params[2], obs, act, logp_old, adv, ret, idx=idx, adv_norm=norm,
-                      obs_norm=self.actor.obs_norm, clip_eps=self.clip, vf_coef=self.vf_coef, ent_coef=self.ent_coef,
-                      grad_actor=self._grads[0], grad_critic=self._grads[1], grad_log_std=self._grads[2],
-                      stats=self._grad_stats)
+        self._gradient(batch, idx, adv_norm(batch[3], idx, out=self._adv_norm) if self.norm_adv else None)
         self.adam.step(self._params, self._grads, self._lr_now, (0.9, 0.999), 1e-5, self.max_grad_norm, info=self._opt_info)
 
     def _schedule(self):
@@ -1057,11 +878,21 @@ class PPO:
         """This update's ``epochs`` permutations into ``_perm`` (``permutation="device"``: one fill)."""
         self.perm.fill(B, self.epochs, out=self._perm.view(self.epochs, B))
 
+    def _chain(self, batch, B):
+        """The ``epochs x minibatches`` chain of ``optimizer="hip"``, launches of the library alone: the schedule's,
+        with ``permutation="device"`` the permutation fill, then every minibatch of ``_perm``."""
+        self._schedule()
+        if self.perm is not None:
+            self._draw(B)
+        for e in range(self.epochs):
+            for idx in self._perm[e]:
+                self._minibatch_opt(batch, idx)
+
     def _update_opt(self, b: Batch) -> dict:
-        """``update`` with ``optimizer="hip"``: the permutations are ``_update_hip``'s (the same generator), every
-        minibatch is ``_minibatch_opt``.  With ``graph=True`` the ``epochs x minibatches`` chain is captured at the
-        first call and replayed from then on: the permutations and ``logp_old`` are written into the buffers the
-        graph reads, and every other pointer it baked (the rollout's trajectories, ``adv``, ``ret``, the normaliser)
+        """``update`` with ``optimizer="hip"``: ``logp_old`` and, with ``permutation="torch"``, the permutations
+        (``_update_hip``'s: the same generator) are written into the buffers ``_chain`` reads, and the chain runs.
+        With ``graph=True`` the chain is captured at the first call and replayed from then on, and every other pointer
+        it baked (the rollout's trajectories, ``adv``, ``ret``, the normaliser)
         is checked to be the one it was captured with: they are allocated once, so the check fires only if something
         outside the trainer moves them, and it raises rather than replaying on stale addresses.  (``VecEnv.rollout``
         keeps one set of trajectory buffers per ``(steps, trajectory)``: a rollout of the trainer's env with another
@@ -1073,54 +904,33 @@ class PPO:
         B, A = T * n, self.actor_dims[3]
         obs, act = b.obs.reshape(B, -1), b.act.reshape(B, A)
         ret, adv = b.ret.reshape(B), b.adv.reshape(B)
-        device_perm = self.permutation == "device"
+        batch = (obs, act, self._logp_old, adv, ret)
+        self._logp_old.copy_(b.logp.reshape(B))   # float64 -> float32, the rounding of ``.float()``
+        if self.perm is None:
+            for e in range(self.epochs):
+                torch.randperm(B, device=obs.device, generator=self._gen, out=self._perm[e].view(B))
         if not self.use_graph:
-            self._schedule()
-            if device_perm:
-                self._logp_old.copy_(b.logp.reshape(B))
-                self._draw(B)
-                for e in range(self.epochs):
-                    for idx in self._perm[e]:
-                        self._minibatch_opt(obs, act, self._logp_old, adv, ret, idx)
-            else:
-                logp_old = b.logp.reshape(B).float()
-                for _ in range(self.epochs):
-                    perm = torch.randperm(B, device=obs.device, generator=self._gen).view(self.minibatches, -1)
-                    for idx in perm:
-                        self._minibatch_opt(obs, act, logp_old, adv, ret, idx)
+            self._chain(batch, B)
             if self._capturing:   # graph="iteration": nothing may be read back inside the capture
                 return {}
-        else:
-            self._logp_old.copy_(b.logp.reshape(B))
-            if not device_perm:
-                for e in range(self.epochs):
-                    torch.randperm(B, device=obs.device, generator=self._gen, out=self._perm[e].view(B))
-            norm = self.actor.obs_norm
-            baked = tuple(t.data_ptr() for t in (obs, act, adv, ret) + (() if norm is None else norm[:2])) + \
-                (None if norm is None else norm[2],)
-            if self._graph is None:
-                # once eagerly what writes only outputs the chain overwrites before it reads them (the normaliser pair,
-                # the gradient, its stats): no kernel is launched for the first time inside the capture
-                idx = self._perm[0, 0]
-                self._schedule()   # it writes only the learning rate the chain's first launch writes again
-                self.grad.run(self._params[0], self._params[1], self._params[2], obs, act, self._logp_old, adv, ret, idx=idx,
-                              adv_norm=adv_norm(adv, idx, out=self._adv_norm) if self.norm_adv else None,
-                              obs_norm=norm, clip_eps=self.clip, vf_coef=self.vf_coef, ent_coef=self.ent_coef,
-                              grad_actor=self._grads[0], grad_critic=self._grads[1], grad_log_std=self._grads[2],
-                              stats=self._grad_stats)
-                with torch.cuda.device(obs.device):
-                    graph = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(graph):
-                        self._schedule()
-                        if device_perm:
-                            self._draw(B)
-                        for e in range(self.epochs):
-                            for idx in self._perm[e]:
-                                self._minibatch_opt(obs, act, self._logp_old, adv, ret, idx)
-                self._graph, self._baked = graph, baked
-            elif baked != self._baked:
-                raise _native.PbgError("PPO.update: a buffer the captured update reads has moved since the capture")
-            self._graph.replay()
+            return self._stats_now()
+        norm = self.actor.obs_norm
+        baked = tuple(t.data_ptr() for t in (obs, act, adv, ret) + (() if norm is None else norm[:2])) + \
+            (None if norm is None else norm[2],)
+        if self._graph is None:
+            # once eagerly what writes only outputs the chain overwrites before it reads them (the normaliser pair,
+            # the gradient, its stats): no kernel is launched for the first time inside the capture
+            idx = self._perm[0, 0]
+            self._schedule()   # it writes only the learning rate the chain's first launch writes again
+            self._gradient(batch, idx, adv_norm(adv, idx, out=self._adv_norm) if self.norm_adv else None)
+            with torch.cuda.device(obs.device):
+                graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graph):
+                    self._chain(batch, B)
+            self._graph, self._baked = graph, baked
+        elif baked != self._baked:
+            raise _native.PbgError("PPO.update: a buffer the captured update reads has moved since the capture")
+        self._graph.replay()
         return self._stats_now()
 
     _capturing = False
@@ -1293,15 +1103,21 @@ class ShardedPPO(PPO):
     def _make_ret_stats(self, n, dev):
         return RetStats(n, self.gamma, dev, n_slots=self.num_global // RetStats.TILE)
 
+    def _gather_slots(self, stats, first, count):
+        """The slots ``first .. first + count - 1`` of every rank's ``stats`` (an ``ObsStats`` or a ``RetStats``), one
+        all-gather of ``counts | sums`` as 8-byte words (bits kept), in rank order into the slots ``0 .. world * count - 1``
+        of this rank's: the global trainer's slots."""
+        counts, sums = stats.get_slots(first, count)
+        got = self._all_gather(torch.cat((counts.view(count, 1), sums.view(torch.int64)), dim=1)).view(self.world * count, -1)
+        stats.set_slots(0, got[:, 0].contiguous(), got[:, 1:].contiguous().view(torch.float64))
+
     def _scale_rewards(self, rew_traj, done_traj):
-        """``PPO._scale_rewards`` over the global envs: this rank's tiles at their global slots, one all-gather of the
-        ranks' slots (8-byte words, bits kept), then the finalize over all of them."""
+        """``PPO._scale_rewards`` over the global envs: this rank's tiles at their global slots, the ranks' slots
+        gathered, then the finalize over all of them."""
         rs, k = self.ret_stats, self.env.num_envs // RetStats.TILE
         rs.update(rew_traj, done_traj, slot_offset=self.rank * k)
         if self.world > 1:
-            counts, sums = rs.get_slots(self.rank * k, k)
-            got = self._all_gather(torch.cat((counts.view(k, 1), sums.view(torch.int64)), dim=1)).view(self.world * k, 3)
-            rs.set_slots(0, got[:, 0].contiguous(), got[:, 1:].contiguous().view(torch.float64))
+            self._gather_slots(rs, self.rank * k, k)
         rs.finalize()
         return rs.apply(rew_traj, out=self._rew_scaled, clip=self.reward_clip)
 
@@ -1312,29 +1128,23 @@ class ShardedPPO(PPO):
     def _share_views(self, block):
         return share_views(block, self._share, self._dtot)
 
-    def _minibatch_opt(self, obs, act, logp_old, adv, ret, idx):
-        """``PPO._minibatch_opt`` with the gradient as parts: this rank's workgroups, one all-gather, the reduction."""
-        norm = adv_norm(adv, idx, out=self._adv_norm) if self.norm_adv else None
-        kw = dict(idx=idx, adv_norm=norm, obs_norm=self.actor.obs_norm, clip_eps=self.clip, vf_coef=self.vf_coef,
-                  ent_coef=self.ent_coef)
-        args = (self._params[0], self._params[1], self._params[2], obs, act, logp_old, adv, ret)
-        if self.world == 1:
-            self.grad.run_part(*args, 0, self._G, self._part, self._part_stats, **kw)
-        else:
-            st, pt = self._share_views(self._send)
-            self.grad.run_part(*args, self._wg0, self._wgn, pt[:self._wgn], st[:self._wgn], **kw)
+    def _gradient(self, batch, idx, adv_norm):
+        """``PPO._gradient`` as parts: this rank's workgroups, one all-gather, the reduction."""
+        args, inputs, outputs = self._grad_args(batch, idx, adv_norm)
+        # world 1: every workgroup (shard_range's 0, G) straight into the reduction's input, no collective
+        st, pt = (self._part_stats, self._part) if self.world == 1 else (v[:self._wgn] for v in self._share_views(self._send))
+        self.grad.run_part(*args, self._wg0, self._wgn, pt, st, **inputs)
+        if self.world > 1:
             got = self._all_gather(self._send)
             for r in range(self.world):   # the pad rows of the narrower shares are dropped
                 off, cnt = self._shard_range(self._G, r, self.world)
                 st, pt = self._share_views(got[r])
                 self._part_stats[off:off + cnt].copy_(st[:cnt])
                 self._part[off:off + cnt].copy_(pt[:cnt])
-        self.grad.reduce(*args, self._G, self._part, self._part_stats, grad_actor=self._grads[0], grad_critic=self._grads[1],
-                         grad_log_std=self._grads[2], stats=self._grad_stats, **kw)
-        self.adam.step(self._params, self._grads, self._lr_now, (0.9, 0.999), 1e-5, self.max_grad_norm, info=self._opt_info)
+        self.grad.reduce(*args, self._G, self._part, self._part_stats, **inputs, **outputs)
 
     def update(self, b: Batch) -> dict:
-        """One gather of the shard's packed ``(obs | act | logp_old | adv | ret)`` columns, then ``PPO``'s
+        """One gather of the shard's packed ``(obs | act | logp_old | adv | ret)`` columns, then ``PPO``'s chain of
         ``epochs x minibatches`` steps on the global batch in the global row order ``t * num_global + e``."""
         from .distributed import gather_traj
         T, o, A = self.steps, self.actor_dims[0], self.actor_dims[3]
@@ -1350,20 +1160,12 @@ class ShardedPPO(PPO):
         self._logp_old.copy_(g[:, o + A])
         self._g_adv.copy_(g[:, o + A + 1])
         self._g_ret.copy_(g[:, o + A + 2])
-        self._schedule()
-        self._draw(B)
-        for e in range(self.epochs):
-            for idx in self._perm[e]:
-                self._minibatch_opt(self._g_obs, self._g_act, self._logp_old, self._g_adv, self._g_ret, idx)
+        self._chain((self._g_obs, self._g_act, self._logp_old, self._g_adv, self._g_ret), B)
         return self._stats_now()
 
     def _merge_slots(self):
-        """Every rank's used slots, gathered in rank order into this rank's object: the global trainer's slots."""
-        n = self.env.num_envs // 16
-        counts, sums = self.obs_stats.get_slots(0, n)
-        got = self._all_gather(torch.cat((counts.view(n, 1), sums.view(torch.int64)), dim=1))   # 8-byte words, bits kept
-        got = got.view(self.world * n, -1)
-        self.obs_stats.set_slots(0, got[:, 0].contiguous(), got[:, 1:].contiguous().view(torch.float64))
+        """Every rank's used observation slots into this rank's object."""
+        self._gather_slots(self.obs_stats, 0, self.env.num_envs // 16)
 
     def _iterate_once(self) -> dict:
         b = self.collect()

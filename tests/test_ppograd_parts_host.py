@@ -11,7 +11,7 @@ import pybulletgym_amd  # noqa: F401
 from pybulletgym_amd import _native
 from pybulletgym_amd.distributed import shard_range
 from pybulletgym_amd.policy import ObsStats
-from pybulletgym_amd.ppo import PPOGrad, ShardedPPO, share_block_bytes, share_views
+from pybulletgym_amd.ppo import AdamClip, Permutation, PPOGrad, RetStats, ShardedPPO, share_block_bytes, share_views
 
 PARTS = ("pbg_ppo_grad_geometry", "pbg_ppo_grad_run_part", "pbg_ppo_grad_reduce", "pbg_obs_stats_get_slots",
          "pbg_obs_stats_set_slots")
@@ -82,6 +82,31 @@ def test_the_host_twin_has_no_parts():
     for call in (lambda: g.geometry(16), lambda: g.run_part(*[None] * 12), lambda: g.reduce(*[None] * 11)):
         with pytest.raises(_native.PbgError, match="needs an open object on a GPU"):
             call()
+
+
+def test_a_host_twin_works_after_close_where_it_owns_no_native_object():
+    """``close`` destroys a native object.  The host twins of PPOGrad, AdamClip and Permutation own none (their state is
+    numpy arrays here), so closing them, twice, changes nothing; RetStats' host twin is a native object and refuses."""
+    r = np.random.default_rng(0)
+    g = PPOGrad((3, 4, 4, 1), 8)
+    batch = [r.standard_normal(s).astype(np.float32) for s in ((g.Da,), (g.Dc,), (1,), (8, 3), (8, 1), (8,), (8,), (8,))]
+    opt, perm, stats = AdamClip([5]), Permutation(0), RetStats(32, 0.99)
+    before = [a.copy() for a in g.run(*batch)]
+    for obj in (g, opt, perm, stats):
+        assert obj.host and obj.device is None
+        obj.close()
+        obj.close()
+        assert not obj._h
+    for a, b in zip(g.run(*batch), before):
+        assert a.tobytes() == b.tobytes()
+    p = [np.ones(5, np.float32)]
+    opt.step(p, [np.ones(5, np.float32)], 0.5)
+    assert opt.state()[2][0] == 1 and (p[0] < 1.0).all()
+    opt.reset()
+    assert opt.state()[2][0] == 0
+    assert sorted(perm.fill(7)[0]) == list(range(7)) and perm.counter == 1
+    with pytest.raises(_native.PbgError, match="closed"):
+        stats.reset()
 
 
 @pytest.mark.parametrize("W", (1, 2, 3))

@@ -9,7 +9,7 @@ import torch
 
 import pybulletgym_amd  # noqa: F401
 from pybulletgym_amd import _native
-from pybulletgym_amd.ppo import PPO, AdamClip, adv_norm
+from pybulletgym_amd.ppo import PPO, AdamClip, Permutation, PPOGrad, RetStats, adv_norm
 from pybulletgym_amd.vec_env import VecEnv
 
 import policies
@@ -254,6 +254,21 @@ def test_refused_argument_combinations():
         with pytest.raises(_native.PbgError):
             PPO(env, **dict(HP, **kw))
     env.close()
+
+
+@pytest.mark.parametrize("make,use", [
+    (lambda: PPOGrad((3, 4, 4, 1), 8, DEV), lambda o: o.geometry(8)),
+    (lambda: AdamClip([5], DEV), lambda o: o.reset()),
+    (lambda: Permutation(0, DEV), lambda o: o.fill(4)),
+    (lambda: RetStats(32, 0.99, DEV), lambda o: o.reset())], ids=["PPOGrad", "AdamClip", "Permutation", "RetStats"])
+def test_every_native_wrapper_closes_once_and_refuses_use_after_close(make, use):
+    obj = make()
+    use(obj)          # open: the call goes through
+    obj.close()
+    obj.close()       # twice is harmless
+    assert not obj._h
+    with pytest.raises(_native.PbgError, match="closed"):
+        use(obj)
 
 
 def test_the_graph_trainer_learns_to_balance_the_pendulum():
