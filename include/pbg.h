@@ -586,9 +586,11 @@ int pbg_gae_host(int T, int n, const float* rew_traj, const uint8_t* done_traj, 
 typedef struct pbg_ppo_grad pbg_ppo_grad;
 
 /* All pointers DEVICE memory of the object's GPU (pbg_ppo_grad_run) or HOST memory (pbg_ppo_grad_host); nothing
- * is copied or kept, the parameters are read where they lie.  Versioned by struct_size like pbg_rollout_io_t:
- * PBG_E_ARG for a size below the first version's (which ends with v_out), above the library's, or not a
- * multiple of 4. */
+ * is copied or kept, the parameters are read where they lie.  Versioned by struct_size like pbg_ppo_opt_io_t: the
+ * library accepts exactly its versions' sizes, the first version's (which ends with v_out, 176 bytes) and the one
+ * that appends value_old, gate, vf_clip and a pad (200 bytes); PBG_E_ARG for every other size: below the first
+ * version's, above the library's, or between the two.  A caller that passes the first version's size gets NULL / 0
+ * for the appended fields. */
 typedef struct {
   uint32_t struct_size;
   int batch_rows;            /* B >= 1 */
@@ -619,6 +621,11 @@ typedef struct {
                                 |ratio - 1| > c, mean_i(logp_old - logp) */
   float* logp_out;           /* [Bm] out, nullable: logp in minibatch order */
   float* v_out;              /* [Bm] out, nullable: v in minibatch order */
+  /* appended ("Value clipping and the KL gate" below) */
+  const float* value_old;    /* [B], nullable: the values the batch was collected under, indexed by batch row like ret */
+  const int32_t* gate;       /* [2], nullable: when set and gate[0] != 0 every launch returns at entry */
+  float vf_clip;             /* e > 0 when value_old is set */
+  int reserved2;             /* 0 */
 } pbg_ppo_grad_io_t;
 
 /* The object owns the reduction's device workspace for up to max_rows minibatch rows.  PBG_E_ARG (before any HIP
@@ -755,8 +762,10 @@ int pbg_adv_norm_host(int n_batch, int n_rows, const float* adv, const int64_t* 
 typedef struct pbg_ppo_opt pbg_ppo_opt;
 
 /* Pointers: DEVICE memory of the object's GPU (pbg_ppo_opt_step) or HOST memory (pbg_ppo_opt_host); entries at and
- * after n_blocks are ignored.  Versioned by struct_size like pbg_ppo_grad_io_t: PBG_E_ARG for a size that is neither the
- * first version's (which ends with bpow) nor the library's (which appends lr_ptr). */
+ * after n_blocks are ignored.  Versioned by struct_size like pbg_ppo_grad_io_t: PBG_E_ARG for a size that is none of
+ * the first version's (which ends with bpow, 328 bytes), the second's (which appends lr_ptr, 336) and the library's
+ * (which appends gate and a reserved word, 352).  344, the second version's size plus one pointer, stays refused as the
+ * second version's contract had it: the third version skips it. */
 typedef struct {
   uint32_t struct_size;
   int reserved;                                /* 0 */
@@ -775,6 +784,9 @@ typedef struct {
   /* appended ("Counter-based permutations and an on-device learning rate" below); a caller built with the struct
    * that ends with bpow passes its struct_size and gets NULL */
   const double* lr_ptr;                        /* [1], nullable: when set, the step uses *lr_ptr in place of lr */
+  /* appended ("Value clipping and the KL gate" below); an older caller gets NULL */
+  const int32_t* gate;                         /* [2], nullable: when set and gate[0] != 0 the step changes nothing */
+  uint64_t reserved2;                          /* 0 */
 } pbg_ppo_opt_io_t;
 
 /* PBG_E_ARG (before any HIP call) for n_blocks outside 1 .. 8, a size < 1, sizes or out NULL, device < 0; PBG_E_HIP
@@ -1004,6 +1016,49 @@ int pbg_ret_stats_get_carry(const pbg_ret_stats* s, double* carry_out, void* str
 int pbg_ret_stats_set_carry(pbg_ret_stats* s, const double* carry, void* stream);
 int pbg_ret_stats_get_scale(const pbg_ret_stats* s, float* scale_out, void* stream);
 int pbg_ret_stats_set_scale(pbg_ret_stats* s, const float* scale, void* stream);
+
+/* ---- Value clipping and the KL gate (appended; nothing above changes) ----
+ * The two knobs of the PPO2 update the gradient and the optimiser step lacked.
+ *
+ * Value clipping.  pbg_ppo_grad_io_t.value_old (float32 [B], indexed by batch row like ret) and vf_clip = e > 0.
+ * Per row, in float64 from the float32 v, ret_r and value_old_r:
+ *   vc = value_old_r + clamp(v - value_old_r, -e, +e)
+ *   u1 = (v - ret_r)^2;  u2 = (vc - ret_r)^2
+ *   the row's value-loss term = 1/2 max(u1, u2)                       (stats[1] is its mean)
+ *   dL/dv_i = vf_coef (u1 >= u2 ? (v - ret_r) : 0) / Bm               rounded once to float32
+ * The clipped branch carries no gradient: it can only win when v is outside the clip range, where vc does not depend
+ * on v.  Inside the range vc is taken as v itself, not as the rounded value_old_r + (v - value_old_r), so u2 == u1
+ * there whatever the magnitudes and the row keeps its derivative.  An exact tie u1 == u2 with v clamped takes the unclipped derivative; torch's `maximum` halves it there.
+ * With value_old NULL the function is the one above, the bits of stats[1] included.  v_out, the forward, every sum's
+ * order and the workspace are as above on both paths and in pbg_ppo_grad_host.  PBG_E_ARG (before any work) for a
+ * vf_clip that is not > 0 (a NaN included) when value_old is set.
+ *
+ * The KL gate.  `gate` is a caller-owned int32 [2] (DEVICE for the device entries, HOST for the host twins): gate[0] is
+ * "stopped", gate[1] the number of minibatch steps applied since the last reset.
+ *   pbg_ppo_gate_reset: both words to 0, one stream-ordered operation.
+ *   pbg_ppo_gate: one launch of one lane.  If gate[0] == 0: if stats[3] > kl_limit then gate[0] = 1, else
+ *     gate[1] += 1.  stats (DEVICE float64 [4]) is pbg_ppo_grad_run's, so stats[3] = mean(logp_old - logp) of the
+ *     float64 forward (Spinning Up's criterion).  A NaN stats[3] does not stop: the comparison is false.  kl_limit is
+ *     not validated.
+ *   pbg_ppo_gate_host: the same on HOST pointers, no GPU.
+ * PBG_E_ARG (before any HIP call) for a NULL pointer.
+ *
+ * What obeys it.  With pbg_ppo_grad_io_t.gate set and gate[0] != 0, the tile kernel of either path (pbg_ppo_grad_run
+ * and pbg_ppo_grad_run_part) returns at entry in every workgroup, before it touches the weights, the batch or idx,
+ * and the reduction returns at entry: grad_*, stats, logp_out, v_out, part_out and part_stats_out keep what they
+ * held.  With pbg_ppo_opt_io_t.gate set and gate[0] != 0, pbg_ppo_opt_step's first launch does not advance t, b1t,
+ * b2t and its second launch moves no parameter and no moment and leaves info.  pbg_ppo_grad_host and pbg_ppo_opt_host
+ * honour the gate the same way (after their argument checks): PBG_OK, outputs and state untouched.
+ *
+ * The gate's words are only ever written by pbg_ppo_gate and pbg_ppo_gate_reset, in launches of their own; every
+ * other launch only reads them, so no kernel reads a word its own launch writes, and there are no atomics.  A
+ * minibatch with the gate is pbg_adv_norm, the tiles, the reduction, pbg_ppo_gate, and the optimiser's two launches: a
+ * plain chain with no parallel branches and no conditional nodes, which captures as before.  The step whose
+ * stats[3] trips the gate is not applied.  After a stop the parameters are those after the last applied step, stats
+ * are the tripping minibatch's, and gate[1] says how many steps were applied. */
+int pbg_ppo_gate_reset(int32_t* gate, void* stream);
+int pbg_ppo_gate(const double* stats, double kl_limit, int32_t* gate, void* stream);
+int pbg_ppo_gate_host(const double* stats, double kl_limit, int32_t* gate);
 
 #ifdef __cplusplus
 }

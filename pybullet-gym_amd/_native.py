@@ -90,7 +90,8 @@ class PPOGradOpts(ctypes.Structure):
 
 
 class PPOGradIO(ctypes.Structure):
-    """pbg_ppo_grad_io_t (pbg_ppo_grad_run, pbg_ppo_grad_host): versioned by struct_size."""
+    """pbg_ppo_grad_io_t (pbg_ppo_grad_run, pbg_ppo_grad_host): versioned by struct_size.  The struct's first version,
+    which ends with v_out: the library keeps accepting it."""
     _fields_ = [("struct_size", ctypes.c_uint32), ("batch_rows", ctypes.c_int), ("mb_rows", ctypes.c_int),
                 ("reserved", ctypes.c_int), ("theta_actor", ctypes.c_void_p), ("theta_critic", ctypes.c_void_p),
                 ("log_std", ctypes.c_void_p), ("mean", ctypes.c_void_p), ("inv_std", ctypes.c_void_p),
@@ -102,7 +103,13 @@ class PPOGradIO(ctypes.Structure):
                 ("logp_out", ctypes.c_void_p), ("v_out", ctypes.c_void_p)]
 
     def __init__(self, **kw):
-        super().__init__(struct_size=ctypes.sizeof(PPOGradIO), **kw)
+        super().__init__(struct_size=ctypes.sizeof(type(self)), **kw)
+
+
+class PPOGradIO2(PPOGradIO):
+    """pbg_ppo_grad_io_t with the appended value clipping (value_old float32 [B], vf_clip) and KL gate (int32 [2])."""
+    _fields_ = [("value_old", ctypes.c_void_p), ("gate", ctypes.c_void_p), ("vf_clip", ctypes.c_float),
+                ("reserved2", ctypes.c_int)]
 
 
 PPO_OPT_MAX_BLOCKS = 8  # PBG_PPO_OPT_MAX_BLOCKS
@@ -129,6 +136,12 @@ class PPOOptIO(ctypes.Structure):
 class PPOOptIO2(PPOOptIO):
     """pbg_ppo_opt_io_t with the appended lr_ptr: a float64 [1] the step reads in place of lr (None: lr)."""
     _fields_ = [("lr_ptr", ctypes.c_void_p)]
+
+
+class PPOOptIO3(PPOOptIO2):
+    """pbg_ppo_opt_io_t with the appended KL gate: an int32 [2] whose first word, when not 0, makes the step a no-op.
+    The reserved word takes the struct to 352 bytes: 344 is a size the second version's contract refuses."""
+    _fields_ = [("gate", ctypes.c_void_p), ("reserved2", ctypes.c_uint64)]
 
 
 POLICY_MAX_DIM = 256  # PBG_POLICY_MAX_DIM: obs_dim, h1, h2
@@ -289,6 +302,12 @@ def lib():
         L.pbg_gae_trunc_host.argtypes = [I, I, P, P, P, P, P, D, D, P, P]
         for f in TRUNC_EXPORTED:
             getattr(L, f).restype = I
+    if hasattr(L, "pbg_ppo_gate"):  # value clipping and the KL gate
+        L.pbg_ppo_gate_reset.argtypes = [P, P]
+        L.pbg_ppo_gate.argtypes = [P, ctypes.c_double, P, P]
+        L.pbg_ppo_gate_host.argtypes = [P, ctypes.c_double, P]
+        for f in PPO_GATE_EXPORTED:
+            getattr(L, f).restype = I
     if hasattr(L, "pbg_ret_stats_create"):  # reward scaling by a running std of the discounted return
         D, F = ctypes.c_double, ctypes.c_float
         L.pbg_ret_stats_create.argtypes = [I, I, I, D, ctypes.POINTER(H)]
@@ -341,13 +360,14 @@ RET_STATS_EXPORTED = ("pbg_ret_stats_create", "pbg_ret_stats_destroy", "pbg_ret_
                       "pbg_ret_stats_apply", "pbg_ret_stats_reset", "pbg_ret_stats_get_slots", "pbg_ret_stats_set_slots",
                       "pbg_ret_stats_get_totals", "pbg_ret_stats_set_totals", "pbg_ret_stats_get_carry",
                       "pbg_ret_stats_set_carry", "pbg_ret_stats_get_scale", "pbg_ret_stats_set_scale")
+PPO_GATE_EXPORTED = ("pbg_ppo_gate_reset", "pbg_ppo_gate", "pbg_ppo_gate_host")
 EXPORTED =("pbg_create", "pbg_create_debug", "pbg_create_ex", "pbg_create_v2", "pbg_precision",
             "pbg_default_sim_params", "pbg_get_sim_params",
             "pbg_destroy", "pbg_info", "pbg_reset", "pbg_step", "pbg_step_ex",
             "pbg_get_state", "pbg_set_state", "pbg_pack_record_sizes", "pbg_pack", "pbg_sample_actions",
             "pbg_debug_poison", "pbg_last_error") + POLICY_EXPORTED + POPULATION_EXPORTED + OBS_NORM_EXPORTED + \
     ACTION_NOISE_EXPORTED + PPO_GRAD_EXPORTED + PPO_OPT_EXPORTED + PERM_EXPORTED + PPO_GRAD_EX_EXPORTED + PPO_PARTS_EXPORTED + \
-    TRUNC_EXPORTED + RET_STATS_EXPORTED
+    TRUNC_EXPORTED + RET_STATS_EXPORTED + PPO_GATE_EXPORTED
 
 
 def check(rc: int, what: str):

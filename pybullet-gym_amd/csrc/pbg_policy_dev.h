@@ -424,11 +424,27 @@ inline void host_layer64(const float* W, const float* b, int K, int H, bool relu
     for (int j = 0; j < H; j++) y[j] = y[j] < 0.0 ? 0.0 : y[j];
 }
 
-// The critic's row: dL/dv; *vf takes the row's term of the value loss.
-__host__ __device__ __forceinline__ float ppo_critic_row(float v, float ret, double vf_coef, double inv_bm, double* vf) {
+// The critic's row: dL/dv; *vf takes the row's term of the value loss.  value_old_r NULL: the plain squared error.
+// Otherwise pbg.h "Value clipping" with e = vf_clip: the larger of the squared errors of v and of v clamped to
+// *value_old_r +- e, and the derivative of the unclipped one where it is the larger or the two tie, else zero.
+__host__ __device__ __forceinline__ float ppo_critic_row(float v, float ret, const float* value_old_r, double e, double vf_coef,
+                                                         double inv_bm, double* vf) {
   const double d = (double)v - (double)ret;
-  *vf = 0.5 * d * d;
-  return (float)(vf_coef * d * inv_bm);
+  if (!value_old_r) {
+    *vf = 0.5 * d * d;
+    return (float)(vf_coef * d * inv_bm);
+  }
+  {
+#pragma clang fp contract(off)
+    const double vo = (double)*value_old_r;
+    const double dv = (double)v - vo;
+    const double vc = dv < -e ? vo - e : (dv > e ? vo + e : (double)v);  // inside the range v itself: u2 == u1 exactly
+    const double dc = vc - (double)ret;
+    const double u1 = d * d, u2 = dc * dc;
+    const bool own = u1 >= u2;
+    *vf = 0.5 * (own ? u1 : u2);
+    return own ? (float)(vf_coef * d * inv_bm) : 0.f;
+  }
 }
 
 // pbg.h's advantage scan for env e, host and device (pbg_actnoise.hip: pbg_gae; pbg_trunc.hip: pbg_gae_trunc): float64,

@@ -213,6 +213,7 @@ __global__ __launch_bounds__(PB) void ppograd_tiles_kernel(const Args a) {
   __shared__ double inv_sig[NA_MAX];
   __shared__ double sstat[4 * PT];
   const Planes L{bX, bH1, bH2, bE, bD, bD2};
+  if (a.gate && a.gate[0] != 0) return;  // stopped: uniform over the launch, nothing read or written
   const int tid = threadIdx.x, A = a.A;
   const Weights Pa = weights_at(a.theta_a, a.obs_dim, a.h1, a.h2, A);
   const Weights Pc = weights_at(a.theta_c, a.obs_dim, a.h1, a.h2, 1);
@@ -287,7 +288,8 @@ __global__ __launch_bounds__(PB) void ppograd_tiles_kernel(const Args a) {
       if (tid < rows) {
         const float v = bD[tid];
         double vf;
-        dv = ppo_critic_row(v, a.ret[r], (double)a.vf_coef, inv_bm, &vf);
+        dv = ppo_critic_row(v, a.ret[r], a.value_old ? a.value_old + r : nullptr, (double)a.vf_clip, (double)a.vf_coef, inv_bm,
+                            &vf);
         st1 += vf;
         if (a.v_out) a.v_out[row0 + tid] = v;
       }
@@ -318,7 +320,9 @@ __global__ __launch_bounds__(PB) void ppograd_tiles_kernel(const Args a) {
 __global__ __launch_bounds__(256) void ppograd_reduce_kernel(const float* __restrict__ part, const double* __restrict__ part_stats,
                                                              int G, int Da, int Dc, int Dtot, float ent_coef, int Bm,
                                                              float* __restrict__ grad_actor, float* __restrict__ grad_critic,
-                                                             float* __restrict__ grad_log_std, double* __restrict__ stats) {
+                                                             float* __restrict__ grad_log_std, double* __restrict__ stats,
+                                                             const int32_t* __restrict__ gate) {
+  if (gate && gate[0] != 0) return;  // stopped: the outputs keep what they held
   const int d = blockIdx.x * 256 + threadIdx.x;
   if (d < Dtot) {
     double s = 0.0;
@@ -344,7 +348,9 @@ int check_io(const char* who, const pbg_ppo_grad_io_t* uio, pbg_ppo_grad_io_t* i
     return pbg::capi_fail(PBG_E_ARG, msg);
   }
   constexpr uint32_t v1_size = (uint32_t)(offsetof(pbg_ppo_grad_io_t, v_out) + sizeof(float*));
-  if (uio->struct_size < v1_size || uio->struct_size > (uint32_t)sizeof(pbg_ppo_grad_io_t) || uio->struct_size % 4u != 0u) {
+  // the two versions: the one that ends with v_out and this library's, which appends value_old, gate and vf_clip (NULL,
+  // NULL and 0 for the first)
+  if (uio->struct_size != v1_size && uio->struct_size != (uint32_t)sizeof(pbg_ppo_grad_io_t)) {
     snprintf(msg, sizeof(msg), "%s: io->struct_size %u is not a pbg_ppo_grad_io_t size", who, uio->struct_size);
     return pbg::capi_fail(PBG_E_ARG, msg);
   }
@@ -368,6 +374,10 @@ int check_io(const char* who, const pbg_ppo_grad_io_t* uio, pbg_ppo_grad_io_t* i
   }
   if (!(io->clip_eps >= 0.f)) {
     snprintf(msg, sizeof(msg), "%s: clip_eps must be >= 0", who);
+    return pbg::capi_fail(PBG_E_ARG, msg);
+  }
+  if (io->value_old && !(io->vf_clip > 0.f)) {
+    snprintf(msg, sizeof(msg), "%s: vf_clip must be > 0 when value_old is given", who);
     return pbg::capi_fail(PBG_E_ARG, msg);
   }
   return PBG_OK;
@@ -447,6 +457,7 @@ int launch_tiles(const pbg_ppo_grad* g, const pbg_ppo_grad_io_t& io, int wg0, in
   a.wg0 = wg0; a.G = G;
   a.part = part; a.part_stats = part_stats;
   a.logp_out = io.logp_out; a.v_out = io.v_out;
+  a.value_old = io.value_old; a.gate = io.gate; a.vf_clip = io.vf_clip;
   const bool reg = g->obs_dim <= 64 && g->h1 <= 64 && g->h2 <= 64;
   int e;
   if (g->path == PBG_PPO_GRAD_MFMA) {
@@ -464,7 +475,7 @@ int launch_tiles(const pbg_ppo_grad* g, const pbg_ppo_grad_io_t& io, int wg0, in
 int launch_reduce(const pbg_ppo_grad* g, const pbg_ppo_grad_io_t& io, int G, const float* part, const double* part_stats,
                   hipStream_t s) {
   hipLaunchKernelGGL(ppograd_reduce_kernel, dim3((unsigned)((g->Dtot + 255) / 256)), dim3(256), 0, s, part, part_stats, G, g->Da,
-                     g->Dc, g->Dtot, io.ent_coef, io.mb_rows, io.grad_actor, io.grad_critic, io.grad_log_std, io.stats);
+                     g->Dc, g->Dtot, io.ent_coef, io.mb_rows, io.grad_actor, io.grad_critic, io.grad_log_std, io.stats, io.gate);
   const int e = (int)hipGetLastError();
   return e ? hip_fail(e, "ppograd_reduce_kernel launch") : PBG_OK;
 }
@@ -577,6 +588,7 @@ int pbg_ppo_grad_host(int obs_dim, int h1, int h2, int act_dim, const pbg_ppo_gr
     for (int i = 0; i < Bm; i++)
       if (io.idx[i] < 0 || io.idx[i] >= (int64_t)io.batch_rows)
         return pbg::capi_fail(PBG_E_ARG, "pbg_ppo_grad_host: an index is outside 0 .. batch_rows - 1");
+  if (io.gate && io.gate[0] != 0) return PBG_OK;  // stopped: the outputs keep what they held
   const int Da = param_count(obs_dim, h1, h2, A), Dc = param_count(obs_dim, h1, h2, 1);
   double* acc = (double*)calloc((size_t)Da + Dc + A, sizeof(double));
   if (!acc) return pbg::capi_fail(PBG_E_NOMEM, "pbg_ppo_grad_host: out of host memory");
@@ -623,7 +635,8 @@ int pbg_ppo_grad_host(int obs_dim, int h1, int h2, int act_dim, const pbg_ppo_gr
       } else {
         double vf;
         const float v = dy[0];
-        dy[0] = ppo_critic_row(v, io.ret[r], (double)io.vf_coef, inv_bm, &vf);
+        dy[0] = ppo_critic_row(v, io.ret[r], io.value_old ? io.value_old + r : nullptr, (double)io.vf_clip, (double)io.vf_coef,
+                               inv_bm, &vf);
         st[1] += vf;
         if (io.v_out) io.v_out[i] = v;
       }

@@ -36,6 +36,9 @@ struct Args {
   float* part;        // [gridDim.x, Dtot]: row i is block i's
   double* part_stats; // [gridDim.x, 4]
   float *logp_out, *v_out;
+  const float* value_old;  // [B], nullable: value clipping with vf_clip
+  const int32_t* gate;     // [2], nullable: gate[0] != 0 ends every workgroup at entry
+  float vf_clip;
 };
 
 // The matrix-core path's tile kernel (pbg_ppograd_mfma.hip) for the `count` workgroups a.wg0 .. a.wg0 + count - 1 on

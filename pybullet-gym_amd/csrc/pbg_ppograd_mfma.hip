@@ -372,7 +372,8 @@ __device__ __forceinline__ void net_pass(const Args& a, const Weights& P, const 
         if (tid < rows) {
           const float v = L.D[tid];
           double vf;
-          dv = ppo_critic_row(v, a.ret[r], (double)a.vf_coef, inv_bm, &vf);
+          const float* vo = karg()->value_old;
+          dv = ppo_critic_row(v, a.ret[r], vo ? vo + r : nullptr, (double)karg()->vf_clip, (double)a.vf_coef, inv_bm, &vf);
           rs.st1 += vf;
           if (a.v_out) a.v_out[row0 + tid] = v;
         }
@@ -459,6 +460,7 @@ __global__ __launch_bounds__(PB) void ppograd_mfma_kernel(const Args a) {
   Planes L;
   L.X = plane; L.H1 = plane + PD * PT; L.H2 = plane + 2 * PD * PT; L.E = plane + 3 * PD * PT; L.F = plane + 4 * PD * PT;
   L.D = plane + 5 * PD * PT; L.D2 = L.D + NA_MAX * PT;
+  if (a.gate && a.gate[0] != 0) return;  // stopped: uniform over the launch, nothing read or written
   const int tid = threadIdx.x, A = a.A;
   const Weights Pa = weights_at(a.theta_a, a.obs_dim, a.h1, a.h2, A);
   const Weights Pc = weights_at(a.theta_c, a.obs_dim, a.h1, a.h2, 1);

@@ -2,7 +2,8 @@
 // step"): the advantage normaliser's (shift, scale) pair as one launch (pbg_adv_norm, pbg_adv_norm_host) and Adam
 // with global-norm gradient clipping over up to 8 flat float32 blocks as two launches with its moments, its step
 // count and the running powers of the betas on the device (pbg_ppo_opt_*, pbg_ppo_opt_host), its learning rate
-// optionally read from device memory (io.lr_ptr; pbg_perm.hip's pbg_ppo_lr_linear writes one).
+// optionally read from device memory (io.lr_ptr; pbg_perm.hip's pbg_ppo_lr_linear writes one).  Both launches of the
+// step obey the KL gate (io.gate; include/pbg.h "Value clipping and the KL gate"), which pbg_ppogate.hip's launches write.
 //
 // Every sum is float64 in the order pbg.h states, every per-element expression one __host__ __device__ function
 // compiled with contraction off, so the host twins give the device's bits.  (The optimiser's summed squares are
@@ -152,6 +153,7 @@ struct OptArgs {
   double lr, beta1, beta2, eps, max_grad_norm;
   double* info;     // [2], nullable
   const double* lr_ptr;  // nullable: launch 2 reads the learning rate here instead of lr
+  const int32_t* gate;   // nullable: gate[0] != 0 makes both launches leave everything as it is
 };
 
 // the block of workgroup `wg` and its fields, by selects: no indexed access into the argument struct
@@ -177,6 +179,7 @@ __device__ __forceinline__ Mine mine(const OptArgs& a, int wg) {
 // launch reads nowhere else and the next launch reads advanced
 __global__ __launch_bounds__(OB) void ppoopt_sumsq_kernel(OptArgs a) {
   __shared__ double sh[OB];
+  if (a.gate && a.gate[0] != 0) return;  // stopped: uniform over the launch; the state word does not advance
   const Mine b = mine(a, (int)blockIdx.x);
   const size_t groups = (b.size + 3) / 4, stride = (size_t)b.G * OB;
   double s = 0.0;
@@ -211,6 +214,7 @@ __global__ __launch_bounds__(OB) void ppoopt_sumsq_kernel(OptArgs a) {
 
 // launch 2: every lane re-adds the partials in ascending order, then updates its elements
 __global__ __launch_bounds__(OB) void ppoopt_step_kernel(OptArgs a) {
+  if (a.gate && a.gate[0] != 0) return;  // stopped: no parameter, no moment and not info
   const int P = a.wg0[a.n_blocks];
   double sumsq = 0.0;
   for (int i = 0; i < P; i++) sumsq += a.partial[i];
@@ -282,8 +286,10 @@ int check_io(const char* who, const pbg_ppo_opt_io_t* uio, int n_blocks, pbg_ppo
     return pbg::capi_fail(PBG_E_ARG, msg);
   }
   constexpr uint32_t v1_size = (uint32_t)(offsetof(pbg_ppo_opt_io_t, bpow) + sizeof(double*));
-  // the two versions: the one that ends with bpow and this library's, which appends lr_ptr (NULL for the first)
-  if (uio->struct_size != v1_size && uio->struct_size != (uint32_t)sizeof(pbg_ppo_opt_io_t)) {
+  constexpr uint32_t v2_size = (uint32_t)(offsetof(pbg_ppo_opt_io_t, lr_ptr) + sizeof(double*));
+  // the three versions: the one that ends with bpow, the one that appends lr_ptr and this library's, which appends gate
+  // and a reserved word (NULL for what a version lacks); the size between the last two stays refused
+  if (uio->struct_size != v1_size && uio->struct_size != v2_size && uio->struct_size != (uint32_t)sizeof(pbg_ppo_opt_io_t)) {
     snprintf(msg, sizeof(msg), "%s: io->struct_size %u is not a pbg_ppo_opt_io_t size", who, uio->struct_size);
     return pbg::capi_fail(PBG_E_ARG, msg);
   }
@@ -430,6 +436,7 @@ int pbg_ppo_opt_step(pbg_ppo_opt* o, const pbg_ppo_opt_io_t* uio, void* stream) 
   a.lr = io.lr; a.beta1 = io.beta1; a.beta2 = io.beta2; a.eps = io.eps; a.max_grad_norm = io.max_grad_norm;
   a.info = io.info;
   a.lr_ptr = io.lr_ptr;
+  a.gate = io.gate;
   DeviceGuard dg(o->device);
   const unsigned G = (unsigned)o->wg0[o->n_blocks];
   hipLaunchKernelGGL(ppoopt_sumsq_kernel, dim3(G), dim3(OB), 0, (hipStream_t)stream, a);
@@ -470,6 +477,7 @@ int pbg_ppo_opt_host(int n_blocks, const int64_t* sizes, const pbg_ppo_opt_io_t*
   for (int b = 0; b < n_blocks; b++)
     if (!io.m[b] || !io.v[b]) return pbg::capi_fail(PBG_E_ARG, "pbg_ppo_opt_host: a block's m or v is NULL");
   if (!io.t || !io.bpow) return pbg::capi_fail(PBG_E_ARG, "pbg_ppo_opt_host: t or bpow is NULL");
+  if (io.gate && io.gate[0] != 0) return PBG_OK;  // stopped: the parameters, the state and info keep what they held
   // launch 1: the partials in the device's geometry
   double sumsq = 0.0;
   double lanes[OB];

@@ -13,10 +13,13 @@ the whole update as one captured graph.  The collection half of an iteration has
 ``lr_linear`` (pbg_ppo_lr_linear) writes a scheduled learning rate that ``AdamClip.step`` reads from device memory, and
 with both an iteration can be one captured graph (``PPO(graph="iteration")``).  ``RetStats`` (pbg_ret_stats, include/pbg.h
 "Return statistics") keeps a running standard deviation of the discounted return on the device and scales the rewards
-``gae`` sees by it (``PPO(reward_norm=True)``): three launches more, inside the captured iteration too.
+``gae`` sees by it (``PPO(reward_norm=True)``): three launches more, inside the captured iteration too.  ``PPOGrad.run(...,
+value_old=, vf_clip=)`` is PPO2's clipped value loss inside the gradient's kernels, and ``KLGate`` (pbg_ppo_gate, include/pbg.h
+"Value clipping and the KL gate") an early stop of the update that lives on the device: one more launch per minibatch writes
+a word that the gradient's and the optimiser's launches read and obey (``PPO(vf_clip=, target_kl=)``).
 
 Who owns what.  ``policy._NativeObject`` is the base of every wrapper here (``PPOGrad``, ``AdamClip``, ``Permutation``,
-``RetStats``): the handle, ``close``, the closed guard, the device, and ``_ptr`` / ``_new`` / ``_launch``, which are
+``RetStats``, ``KLGate``): the handle, ``close``, the closed guard, the device, and ``_ptr`` / ``_new`` / ``_launch``, which are
 ``policy.check_array`` / ``new_array`` / ``launch`` on the object's side (its GPU, or the host twin's numpy arrays).  The
 free functions ``gae``, ``adv_norm`` and ``lr_linear`` call the same three directly.  In the trainer ``PPO._grad_args`` is
 the one place that knows what ``PPOGrad.run`` takes, ``PPO._gradient`` the one call of it (``ShardedPPO._gradient``: of
@@ -149,9 +152,10 @@ class PPOGrad(_NativeObject):
         return tuple(self._new(n, dt) if t is None else t for t, n, dt in given)
 
     def _io(self, who, theta_actor, theta_critic, log_std, obs, act, logp_old, adv, ret, idx, rows, adv_norm, obs_norm, clip_eps,
-            vf_coef, ent_coef, out, logp_out, v_out):
+            vf_coef, ent_coef, out, logp_out, v_out, value_old=None, vf_clip=None, gate=None):
         """The checked pbg_ppo_grad_io_t of ``run``, ``run_part`` and ``reduce``.  ``out``: the four output arrays
-        (``_outputs``), or four ``None`` for ``run_part``, which writes no gradient."""
+        (``_outputs``), or four ``None`` for ``run_part``, which writes no gradient.  The struct's first version while
+        neither ``value_old`` nor ``gate`` is given."""
         o, h1, h2, A = self.dims
         f32, f64 = np.float32, np.float64
         if getattr(obs, "ndim", 0) != 2:
@@ -167,6 +171,8 @@ class PPOGrad(_NativeObject):
                   ("grad_log_std", out[2], (A,), f32, True), ("stats", out[3], (4,), f64, True),
                   ("idx", idx, (Bm,), np.int64, True), ("adv_norm", adv_norm, (2,), f32, True), ("mean", mean, (o,), f32, True),
                   ("inv_std", inv_std, (o,), f32, True), ("logp_out", logp_out, (Bm,), f32, True), ("v_out", v_out, (Bm,), f32, True))
+        if value_old is not None or gate is not None:
+            arrays += (("value_old", value_old, (B,), f32, True), ("gate", gate, (2,), np.int32, True))
         at, dev = (self, who), self.device   # _ptr's check, without a call in between: eighteen pointers per minibatch
         p = {name: None if t is None and optional else check_array(t, at, name, shape, dt, dev)
              for name, t, shape, dt, optional in arrays}
@@ -174,22 +180,32 @@ class PPOGrad(_NativeObject):
             raise _native.PbgError(f"PPOGrad.{who}: {Bm} minibatch rows outside 1 .. max_rows = {self.max_rows} (or the batch's {B})")
         if (mean is None) != (inv_std is None):
             raise _native.PbgError(f"PPOGrad.{who}: obs_norm needs both mean and inv_std")
-        return _native.PPOGradIO(batch_rows=B, mb_rows=Bm, clip=float(clip), clip_eps=float(clip_eps), vf_coef=float(vf_coef),
-                                 ent_coef=float(ent_coef), **p)
+        if (value_old is None) != (vf_clip is None):
+            raise _native.PbgError(f"PPOGrad.{who}: value_old and vf_clip go together (both or neither)")
+        IO, more = _native.PPOGradIO, {}
+        if value_old is not None or gate is not None:
+            if not hasattr(_native.lib(), "pbg_ppo_gate"):
+                raise _native.PbgError(f"{_native.LIB_PATH} has no pbg_ppo_gate: a build without value clipping and the KL gate")
+            IO, more = _native.PPOGradIO2, dict(vf_clip=0.0 if vf_clip is None else float(vf_clip))
+        return IO(batch_rows=B, mb_rows=Bm, clip=float(clip), clip_eps=float(clip_eps), vf_coef=float(vf_coef),
+                  ent_coef=float(ent_coef), **p, **more)
 
     def run(self, theta_actor, theta_critic, log_std, obs, act, logp_old, adv, ret, idx=None, rows=None, adv_norm=None,
             obs_norm=None, clip_eps: float = 0.2, vf_coef: float = 0.5, ent_coef: float = 0.0, grad_actor=None,
-            grad_critic=None, grad_log_std=None, stats=None, logp_out=None, v_out=None):
+            grad_critic=None, grad_log_std=None, stats=None, logp_out=None, v_out=None, value_old=None, vf_clip=None, gate=None):
         """``(grad_actor [Da], grad_critic [Dc], grad_log_std [A], stats float64 [4])`` of the minibatch ``idx`` (int64
         ``[Bm]`` rows of the batch; ``None``: the first ``rows`` rows, default all) of the batch ``obs [B, obs_dim]``,
         ``act [B, A]``, ``logp_old``, ``adv``, ``ret`` ``[B]``: contiguous float32 tensors on the object's GPU (numpy
         arrays on the host).  ``adv_norm``: float32 ``[2]`` (shift, scale) or ``None``; ``obs_norm``: ``(mean, inv_std,
         clip)`` or ``None``.  The outputs are written into the given tensors, or into new ones.  ``stats``: pg loss, vf
         loss, clipped fraction, mean(logp_old - logp).  ``logp_out``, ``v_out``: optional float32 ``[Bm]``.  The indices
-        are not validated on a GPU."""
+        are not validated on a GPU.  ``value_old`` (float32 ``[B]``, the values the batch was collected under) with
+        ``vf_clip > 0``: PPO2's clipped value loss (include/pbg.h "Value clipping").  ``gate``: an int32 ``[2]`` array
+        (``KLGate.gate``); while its first word is not 0 both launches return at entry and every output keeps what it
+        held."""
         out = self._outputs(grad_actor, grad_critic, grad_log_std, stats)
         io = self._io("run", theta_actor, theta_critic, log_std, obs, act, logp_old, adv, ret, idx, rows, adv_norm, obs_norm,
-                      clip_eps, vf_coef, ent_coef, out, logp_out, v_out)
+                      clip_eps, vf_coef, ent_coef, out, logp_out, v_out, value_old, vf_clip, gate)
         if self.host:
             self._launch("pbg_ppo_grad_host", *self.dims, ctypes.byref(io))
         else:
@@ -214,7 +230,7 @@ class PPOGrad(_NativeObject):
 
     def run_part(self, theta_actor, theta_critic, log_std, obs, act, logp_old, adv, ret, wg_first, wg_count, part_out,
                  part_stats_out, idx=None, rows=None, adv_norm=None, obs_norm=None, clip_eps: float = 0.2, vf_coef: float = 0.5,
-                 ent_coef: float = 0.0, logp_out=None, v_out=None):
+                 ent_coef: float = 0.0, logp_out=None, v_out=None, value_old=None, vf_clip=None, gate=None):
         """``run``'s tile launch for the workgroups ``wg_first .. wg_first + wg_count - 1`` of the minibatch's ``G``
         (``geometry``): their partials into ``part_out`` (float32 ``[wg_count, Dtot]``) and ``part_stats_out`` (float64
         ``[wg_count, 4]``), contiguous tensors (or row ranges of ones) on the object's GPU.  No gradient is written;
@@ -222,7 +238,7 @@ class PPOGrad(_NativeObject):
         arguments and their checks are ``run``'s."""
         h = self._parts("run_part")
         io = self._io("run_part", theta_actor, theta_critic, log_std, obs, act, logp_old, adv, ret, idx, rows, adv_norm, obs_norm,
-                      clip_eps, vf_coef, ent_coef, (None,) * 4, logp_out, v_out)
+                      clip_eps, vf_coef, ent_coef, (None,) * 4, logp_out, v_out, value_old, vf_clip, gate)
         wg_first, wg_count = int(wg_first), int(wg_count)
         G, dtot = self.geometry(io.mb_rows)
         if wg_first < 0 or wg_count < 0 or wg_first + wg_count > G:
@@ -233,7 +249,8 @@ class PPOGrad(_NativeObject):
 
     def reduce(self, theta_actor, theta_critic, log_std, obs, act, logp_old, adv, ret, G, part, part_stats, idx=None, rows=None,
                adv_norm=None, obs_norm=None, clip_eps: float = 0.2, vf_coef: float = 0.5, ent_coef: float = 0.0, grad_actor=None,
-               grad_critic=None, grad_log_std=None, stats=None, logp_out=None, v_out=None):
+               grad_critic=None, grad_log_std=None, stats=None, logp_out=None, v_out=None, value_old=None, vf_clip=None,
+               gate=None):
         """``run``'s reduction over the ``G`` partials of ``part`` (float32 ``[G, Dtot]``) and ``part_stats`` (float64
         ``[G, 4]``): ``(grad_actor, grad_critic, grad_log_std, stats)`` as ``run`` returns them.  ``G`` must be
         ``geometry``'s for the minibatch; the other arguments and their checks are ``run``'s (of them the launch reads
@@ -241,7 +258,7 @@ class PPOGrad(_NativeObject):
         h = self._parts("reduce")
         out = self._outputs(grad_actor, grad_critic, grad_log_std, stats)
         io = self._io("reduce", theta_actor, theta_critic, log_std, obs, act, logp_old, adv, ret, idx, rows, adv_norm, obs_norm,
-                      clip_eps, vf_coef, ent_coef, out, logp_out, v_out)
+                      clip_eps, vf_coef, ent_coef, out, logp_out, v_out, value_old, vf_clip, gate)
         G = int(G)
         Gq, dtot = self.geometry(io.mb_rows)
         if G != Gq:
@@ -298,13 +315,15 @@ class AdamClip(_NativeObject):
         _native.check(L.pbg_ppo_opt_create(index, len(self.sizes), self._sizes, ctypes.byref(h)), "pbg_ppo_opt_create")
         self._h = h
 
-    def step(self, params, grads, lr, betas=(0.9, 0.999), eps: float = 1e-8, max_grad_norm: float = 0.0, info=None):
+    def step(self, params, grads, lr, betas=(0.9, 0.999), eps: float = 1e-8, max_grad_norm: float = 0.0, info=None, gate=None):
         """One step on ``params`` (updated in place) with ``grads``: sequences of contiguous float32 ``[sizes[b]]``
         tensors on the object's GPU (numpy arrays on the host).  ``max_grad_norm`` 0 (or None): no clipping.  ``info``:
         optional float64 ``[2]`` that receives the gradient's global norm and the clipping coefficient.  ``lr``: a
         float, a launch argument like the other scalars (a captured step keeps the value it was captured with), or a
         float64 ``[1]`` tensor on the object's GPU (a numpy ``[1]`` array on the host) that the step reads where it
-        lies: the bits of the same value passed as a float, and a captured step follows the tensor."""
+        lies: the bits of the same value passed as a float, and a captured step follows the tensor.  ``gate``: an int32
+        ``[2]`` array (``KLGate.gate``); while its first word is not 0 the step changes nothing: no parameter, no moment,
+        not the step count and not ``info``."""
         h = self._open("step")
         params, grads = list(params), list(grads)
         lr_t = lr if isinstance(lr, (np.ndarray, torch.Tensor)) else None
@@ -321,6 +340,9 @@ class AdamClip(_NativeObject):
         if lr_t is not None:
             _need_perm()
             IO, kw["lr_ptr"] = _native.PPOOptIO2, self._ptr(lr_t, "step", "lr", (1,), np.float64)
+        if gate is not None:
+            _need_gate()
+            IO, kw["gate"] = _native.PPOOptIO3, self._ptr(gate, "step", "gate", (2,), np.int32)
         if self.host:
             io = IO(m=[t.ctypes.data for t in self._m], v=[t.ctypes.data for t in self._v], t=self._t.ctypes.data,
                     bpow=self._bpow.ctypes.data, **kw)
@@ -424,6 +446,44 @@ def lr_linear(it, n_total: int, lr0: float, out=None):
            check_array(it, "lr_linear", "it", (1,), np.uint32 if dev is None else np.int32, dev), n_total, float(lr0),
            check_array(out, "lr_linear", "out", (1,), np.float64, dev))
     return out
+
+
+def _need_gate():
+    if not hasattr(_native.lib(), "pbg_ppo_gate"):
+        raise _native.PbgError(f"{_native.LIB_PATH} has no pbg_ppo_gate: a build without value clipping and the KL gate")
+    return _native.lib()
+
+
+class KLGate(_NativeObject):
+    """The device-side early stop of a PPO update (include/pbg.h "Value clipping and the KL gate"): an int32 ``[2]``
+    array ``gate`` = (stopped, minibatch steps applied since the last ``reset``), on a GPU or, with ``device`` ``None`` /
+    ``"cpu"``, a numpy array for the host twin.  ``check(stats, kl_limit)`` is one launch of one lane (pbg_ppo_gate): while
+    not stopped, ``stats[3] > kl_limit`` stops, anything else (a NaN included) counts one more step.  ``PPOGrad.run`` /
+    ``run_part`` / ``reduce`` and ``AdamClip.step`` take ``gate`` and do nothing while it is stopped.  Only ``check`` and
+    ``reset`` write the two words, in launches of their own, so a chain of them captures as a plain chain."""
+    _HOST_HANDLE = False   # no native object on either side: the array is the state
+
+    def __init__(self, device=None):
+        _need_gate()
+        self._set_device(device, "a GPU or None", host=True)
+        self.gate = np.zeros(2, np.int32) if self.host else torch.zeros(2, dtype=torch.int32, device=self.device)
+
+    def reset(self):
+        """Both words to 0 (stream order on a GPU)."""
+        if self.host:
+            self.gate[:] = 0
+        else:
+            self._launch("pbg_ppo_gate_reset", self.gate.data_ptr())
+
+    def check(self, stats, kl_limit: float):
+        """``stats``: ``PPOGrad.run``'s float64 ``[4]``, read where it lies."""
+        self._launch("pbg_ppo_gate" + "_host" * self.host, self._ptr(stats, "check", "stats", (4,), np.float64), float(kl_limit),
+                     self._ptr(self.gate, "check", "gate", (2,), np.int32))
+
+    @property
+    def state(self):
+        """A copy of ``gate`` (a device tensor on a GPU, made on the stream: nothing is read back)."""
+        return self.gate.copy() if self.host else self.gate.clone()
 
 
 class RetStats(_NativeObject):
@@ -616,7 +676,17 @@ class PPO:
     batch of iteration i is scaled by the statistics of iterations 0 .. i.  ``Batch.rew`` and ``evaluate()`` stay in the
     robot's units, ``Batch.rew_scaled`` is what the advantages were computed from, and the value loss is then in scaled
     units.  ``iterate()``'s stats gain ``rew_scale`` (a device tensor).  It works with every setting above, a captured
-    iteration included."""
+    iteration included.
+
+    ``vf_clip=e``: PPO2's clipped value loss, ``1/2 mean(max((v - ret)^2, (vc - ret)^2))`` with
+    ``vc`` the value clamped to within ``e`` of the value the batch was collected under (``Batch.value``).  It works with
+    every ``backward``: the torch path adds the same expression, the HIP paths pass the trainer's own value buffer to
+    ``PPOGrad.run``.  ``target_kl=k`` (needs ``optimizer="hip"``): every update starts by resetting a ``KLGate``, every
+    minibatch's gradient is followed by the gate's launch with ``kl_limit = 1.5 k`` on ``mean(logp_old - logp)``, and once
+    it trips the rest of the update's launches return at entry: the tripping step is not applied.  Nothing is read back,
+    so it works eager, under ``graph=True`` and inside a captured iteration.  The stats gain ``updates`` (minibatch steps
+    applied) and ``kl_stop`` (0 or 1), device tensors; after a stop ``pg``, ``vf``, ``clipfrac`` and ``kl`` are the tripping
+    minibatch's."""
 
     def __init__(self, env, hidden=(64, 64), steps: int = 64, seed: int = 0, gamma: float = 0.99, lam: float = 0.95,
                  clip: float = 0.2, lr: float = 3e-4, epochs: int = 4, minibatches: int = 4, vf_coef: float = 0.5,
@@ -624,7 +694,7 @@ class PPO:
                  obs_norm: bool = False, obs_clip: float = 5.0, backward: str = "torch", optimizer: str = "torch",
                  graph=False, permutation: str = "torch", lr_schedule=None, schedule_iterations=None,
                  grad_path: str = "fma", truncation: str = "terminal", reward_norm: bool = False,
-                 reward_clip: float = 10.0):
+                 reward_clip: float = 10.0, vf_clip=None, target_kl=None):
         n, dev = env.num_envs, env.device
         nb = self._batch_envs(env)   # the envs whose rows make one update's batch: the env's own
         if truncation not in ("terminal", "bootstrap"):
@@ -658,6 +728,14 @@ class PPO:
             raise _native.PbgError(f"PPO: grad_path must be 'fma' or 'mfma', got {grad_path!r}")
         if grad_path != "fma" and backward != "hip":
             raise _native.PbgError("PPO: grad_path selects a path of pbg_ppo_grad: it needs backward='hip'")
+        if vf_clip is not None and not float(vf_clip) > 0.0:
+            raise _native.PbgError(f"PPO: vf_clip must be None or > 0, got {vf_clip!r}")
+        if target_kl is not None and optimizer != "hip":
+            raise _native.PbgError("PPO: target_kl is a gate the library's launches read on the device: it needs optimizer='hip'")
+        if target_kl is not None and not float(target_kl) > 0.0:
+            raise _native.PbgError(f"PPO: target_kl must be None or > 0, got {target_kl!r}")
+        self.vf_clip = None if vf_clip is None else float(vf_clip)
+        self.target_kl = None if target_kl is None else float(target_kl)
         self.backward, self.grad_path = backward, grad_path
         if n % 2 != 0 or not env.autoreset:
             raise _native.PbgError("PPO: the env must have an even number of envs (the actors are populations of one "
@@ -714,7 +792,7 @@ class PPO:
             # the storage both optimisers move in place: what every launch of the update reads and writes
             self._params = [self.actor_theta.data, self.critic_theta.data, self.log_std.data]
             self._grads = [self.actor_theta.grad, self.critic_theta.grad, self.log_std.grad]
-        self.adam = self._graph = self.perm = self._it_dev = self._iter_graph = None
+        self.adam = self._graph = self.perm = self._it_dev = self._iter_graph = self.kl_gate = None
         self.permutation, self.lr_schedule, self.graph_iteration = permutation, lr_schedule, graph == "iteration"
         if optimizer == "hip":
             if norm_adv and (T * nb) // self.minibatches < 2:
@@ -736,6 +814,8 @@ class PPO:
             # what the chain (and a replay of it) reads and every update refills in place
             self._perm = torch.zeros((self.epochs, self.minibatches, (T * nb) // self.minibatches), dtype=torch.int64, device=dev)
             self._logp_old = torch.zeros(T * nb, **kw)
+            if self.target_kl is not None:
+                self.kl_gate, self.kl_limit = KLGate(dev), 1.5 * self.target_kl
         env.reset()
 
     def _batch_envs(self, env) -> int:
@@ -815,6 +895,10 @@ class PPO:
                 ratio = torch.exp(logp - logp_old[idx])
                 pg = -torch.min(ratio * a_mb, torch.clamp(ratio, 1.0 - self.clip, 1.0 + self.clip) * a_mb).mean()
                 vf = 0.5 * ((v - ret[idx]) ** 2).mean()
+                if self.vf_clip is not None:
+                    vo = self._value_old()[idx]
+                    vc = vo + torch.clamp(v - vo, -self.vf_clip, self.vf_clip)
+                    vf = 0.5 * torch.maximum((v - ret[idx]) ** 2, (vc - ret[idx]) ** 2).mean()
                 entropy = self.log_std.sum() + 0.5 * A * (1.0 + math.log(2.0 * math.pi))
                 loss = pg + self.vf_coef * vf - self.ent_coef * entropy
                 self.opt.zero_grad(set_to_none=True)
@@ -833,8 +917,17 @@ class PPO:
         the first two."""
         inputs = dict(idx=idx, adv_norm=adv_norm, obs_norm=self.actor.obs_norm, clip_eps=self.clip, vf_coef=self.vf_coef,
                       ent_coef=self.ent_coef)
+        if self.vf_clip is not None:
+            inputs.update(value_old=self._value_old(), vf_clip=self.vf_clip)
+        if self.kl_gate is not None:
+            inputs.update(gate=self.kl_gate.gate)
         outputs = dict(grad_actor=self._grads[0], grad_critic=self._grads[1], grad_log_std=self._grads[2], stats=self._grad_stats)
         return (*self._params, *batch), inputs, outputs
+
+    def _value_old(self):
+        """``vf_clip``'s ``value_old [B]``: ``Batch.value[:T]``, a view of the trainer's own buffer, in the batch's row
+        order."""
+        return self._value[:self.steps].reshape(-1)
 
     def _gradient(self, batch, idx, adv_norm):
         """The minibatch's gradient into the parameters' ``.grad``: pbg_ppo_grad_run, two launches."""
@@ -865,9 +958,15 @@ class PPO:
 
     def _minibatch_opt(self, batch, idx):
         """One minibatch step as at most five launches of the library: pbg_adv_norm, pbg_ppo_grad_run (two),
-        pbg_ppo_opt_step (two)."""
+        pbg_ppo_opt_step (two); with ``target_kl`` a sixth between the two pairs, pbg_ppo_gate, and the gate's array goes
+        to both."""
         self._gradient(batch, idx, adv_norm(batch[3], idx, out=self._adv_norm) if self.norm_adv else None)
-        self.adam.step(self._params, self._grads, self._lr_now, (0.9, 0.999), 1e-5, self.max_grad_norm, info=self._opt_info)
+        if self.kl_gate is None:
+            self.adam.step(self._params, self._grads, self._lr_now, (0.9, 0.999), 1e-5, self.max_grad_norm, info=self._opt_info)
+            return
+        self.kl_gate.check(self._grad_stats, self.kl_limit)
+        self.adam.step(self._params, self._grads, self._lr_now, (0.9, 0.999), 1e-5, self.max_grad_norm, info=self._opt_info,
+                       gate=self.kl_gate.gate)
 
     def _schedule(self):
         """The schedule's launch: this iteration's learning rate into ``_lr_dev``, from the device's iteration count."""
@@ -879,8 +978,11 @@ class PPO:
         self.perm.fill(B, self.epochs, out=self._perm.view(self.epochs, B))
 
     def _chain(self, batch, B):
-        """The ``epochs x minibatches`` chain of ``optimizer="hip"``, launches of the library alone: the schedule's,
-        with ``permutation="device"`` the permutation fill, then every minibatch of ``_perm``."""
+        """The ``epochs x minibatches`` chain of ``optimizer="hip"``, launches of the library alone: with ``target_kl``
+        the gate's reset, the schedule's, with ``permutation="device"`` the permutation fill, then every minibatch of
+        ``_perm``."""
+        if self.kl_gate is not None:
+            self.kl_gate.reset()
         self._schedule()
         if self.perm is not None:
             self._draw(B)
@@ -947,7 +1049,11 @@ class PPO:
 
     def _stats_now(self) -> dict:
         st, info = self._grad_stats.clone(), self._opt_info.clone()   # the last minibatch's
-        return dict(pg=st[0], vf=st[1], clipfrac=st[2], kl=st[3], grad_norm=info[0])
+        stats = dict(pg=st[0], vf=st[1], clipfrac=st[2], kl=st[3], grad_norm=info[0])
+        if self.kl_gate is not None:
+            g = self.kl_gate.state   # a stopped update: the tripping minibatch's stats, the last applied step's norm
+            stats.update(updates=g[1], kl_stop=g[0])
+        return stats
 
     def _baked_iteration(self):
         """The addresses an iteration's launches take that the trainer does not own alone: the env's observation and
@@ -1011,7 +1117,8 @@ class PPO:
     def close(self):
         self.actor.attach_action_noise(None)
         self._graph = self._iter_graph = None
-        for o in (self.actor, self.critic, self.noise, self.obs_stats, self.grad, self.adam, self.perm, self.ret_stats):
+        for o in (self.actor, self.critic, self.noise, self.obs_stats, self.grad, self.adam, self.perm, self.ret_stats,
+                  self.kl_gate):
             if o is not None:
                 o.close()
 
@@ -1093,15 +1200,20 @@ class ShardedPPO(PPO):
         self._part = torch.zeros((self._G, self._dtot), dtype=torch.float32, device=dev)
         self._part_stats = torch.zeros((self._G, 4), dtype=torch.float64, device=dev)
         kw = dict(dtype=torch.float32, device=dev)
-        self._packed = torch.zeros((T, self.env.num_envs, o + A + 3), **kw)
+        # vf_clip: one more column, the values the batch was collected under
+        self._packed = torch.zeros((T, self.env.num_envs, o + A + 3 + (self.vf_clip is not None)), **kw)
         self._g_obs, self._g_act = torch.zeros((B, o), **kw), torch.zeros((B, A), **kw)
         self._g_adv, self._g_ret = torch.zeros(B, **kw), torch.zeros(B, **kw)
+        self._g_value = torch.zeros(B, **kw) if self.vf_clip is not None else None
 
     def _batch_envs(self, env) -> int:
         return self.num_global
 
     def _make_ret_stats(self, n, dev):
         return RetStats(n, self.gamma, dev, n_slots=self.num_global // RetStats.TILE)
+
+    def _value_old(self):
+        return self._g_value
 
     def _gather_slots(self, stats, first, count):
         """The slots ``first .. first + count - 1`` of every rank's ``stats`` (an ``ObsStats`` or a ``RetStats``), one
@@ -1154,12 +1266,16 @@ class ShardedPPO(PPO):
         p[:, :, o + A].copy_(b.logp)   # float64 -> float32, the rounding of PPO's own copy
         p[:, :, o + A + 1].copy_(b.adv)
         p[:, :, o + A + 2].copy_(b.ret)
-        g = (p if self.world == 1 else gather_traj(p, self.num_global, self._group)).view(B, o + A + 3)
+        if self.vf_clip is not None:
+            p[:, :, o + A + 3].copy_(b.value[:T])
+        g = (p if self.world == 1 else gather_traj(p, self.num_global, self._group)).view(B, p.shape[2])
         self._g_obs.copy_(g[:, :o])
         self._g_act.copy_(g[:, o:o + A])
         self._logp_old.copy_(g[:, o + A])
         self._g_adv.copy_(g[:, o + A + 1])
         self._g_ret.copy_(g[:, o + A + 2])
+        if self.vf_clip is not None:
+            self._g_value.copy_(g[:, o + A + 3])
         self._chain((self._g_obs, self._g_act, self._logp_old, self._g_adv, self._g_ret), B)
         return self._stats_now()
 

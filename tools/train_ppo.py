@@ -9,7 +9,7 @@ as an npz that tools/enjoy.py and MLPPolicy.from_npz load.
          [--obs-norm] [--obs-clip 5.0] [--eval-envs 256] [--eval-steps 200] [--eval-every 1] [--curve curve.json]
          [--backward hip] [--optimizer hip] [--graph [iteration]] [--permutation device]
          [--lr-schedule linear --schedule-iterations N] [--grad-path mfma] [--truncation bootstrap] [--sharded]
-         [--reward-norm] [--reward-clip 10.0]
+         [--reward-norm] [--reward-clip 10.0] [--vf-clip X] [--target-kl Y]
 
 --obs-norm trains under running observation normalisation (PPO(obs_norm=True)) and saves the final normaliser
 in the npz (obs_mean, obs_inv_std, obs_clip); --curve writes the per-iteration evaluation as JSON.  --optimizer hip
@@ -24,6 +24,9 @@ observation through a TimeLimit truncation instead of treating it as a death; th
 --reward-norm (PPO(reward_norm=True)) divides the rewards the critic regresses by a running standard deviation of the
 discounted return (ppo.RetStats, pbg_ret_stats) and clips them to +-reward-clip; the printed returns stay in the robot's
 units, the curve's vf_loss is then in scaled units and gains rew_scale.
+--vf-clip X (PPO(vf_clip=X)) clips the value loss PPO2's way, against the values the batch was collected under; --target-kl Y
+(PPO(target_kl=Y), needs --optimizer hip) stops an update on the device once a minibatch's mean(logp_old - logp) exceeds
+1.5 Y; the curve gains updates (minibatch steps applied) and kl.
 
 --sharded trains data-parallel (ppo.ShardedPPO: --envs is the global count; --backward, --optimizer and --permutation
 default to hip, hip and device, any other choice is refused by ShardedPPO, and it takes no --graph): one process per
@@ -91,6 +94,9 @@ def main():
     ap.add_argument("--reward-norm", action="store_true",
                     help="scale the rewards by a running std of the discounted return (pbg_ret_stats)")
     ap.add_argument("--reward-clip", type=float, default=10.0, help="the scaled rewards' clip")
+    ap.add_argument("--vf-clip", type=float, default=None, help="clip the value loss within this range of the batch's values")
+    ap.add_argument("--target-kl", type=float, default=None,
+                    help="stop an update on the device once mean(logp_old - logp) exceeds 1.5 times this (needs --optimizer hip)")
     ap.add_argument("--curve", default=None, help="write the per-iteration evaluation here (JSON)")
     ap.add_argument("--sharded", action="store_true",
                     help="data-parallel over the ranks of RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT (ShardedPPO)")
@@ -135,13 +141,14 @@ def main():
               log_std=args.log_std, obs_norm=args.obs_norm, obs_clip=args.obs_clip, backward=args.backward,
               optimizer=args.optimizer, permutation=args.permutation, lr_schedule=args.lr_schedule,
               schedule_iterations=args.schedule_iterations, grad_path=args.grad_path, truncation=args.truncation,
-              reward_norm=args.reward_norm, reward_clip=args.reward_clip)
+              reward_norm=args.reward_norm, reward_clip=args.reward_clip, vf_clip=args.vf_clip, target_kl=args.target_kl)
     say(f"{args.env_id} (float{args.precision}): {args.envs} envs x {args.steps} steps per iteration, actor MLP "
           f"{ppo.actor_dims}, lr {args.lr}, {args.epochs} epochs x {args.minibatches} minibatches, observation "
           f"normalisation {'on' if args.obs_norm else 'off'}, backward pass {args.backward}, optimizer "
           f"{args.optimizer}{' (one graph per iteration)' if args.graph == 'iteration' else ' (one graph)' if args.graph else ''}, "
           f"permutation {args.permutation}, lr schedule {args.lr_schedule}, gradient path {args.grad_path}, truncation "
-          f"{args.truncation}, reward normalisation {'on' if args.reward_norm else 'off'}" +
+          f"{args.truncation}, reward normalisation {'on' if args.reward_norm else 'off'}, vf_clip {args.vf_clip}, target_kl "
+          f"{args.target_kl}" +
         (f", {ppo.world} ranks" if args.sharded else ""))
     curve = []
     stats = {}   # the last iterate()'s: the last minibatch's losses
@@ -152,7 +159,9 @@ def main():
                           length_mean=length.double().mean().item(), std_mean=ppo.log_std.data.exp().mean().item(),
                           vf_loss=float(stats["vf"]) if "vf" in stats else None,
                           grad_norm=float(stats["grad_norm"]) if "grad_norm" in stats else None,
-                          rew_scale=float(stats["rew_scale"]) if "rew_scale" in stats else None))
+                          rew_scale=float(stats["rew_scale"]) if "rew_scale" in stats else None,
+                          kl=float(stats["kl"]) if "kl" in stats else None,
+                          updates=int(stats["updates"]) if "updates" in stats else None))
         say(f"iteration {it:4d}: mean policy return mean {ret.mean().item():9.2f} min {ret.min().item():9.2f}  "
               f"first-episode length mean {length.double().mean().item():6.1f} of {args.eval_steps}  "
               f"action std {curve[-1]['std_mean']:.3f}", flush=True)
