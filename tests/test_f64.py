@@ -31,6 +31,7 @@ import numpy as np
 import pytest
 import torch
 
+import kernel_plans
 import oracle
 import pybulletgym_amd  # noqa: F401
 from pybulletgym_amd._native import PbgError
@@ -195,6 +196,20 @@ def test_f64_sim_params_teacher_forced():
     """A changed scene reaches the float64 kernels at float64 precision (SimPT<double>)."""
     _teacher_forced64("AntPyBulletEnv-v0", 128, 30, sim={"gravity": 4.9, "solver_iterations": 8},
                       name="f64_sim_params[Ant,g=4.9,it=8]")
+
+
+@pytest.mark.parametrize("env_id,over,opts", [pytest.param(e, s, o, id=kernel_plans.scene_id(e, s, o))
+                                              for e, s, o in kernel_plans.f64_scene_cases()])
+def test_f64_sim_params_every_family(env_id, over, opts):
+    """A non-default SimPT<double> on every float64 kernel family -- lane, quad, 16- and 32-lane gangs, replicated
+    and distributed gang dynamics -- with every scene field changed somewhere and the documented edges (gravity 0,
+    ERP 0 and 1, one PGS sweep, frame_skip 1): tests/kernel_plans.py's F64_SCENE_VARIANTS, 64 envs x 20 steps
+    (Atlas 32 x 12), the helper's bounds.  The oracle forms the scene in its own code (oracle/pbg_physics.h), so
+    this holds resolve_sim_params<double>'s derived fields (k_contact, k_limit, ang_max, dt3c, flag_timeout,
+    env_dt) to it as well.  tests/test_kernel_plans_host.py: every variant leaves the default scene's trajectory."""
+    n, steps = kernel_plans.scene_size(env_id)
+    _teacher_forced64(env_id, n, steps, sim=over, name=f"f64_sim_params_every_family[{kernel_plans.scene_id(env_id, over, opts)}]",
+                      **opts)
 
 
 @pytest.mark.timeout(900)

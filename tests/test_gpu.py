@@ -20,6 +20,7 @@ import numpy as np
 import pytest
 import torch
 
+import kernel_plans
 import oracle
 import pybulletgym_amd  # noqa: F401
 from pybulletgym_amd import rng
@@ -1009,14 +1010,20 @@ def test_checkpoint_restore_is_bitwise_across_resets():
     np.testing.assert_array_equal(a.get_state()[1].cpu().numpy(), b.get_state()[1].cpu().numpy())
 
 
-@pytest.mark.parametrize("env_id,precision,opts", [
+POISON_CASES = [
     ("AntPyBulletEnv-v0", 32, {}), ("AntPyBulletEnv-v0", 64, {}), ("AntPyBulletEnv-v0", 64, {"lds_rows": 0}),
     ("HumanoidPyBulletEnv-v0", 32, {}), ("HumanoidPyBulletEnv-v0", 64, {}), ("HumanoidPyBulletEnv-v0", 32, {"lds_rows": 0}),
     ("HumanoidFlagrunHarderPyBulletEnv-v0", 32, {}), ("HalfCheetahMuJoCoEnv-v0", 64, {}),
     ("HopperPyBulletEnv-v0", 64, {"kernel": 0}), ("HalfCheetahPyBulletEnv-v0", 32, {"kernel": 0}),
     ("AtlasPyBulletEnv-v0", 32, {}), ("InvertedDoublePendulumPyBulletEnv-v0", 64, {}),
     ("HopperPyBulletEnv-v0", 64, {}), ("HumanoidFlagrunHarderPyBulletEnv-v0", 32, {"gang_lanes": 32}),
-    ("HumanoidPyBulletEnv-v0", 64, {"kernel": 0}), ("AntMuJoCoEnv-v0", 64, {})])
+    ("HumanoidPyBulletEnv-v0", 64, {"kernel": 0}), ("AntMuJoCoEnv-v0", 64, {})]
+# ... and every other float64 kernel plan of the recorded table (tests/kernel_plans.py): the float64 gang and quad
+# kernels run pbg_sincos64.h, on which the lane kernel computed state-dependent results
+POISON_CASES += [(e, 64, o) for e, o, _ in kernel_plans.plans(64) if (e, 64, o) not in POISON_CASES]
+
+
+@pytest.mark.parametrize("env_id,precision,opts", POISON_CASES)
 def test_uninitialised_memory_invariance(env_id, precision, opts):
     """Every kernel writes what it reads within a launch.  pbg_debug_poison fills every CU's LDS and the
     handle's device workspace with a pattern before each step (float NaN 0x7FC00000 -- a double NaN
@@ -1224,6 +1231,8 @@ SIM_VARIANTS = [("AntPyBulletEnv-v0", {"gravity": 4.9, "solver_iterations": 8}),
                 ("HumanoidFlagrunPyBulletEnv-v0", {"gravity": 9.0, "solver_iterations": 6}),
                 ("HopperMuJoCoEnv-v0", {"timestep": 0.002, "frame_skip": 6}),
                 ("InvertedPendulumPyBulletEnv-v0", {"gravity": 3.7, "timestep": 0.01})]
+# the documented edges: no gravity, ERP 0 (contacts and joint limits), one PGS sweep
+SIM_VARIANTS += kernel_plans.F32_EDGE_VARIANTS
 
 
 @pytest.mark.timeout(300)
