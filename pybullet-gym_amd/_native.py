@@ -147,11 +147,158 @@ class PPOOptIO3(PPOOptIO2):
 POLICY_MAX_DIM = 256  # PBG_POLICY_MAX_DIM: obs_dim, h1, h2
 POLICY_MAX_ACT = 64   # PBG_POLICY_MAX_ACT
 
+# Every entry point of include/pbg.h, once: group -> {name: (restype, argtypes)}.  "core" is what every build has;
+# any other group is bound when the loaded library has its first name (the tools also load diagnostic and older
+# builds), and GROUP_EXPORTED is its names.  A new unit is one group here.
+_P = _H = ctypes.c_void_p
+_I, _U32, _U64, _F, _D, _S = (ctypes.c_int, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_float, ctypes.c_double,
+                              ctypes.c_char_p)
+_HP, _IP, _I64P, _FP = (ctypes.POINTER(t) for t in (_H, _I, ctypes.c_int64, ctypes.c_float))
+_SIM, _DBG, _RIO, _GIO = (ctypes.POINTER(t) for t in (SimParams, DebugOpts, RolloutIO, PPOGradIO))
+SIGNATURES = {
+    "core": {
+        "pbg_create": (_I, [_S, _I, _I, _U64, _I, _HP]),
+        "pbg_create_debug": (_I, [_S, _I, _I, _U64, _I, _DBG, _HP]),
+        "pbg_create_ex": (_I, [_S, _I, _I, _U64, _I, _SIM, _DBG, _HP]),
+        "pbg_create_v2": (_I, [_S, _I, _I, _U64, _I, _SIM, ctypes.POINTER(CreateOpts), _HP]),
+        "pbg_precision": (_I, [_H]),
+        "pbg_default_sim_params": (_I, [_S, _SIM]),
+        "pbg_get_sim_params": (_I, [_H, _SIM]),
+        "pbg_destroy": (None, [_H]),
+        "pbg_info": (_I, [_H, ctypes.POINTER(Info)]),
+        "pbg_reset": (_I, [_H, _P, _P, _P, _P]),
+        "pbg_step": (_I, [_H, _P, _P, _P, _P, _P]),
+        "pbg_step_ex": (_I, [_H, ctypes.POINTER(StepIO), _P]),
+        "pbg_get_state": (_I, [_H, _P, _P, _P]),
+        "pbg_set_state": (_I, [_H, _P, _P, _P]),
+        "pbg_pack_record_sizes": (_I, [_S, _IP, _IP]),
+        "pbg_pack": (_I, [_S, _I, _P, _P, _P]),
+        "pbg_sample_actions": (_I, [_I, _I, _I, _U64, _U32, _I, _P, _P]),
+        "pbg_last_error": (_S, []),
+    },
+    "debug_poison": {  # diagnostic entry (tools/vgpr_poison_probe.py also loads older builds)
+        "pbg_debug_poison": (_I, [_H, _U32, _P]),
+    },
+    "policy": {
+        "pbg_policy_create": (_I, [_I, _I, _I, _I, _I, _FP, _FP, _FP, _FP, _FP, _FP, _HP]),
+        "pbg_policy_destroy": (None, [_H]),
+        "pbg_policy_act": (_I, [_H, _I, _P, _P, _P]),
+        "pbg_policy_act_host": (_I, [_H, _I, _P, _P]),
+        "pbg_rollout": (_I, [_H, _H, _RIO, _P]),
+    },
+    "population": {  # policy populations / evolution strategies
+        "pbg_population_create": (_I, [_I, _I, _I, _I, _I, _I, _I, _HP]),
+        "pbg_population_destroy": (None, [_H]),
+        "pbg_population_noise": (_I, [_H, _U64, _U32, _P, _P]),
+        "pbg_population_noise_host": (_I, [_I, _I, _I, _I, _U64, _U32, _I, _I, _P]),
+        "pbg_population_perturb": (_I, [_H, _P, _F, _U64, _U32, _P]),
+        "pbg_population_set_member": (_I, [_H, _I, _P, _P]),
+        "pbg_population_get_member": (_I, [_H, _I, _P, _P]),
+        "pbg_population_act": (_I, [_H, _I, _P, _P, _P]),
+        "pbg_rollout_population": (_I, [_H, _H, _RIO, _P]),
+        "pbg_population_fitness": (_I, [_H, _I, _P, _P, _P, _P]),
+        "pbg_population_grad": (_I, [_H, _P, _U64, _U32, _P, _P]),
+    },
+    "obs_norm": {  # running observation normalisation
+        "pbg_obs_stats_create": (_I, [_I, _I, _I, _HP]),
+        "pbg_obs_stats_destroy": (None, [_H]),
+        "pbg_obs_stats_update": (_I, [_H, _I, _I, _P, _P, _P]),
+        "pbg_obs_stats_finalize": (_I, [_H, _P, _P, _P]),
+        "pbg_obs_stats_get_totals": (_I, [_H, _P, _P]),
+        "pbg_obs_stats_set_totals": (_I, [_H, _P, _P]),
+        "pbg_policy_set_obs_norm": (_I, [_H, _P, _P, _F]),
+        "pbg_population_set_obs_norm": (_I, [_H, _P, _P, _F, _P]),
+        "pbg_policy_attach_obs_stats": (_I, [_H, _H]),
+        "pbg_population_attach_obs_stats": (_I, [_H, _H]),
+    },
+    "action_noise": {  # stochastic actions and advantage estimation
+        "pbg_action_noise_create": (_I, [_I, _I, _U64, _HP]),
+        "pbg_action_noise_destroy": (None, [_H]),
+        "pbg_action_noise_set_std": (_I, [_H, _P, _P]),
+        "pbg_action_noise_set_counter": (_I, [_H, _U32, _P]),
+        "pbg_action_noise_get_counter": (_I, [_H, _P, _P]),
+        "pbg_action_noise_set_eps2_traj": (_I, [_H, _P]),
+        "pbg_action_noise_fill": (_I, [_H, _I, _I, _U32, _P, _P]),
+        "pbg_action_noise_host": (_I, [_I, _U64, _I, _I, _U32, _P]),
+        "pbg_policy_attach_action_noise": (_I, [_H, _H]),
+        "pbg_population_attach_action_noise": (_I, [_H, _H]),
+        "pbg_gae": (_I, [_I, _I, _P, _P, _P, _D, _D, _P, _P, _P]),
+        "pbg_gae_host": (_I, [_I, _I, _P, _P, _P, _D, _D, _P, _P]),
+    },
+    "ppo_grad": {  # the PPO update's backward pass
+        "pbg_ppo_grad_create": (_I, [_I, _I, _I, _I, _I, _I, _HP]),
+        "pbg_ppo_grad_destroy": (None, [_H]),
+        "pbg_ppo_grad_run": (_I, [_H, _GIO, _P]),
+        "pbg_ppo_grad_host": (_I, [_I, _I, _I, _I, _GIO]),
+    },
+    "ppo_opt": {  # the advantage normaliser and the clip + Adam step
+        "pbg_adv_norm": (_I, [_I, _I, _P, _P, _P, _P]),
+        "pbg_adv_norm_host": (_I, [_I, _I, _P, _P, _P]),
+        "pbg_ppo_opt_create": (_I, [_I, _I, _I64P, _HP]),
+        "pbg_ppo_opt_destroy": (None, [_H]),
+        "pbg_ppo_opt_step": (_I, [_H, _P, _P]),
+        "pbg_ppo_opt_reset": (_I, [_H, _P]),
+        "pbg_ppo_opt_get_state": (_I, [_H, _P, _P, _P, _P]),
+        "pbg_ppo_opt_host": (_I, [_I, _I64P, _P]),
+    },
+    "perm": {  # counter-based permutations and the on-device learning rate
+        "pbg_perm_create": (_I, [_I, _U64, _HP]),
+        "pbg_perm_destroy": (None, [_H]),
+        "pbg_perm_fill": (_I, [_H, _I, _I, _P, _P]),
+        "pbg_perm_set_counter": (_I, [_H, _U32, _P]),
+        "pbg_perm_get_counter": (_I, [_H, _P, _P]),
+        "pbg_perm_host": (_I, [_U64, _U32, _I, _I, _P]),
+        "pbg_ppo_lr_linear": (_I, [_P, _U32, _D, _P, _P]),
+        "pbg_ppo_lr_linear_host": (_I, [_P, _U32, _D, _P]),
+    },
+    "ppo_grad_ex": {  # the gradient's matrix-core path
+        "pbg_ppo_grad_create_ex": (_I, [_I, _I, _I, _I, _I, _I, ctypes.POINTER(PPOGradOpts), _HP]),
+    },
+    "ppo_parts": {  # the gradient as parts and the statistics' slots
+        "pbg_ppo_grad_geometry": (_I, [_H, _I, _IP, _I64P]),
+        "pbg_ppo_grad_run_part": (_I, [_H, _GIO, _I, _I, _P, _P, _P]),
+        "pbg_ppo_grad_reduce": (_I, [_H, _GIO, _I, _P, _P, _P]),
+        "pbg_obs_stats_get_slots": (_I, [_H, _I, _I, _P, _P, _P]),
+        "pbg_obs_stats_set_slots": (_I, [_H, _I, _I, _P, _P, _P]),
+    },
+    "trunc": {  # truncation bootstrapping: the masked actor launch and its GAE
+        "pbg_population_act_where": (_I, [_H, _I, _I, _P, _P, _P, _P]),
+        "pbg_gae_trunc": (_I, [_I, _I, _P, _P, _P, _P, _P, _D, _D, _P, _P, _P]),
+        "pbg_gae_trunc_host": (_I, [_I, _I, _P, _P, _P, _P, _P, _D, _D, _P, _P]),
+    },
+    "ret_stats": {  # reward scaling by a running std of the discounted return
+        "pbg_ret_stats_create": (_I, [_I, _I, _I, _D, _HP]),
+        "pbg_ret_stats_destroy": (None, [_H]),
+        "pbg_ret_stats_walk": (_I, [_H, _I, _I, _I, _P, _P, _P]),
+        "pbg_ret_stats_finalize": (_I, [_H, _I, _D, _P]),
+        "pbg_ret_stats_apply": (_I, [_H, _I, _F, _P, _P, _P]),
+        "pbg_ret_stats_reset": (_I, [_H, _P]),
+        "pbg_ret_stats_get_slots": (_I, [_H, _I, _I, _P, _P, _P]),
+        "pbg_ret_stats_set_slots": (_I, [_H, _I, _I, _P, _P, _P]),
+        "pbg_ret_stats_get_totals": (_I, [_H, _P, _P, _P]),
+        "pbg_ret_stats_set_totals": (_I, [_H, _P, _P, _P]),
+        "pbg_ret_stats_get_carry": (_I, [_H, _P, _P]),
+        "pbg_ret_stats_set_carry": (_I, [_H, _P, _P]),
+        "pbg_ret_stats_get_scale": (_I, [_H, _P, _P]),
+        "pbg_ret_stats_set_scale": (_I, [_H, _P, _P]),
+    },
+    "ppo_gate": {  # value clipping and the KL gate
+        "pbg_ppo_gate_reset": (_I, [_P, _P]),
+        "pbg_ppo_gate": (_I, [_P, _D, _P, _P]),
+        "pbg_ppo_gate_host": (_I, [_P, _D, _P]),
+    },
+}
+EXPORTED = tuple(n for sigs in SIGNATURES.values() for n in sigs)
+# POLICY_EXPORTED, POPULATION_EXPORTED, OBS_NORM_EXPORTED, ACTION_NOISE_EXPORTED, PPO_GRAD_EXPORTED, PPO_OPT_EXPORTED,
+# PERM_EXPORTED, PPO_GRAD_EX_EXPORTED, PPO_PARTS_EXPORTED, TRUNC_EXPORTED, RET_STATS_EXPORTED, PPO_GATE_EXPORTED
+globals().update({f"{g.upper()}_EXPORTED": tuple(sigs) for g, sigs in SIGNATURES.items()
+                  if g not in ("core", "debug_poison")})
+
 _lib = None
 
 
 def lib():
-    """Load libpbg_amd.so, failing loudly if it is absent."""
+    """Load libpbg_amd.so, failing loudly if it is absent, and give every entry point its signature."""
     global _lib
     if _lib is not None:
         return _lib
@@ -159,215 +306,14 @@ def lib():
         raise PbgError(f"{LIB_PATH} not found: the HIP extension is not built "
                        "(run `python __graft_entry__.py` or `make -C pybullet-gym_amd`)")
     L = ctypes.CDLL(LIB_PATH)
-    P, I, H = ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p
-    L.pbg_create.argtypes = [ctypes.c_char_p, I, I, ctypes.c_uint64, I, ctypes.POINTER(H)]
-    L.pbg_create.restype = I
-    L.pbg_create_debug.argtypes = [ctypes.c_char_p, I, I, ctypes.c_uint64, I, ctypes.POINTER(DebugOpts),
-                                   ctypes.POINTER(H)]
-    L.pbg_create_ex.argtypes = [ctypes.c_char_p, I, I, ctypes.c_uint64, I, ctypes.POINTER(SimParams),
-                                ctypes.POINTER(DebugOpts), ctypes.POINTER(H)]
-    L.pbg_create_v2.argtypes = [ctypes.c_char_p, I, I, ctypes.c_uint64, I, ctypes.POINTER(SimParams),
-                                ctypes.POINTER(CreateOpts), ctypes.POINTER(H)]
-    L.pbg_precision.argtypes = [H]
-    L.pbg_default_sim_params.argtypes = [ctypes.c_char_p, ctypes.POINTER(SimParams)]
-    L.pbg_get_sim_params.argtypes = [H, ctypes.POINTER(SimParams)]
-    L.pbg_sample_actions.argtypes = [I, I, I, ctypes.c_uint64, ctypes.c_uint32, I, P, P]
-    L.pbg_destroy.argtypes = [H]
-    L.pbg_destroy.restype = None
-    L.pbg_info.argtypes = [H, ctypes.POINTER(Info)]
-    L.pbg_reset.argtypes = [H, P, P, P, P]
-    L.pbg_step.argtypes = [H, P, P, P, P, P]
-    L.pbg_step_ex.argtypes = [H, ctypes.POINTER(StepIO), P]
-    L.pbg_get_state.argtypes = [H, P, P, P]
-    L.pbg_set_state.argtypes = [H, P, P, P]
-    L.pbg_pack_record_sizes.argtypes = [ctypes.c_char_p, ctypes.POINTER(I), ctypes.POINTER(I)]
-    L.pbg_pack.argtypes = [ctypes.c_char_p, I, P, P, P]
-    if hasattr(L, "pbg_debug_poison"):  # diagnostic entry (tools/vgpr_poison_probe.py also loads older builds)
-        L.pbg_debug_poison.argtypes = [H, ctypes.c_uint32, P]
-        L.pbg_debug_poison.restype = I
-    L.pbg_last_error.restype = ctypes.c_char_p
-    if hasattr(L, "pbg_policy_create"):  # the tools also load diagnostic and older builds without the policy
-        FP = ctypes.POINTER(ctypes.c_float)
-        L.pbg_policy_create.argtypes = [I, I, I, I, I, FP, FP, FP, FP, FP, FP, ctypes.POINTER(H)]
-        L.pbg_policy_destroy.argtypes = [H]
-        L.pbg_policy_destroy.restype = None
-        L.pbg_policy_act.argtypes = [H, I, P, P, P]
-        L.pbg_policy_act_host.argtypes = [H, I, P, P]
-        L.pbg_rollout.argtypes = [H, H, ctypes.POINTER(RolloutIO), P]
-        for f in ("pbg_policy_create", "pbg_policy_act", "pbg_policy_act_host", "pbg_rollout"):
-            getattr(L, f).restype = I
-    if hasattr(L, "pbg_population_create"):  # policy populations / evolution strategies
-        U64, U32, F = ctypes.c_uint64, ctypes.c_uint32, ctypes.c_float
-        L.pbg_population_create.argtypes = [I, I, I, I, I, I, I, ctypes.POINTER(H)]
-        L.pbg_population_destroy.argtypes = [H]
-        L.pbg_population_destroy.restype = None
-        L.pbg_population_noise.argtypes = [H, U64, U32, P, P]
-        L.pbg_population_noise_host.argtypes = [I, I, I, I, U64, U32, I, I, P]
-        L.pbg_population_perturb.argtypes = [H, P, F, U64, U32, P]
-        L.pbg_population_set_member.argtypes = [H, I, P, P]
-        L.pbg_population_get_member.argtypes = [H, I, P, P]
-        L.pbg_population_act.argtypes = [H, I, P, P, P]
-        L.pbg_rollout_population.argtypes = [H, H, ctypes.POINTER(RolloutIO), P]
-        L.pbg_population_fitness.argtypes = [H, I, P, P, P, P]
-        L.pbg_population_grad.argtypes = [H, P, U64, U32, P, P]
-        for f in POPULATION_EXPORTED:
-            if f != "pbg_population_destroy":
-                getattr(L, f).restype = I
-    if hasattr(L, "pbg_obs_stats_create"):  # running observation normalisation
-        F = ctypes.c_float
-        L.pbg_obs_stats_create.argtypes = [I, I, I, ctypes.POINTER(H)]
-        L.pbg_obs_stats_destroy.argtypes = [H]
-        L.pbg_obs_stats_destroy.restype = None
-        L.pbg_obs_stats_update.argtypes = [H, I, I, P, P, P]
-        L.pbg_obs_stats_finalize.argtypes = [H, P, P, P]
-        L.pbg_obs_stats_get_totals.argtypes = [H, P, P]
-        L.pbg_obs_stats_set_totals.argtypes = [H, P, P]
-        L.pbg_policy_set_obs_norm.argtypes = [H, P, P, F]
-        L.pbg_population_set_obs_norm.argtypes = [H, P, P, F, P]
-        L.pbg_policy_attach_obs_stats.argtypes = [H, H]
-        L.pbg_population_attach_obs_stats.argtypes = [H, H]
-        for f in OBS_NORM_EXPORTED:
-            if f != "pbg_obs_stats_destroy":
-                getattr(L, f).restype = I
-    if hasattr(L, "pbg_action_noise_create"):  # stochastic actions and advantage estimation
-        U64, U32, D = ctypes.c_uint64, ctypes.c_uint32, ctypes.c_double
-        L.pbg_action_noise_create.argtypes = [I, I, U64, ctypes.POINTER(H)]
-        L.pbg_action_noise_destroy.argtypes = [H]
-        L.pbg_action_noise_destroy.restype = None
-        L.pbg_action_noise_set_std.argtypes = [H, P, P]
-        L.pbg_action_noise_set_counter.argtypes = [H, U32, P]
-        L.pbg_action_noise_get_counter.argtypes = [H, P, P]
-        L.pbg_action_noise_set_eps2_traj.argtypes = [H, P]
-        L.pbg_action_noise_fill.argtypes = [H, I, I, U32, P, P]
-        L.pbg_action_noise_host.argtypes = [I, U64, I, I, U32, P]
-        L.pbg_policy_attach_action_noise.argtypes = [H, H]
-        L.pbg_population_attach_action_noise.argtypes = [H, H]
-        L.pbg_gae.argtypes = [I, I, P, P, P, D, D, P, P, P]
-        L.pbg_gae_host.argtypes = [I, I, P, P, P, D, D, P, P]
-        for f in ACTION_NOISE_EXPORTED:
-            if f != "pbg_action_noise_destroy":
-                getattr(L, f).restype = I
-    if hasattr(L, "pbg_ppo_grad_create"):  # the PPO update's backward pass
-        L.pbg_ppo_grad_create.argtypes = [I, I, I, I, I, I, ctypes.POINTER(H)]
-        L.pbg_ppo_grad_destroy.argtypes = [H]
-        L.pbg_ppo_grad_destroy.restype = None
-        L.pbg_ppo_grad_run.argtypes = [H, ctypes.POINTER(PPOGradIO), P]
-        L.pbg_ppo_grad_host.argtypes = [I, I, I, I, ctypes.POINTER(PPOGradIO)]
-        for f in PPO_GRAD_EXPORTED:
-            if f != "pbg_ppo_grad_destroy":
-                getattr(L, f).restype = I
-    if hasattr(L, "pbg_ppo_grad_create_ex"):  # its matrix-core path
-        L.pbg_ppo_grad_create_ex.argtypes = [I, I, I, I, I, I, ctypes.POINTER(PPOGradOpts), ctypes.POINTER(H)]
-        L.pbg_ppo_grad_create_ex.restype = I
-    if hasattr(L, "pbg_ppo_opt_create"):  # the advantage normaliser and the clip + Adam step
-        I64P = ctypes.POINTER(ctypes.c_int64)
-        L.pbg_adv_norm.argtypes = [I, I, P, P, P, P]
-        L.pbg_adv_norm_host.argtypes = [I, I, P, P, P]
-        L.pbg_ppo_opt_create.argtypes = [I, I, I64P, ctypes.POINTER(H)]
-        L.pbg_ppo_opt_destroy.argtypes = [H]
-        L.pbg_ppo_opt_destroy.restype = None
-        L.pbg_ppo_opt_step.argtypes = [H, P, P]
-        L.pbg_ppo_opt_reset.argtypes = [H, P]
-        L.pbg_ppo_opt_get_state.argtypes = [H, P, P, P, P]
-        L.pbg_ppo_opt_host.argtypes = [I, I64P, P]
-        for f in PPO_OPT_EXPORTED:
-            if f != "pbg_ppo_opt_destroy":
-                getattr(L, f).restype = I
-    if hasattr(L, "pbg_perm_create"):  # counter-based permutations and the on-device learning rate
-        U64, U32, D = ctypes.c_uint64, ctypes.c_uint32, ctypes.c_double
-        L.pbg_perm_create.argtypes = [I, U64, ctypes.POINTER(H)]
-        L.pbg_perm_destroy.argtypes = [H]
-        L.pbg_perm_destroy.restype = None
-        L.pbg_perm_fill.argtypes = [H, I, I, P, P]
-        L.pbg_perm_set_counter.argtypes = [H, U32, P]
-        L.pbg_perm_get_counter.argtypes = [H, P, P]
-        L.pbg_perm_host.argtypes = [U64, U32, I, I, P]
-        L.pbg_ppo_lr_linear.argtypes = [P, U32, D, P, P]
-        L.pbg_ppo_lr_linear_host.argtypes = [P, U32, D, P]
-        for f in PERM_EXPORTED:
-            if f != "pbg_perm_destroy":
-                getattr(L, f).restype = I
-    if hasattr(L, "pbg_ppo_grad_run_part"):  # the gradient as parts and the statistics' slots
-        L.pbg_ppo_grad_geometry.argtypes = [H, I, ctypes.POINTER(I), ctypes.POINTER(ctypes.c_int64)]
-        L.pbg_ppo_grad_run_part.argtypes = [H, ctypes.POINTER(PPOGradIO), I, I, P, P, P]
-        L.pbg_ppo_grad_reduce.argtypes = [H, ctypes.POINTER(PPOGradIO), I, P, P, P]
-        L.pbg_obs_stats_get_slots.argtypes = [H, I, I, P, P, P]
-        L.pbg_obs_stats_set_slots.argtypes = [H, I, I, P, P, P]
-        for f in PPO_PARTS_EXPORTED:
-            getattr(L, f).restype = I
-    if hasattr(L, "pbg_population_act_where"):  # truncation bootstrapping: the masked actor launch and its GAE
-        D = ctypes.c_double
-        L.pbg_population_act_where.argtypes = [H, I, I, P, P, P, P]
-        L.pbg_gae_trunc.argtypes = [I, I, P, P, P, P, P, D, D, P, P, P]
-        L.pbg_gae_trunc_host.argtypes = [I, I, P, P, P, P, P, D, D, P, P]
-        for f in TRUNC_EXPORTED:
-            getattr(L, f).restype = I
-    if hasattr(L, "pbg_ppo_gate"):  # value clipping and the KL gate
-        L.pbg_ppo_gate_reset.argtypes = [P, P]
-        L.pbg_ppo_gate.argtypes = [P, ctypes.c_double, P, P]
-        L.pbg_ppo_gate_host.argtypes = [P, ctypes.c_double, P]
-        for f in PPO_GATE_EXPORTED:
-            getattr(L, f).restype = I
-    if hasattr(L, "pbg_ret_stats_create"):  # reward scaling by a running std of the discounted return
-        D, F = ctypes.c_double, ctypes.c_float
-        L.pbg_ret_stats_create.argtypes = [I, I, I, D, ctypes.POINTER(H)]
-        L.pbg_ret_stats_destroy.argtypes = [H]
-        L.pbg_ret_stats_destroy.restype = None
-        L.pbg_ret_stats_walk.argtypes = [H, I, I, I, P, P, P]
-        L.pbg_ret_stats_finalize.argtypes = [H, I, D, P]
-        L.pbg_ret_stats_apply.argtypes = [H, I, F, P, P, P]
-        L.pbg_ret_stats_reset.argtypes = [H, P]
-        L.pbg_ret_stats_get_slots.argtypes = [H, I, I, P, P, P]
-        L.pbg_ret_stats_set_slots.argtypes = [H, I, I, P, P, P]
-        L.pbg_ret_stats_get_totals.argtypes = [H, P, P, P]
-        L.pbg_ret_stats_set_totals.argtypes = [H, P, P, P]
-        for f in ("carry", "scale"):
-            getattr(L, f"pbg_ret_stats_get_{f}").argtypes = [H, P, P]
-            getattr(L, f"pbg_ret_stats_set_{f}").argtypes = [H, P, P]
-        for f in RET_STATS_EXPORTED:
-            if f != "pbg_ret_stats_destroy":
-                getattr(L, f).restype = I
-    for f in ("pbg_info", "pbg_reset", "pbg_step", "pbg_step_ex", "pbg_get_state", "pbg_set_state",
-              "pbg_pack_record_sizes", "pbg_pack", "pbg_create_debug", "pbg_sample_actions", "pbg_create_ex",
-              "pbg_default_sim_params", "pbg_get_sim_params", "pbg_create_v2", "pbg_precision"):
-        getattr(L, f).restype = I
+    for group, sigs in SIGNATURES.items():
+        if group != "core" and not hasattr(L, next(iter(sigs))):
+            continue
+        for name, (restype, argtypes) in sigs.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
     _lib = L
     return L
-
-
-POLICY_EXPORTED = ("pbg_policy_create", "pbg_policy_destroy", "pbg_policy_act", "pbg_policy_act_host", "pbg_rollout")
-POPULATION_EXPORTED = ("pbg_population_create", "pbg_population_destroy", "pbg_population_noise",
-                       "pbg_population_noise_host", "pbg_population_perturb", "pbg_population_set_member",
-                       "pbg_population_get_member", "pbg_population_act", "pbg_rollout_population",
-                       "pbg_population_fitness", "pbg_population_grad")
-OBS_NORM_EXPORTED = ("pbg_obs_stats_create", "pbg_obs_stats_destroy", "pbg_obs_stats_update", "pbg_obs_stats_finalize",
-                     "pbg_obs_stats_get_totals", "pbg_obs_stats_set_totals", "pbg_policy_set_obs_norm",
-                     "pbg_population_set_obs_norm", "pbg_policy_attach_obs_stats", "pbg_population_attach_obs_stats")
-ACTION_NOISE_EXPORTED = ("pbg_action_noise_create", "pbg_action_noise_destroy", "pbg_action_noise_set_std",
-                         "pbg_action_noise_set_counter", "pbg_action_noise_get_counter", "pbg_action_noise_set_eps2_traj",
-                         "pbg_action_noise_fill", "pbg_action_noise_host", "pbg_policy_attach_action_noise",
-                         "pbg_population_attach_action_noise", "pbg_gae", "pbg_gae_host")
-PPO_GRAD_EXPORTED = ("pbg_ppo_grad_create", "pbg_ppo_grad_destroy", "pbg_ppo_grad_run", "pbg_ppo_grad_host")
-PPO_GRAD_EX_EXPORTED = ("pbg_ppo_grad_create_ex",)
-PPO_OPT_EXPORTED = ("pbg_adv_norm", "pbg_adv_norm_host", "pbg_ppo_opt_create", "pbg_ppo_opt_destroy", "pbg_ppo_opt_step",
-                    "pbg_ppo_opt_reset", "pbg_ppo_opt_get_state", "pbg_ppo_opt_host")
-PERM_EXPORTED = ("pbg_perm_create", "pbg_perm_destroy", "pbg_perm_fill", "pbg_perm_set_counter", "pbg_perm_get_counter",
-                 "pbg_perm_host", "pbg_ppo_lr_linear", "pbg_ppo_lr_linear_host")
-PPO_PARTS_EXPORTED = ("pbg_ppo_grad_geometry", "pbg_ppo_grad_run_part", "pbg_ppo_grad_reduce", "pbg_obs_stats_get_slots",
-                      "pbg_obs_stats_set_slots")
-TRUNC_EXPORTED = ("pbg_population_act_where", "pbg_gae_trunc", "pbg_gae_trunc_host")
-RET_STATS_EXPORTED = ("pbg_ret_stats_create", "pbg_ret_stats_destroy", "pbg_ret_stats_walk", "pbg_ret_stats_finalize",
-                      "pbg_ret_stats_apply", "pbg_ret_stats_reset", "pbg_ret_stats_get_slots", "pbg_ret_stats_set_slots",
-                      "pbg_ret_stats_get_totals", "pbg_ret_stats_set_totals", "pbg_ret_stats_get_carry",
-                      "pbg_ret_stats_set_carry", "pbg_ret_stats_get_scale", "pbg_ret_stats_set_scale")
-PPO_GATE_EXPORTED = ("pbg_ppo_gate_reset", "pbg_ppo_gate", "pbg_ppo_gate_host")
-EXPORTED =("pbg_create", "pbg_create_debug", "pbg_create_ex", "pbg_create_v2", "pbg_precision",
-            "pbg_default_sim_params", "pbg_get_sim_params",
-            "pbg_destroy", "pbg_info", "pbg_reset", "pbg_step", "pbg_step_ex",
-            "pbg_get_state", "pbg_set_state", "pbg_pack_record_sizes", "pbg_pack", "pbg_sample_actions",
-            "pbg_debug_poison", "pbg_last_error") + POLICY_EXPORTED + POPULATION_EXPORTED + OBS_NORM_EXPORTED + \
-    ACTION_NOISE_EXPORTED + PPO_GRAD_EXPORTED + PPO_OPT_EXPORTED + PERM_EXPORTED + PPO_GRAD_EX_EXPORTED + PPO_PARTS_EXPORTED + \
-    TRUNC_EXPORTED + RET_STATS_EXPORTED + PPO_GATE_EXPORTED
 
 
 def check(rc: int, what: str):

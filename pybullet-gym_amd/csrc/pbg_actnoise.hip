@@ -43,11 +43,6 @@ __global__ __launch_bounds__(256) void gae_kernel(int T, int n, const float* __r
   if (e < n) gae_env<false>(T, n, e, rew, done, nullptr, value, nullptr, gamma, gl, adv, ret);
 }
 
-int launched(const char* what) {
-  const int e = (int)hipGetLastError();
-  return e ? hip_fail(e, what) : PBG_OK;
-}
-
 bool gae_args_ok(int T, int n, const void* rew, const void* done, const void* value, const void* adv, const void* ret) {
   return T >= 1 && n >= 1 && rew && done && value && adv && ret;
 }

@@ -141,11 +141,6 @@ __global__ void lr_linear_kernel(const uint32_t* __restrict__ it, uint32_t n_tot
   if (blockIdx.x == 0 && threadIdx.x == 0) *lr_out = lr_linear(*it, n_total, lr0);
 }
 
-int launched(const char* what) {
-  const int e = (int)hipGetLastError();
-  return e ? hip_fail(e, what) : PBG_OK;
-}
-
 int fill_args(const char* who, int n_rows, int n_perms, const int64_t* out) {
   if (n_rows < 1 || n_perms < 1 || n_perms > MAX_PERMS || !out) {
     char msg[200];

@@ -251,13 +251,8 @@ int pbg::policy::rollout_loop(const char* who, pbg_handle* h, const pbg_rollout_
   constexpr uint32_t v1_size = (uint32_t)(offsetof(pbg_rollout_io_t, done_traj) + sizeof(uint8_t*));
   constexpr uint32_t v2_size = (uint32_t)(offsetof(pbg_rollout_io_t, term_obs_traj) + sizeof(float*));
   static_assert(v2_size == sizeof(pbg_rollout_io_t), "a field appended to pbg_rollout_io_t needs its version here");
-  if (uio->struct_size != v1_size && uio->struct_size != v2_size) {
-    snprintf(msg, sizeof(msg), "%s: io->struct_size %u is not a pbg_rollout_io_t size", who, uio->struct_size);
-    return pbg::capi_fail(PBG_E_ARG, msg);
-  }
   pbg_rollout_io_t io_copy;
-  memset(&io_copy, 0, sizeof(io_copy));
-  memcpy(&io_copy, uio, uio->struct_size);
+  if (const int rc = pbg::read_versioned(who, "pbg_rollout_io_t", uio, {v1_size, v2_size}, &io_copy)) return rc;
   const pbg_rollout_io_t* io = &io_copy;
   const int dev = pbg::handle_device(h);
   if (a.device != dev) {

@@ -511,6 +511,12 @@ inline int hip_fail(int e, const char* what) {
   return pbg::capi_fail(PBG_E_HIP, msg);
 }
 
+// PBG_OK when the launch just enqueued left no error behind; `what` names it in the message
+inline int launched(const char* what) {
+  const int e = (int)hipGetLastError();
+  return e ? hip_fail(e, what) : PBG_OK;
+}
+
 // PBG_OK when HIP device `device` exists
 inline int check_device(const char* who, int device) {
   int ndev = 0;

@@ -108,11 +108,6 @@ __global__ __launch_bounds__(256) void copy_rows_kernel(int D, size_t src_stride
 }
 
 // ---------------------------------------------------------------- host side
-int launched(const char* what) {
-  const int e = (int)hipGetLastError();
-  return e ? hip_fail(e, what) : PBG_OK;
-}
-
 // the largest population whose member count and whose global pair indices stay inside an int
 bool pairs_ok(int n_pairs, int pair0) { return n_pairs >= 1 && n_pairs <= INT_MAX / 2 && pair0 >= 0 && pair0 <= INT_MAX - n_pairs; }
 

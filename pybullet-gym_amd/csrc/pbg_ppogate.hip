@@ -29,11 +29,6 @@ __global__ void ppo_gate_reset_kernel(int32_t* gate) {
   }
 }
 
-int launched(const char* what) {
-  const int e = (int)hipGetLastError();
-  return e ? hip_fail(e, what) : PBG_OK;
-}
-
 }  // namespace
 
 extern "C" {

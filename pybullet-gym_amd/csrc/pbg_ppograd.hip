@@ -350,12 +350,8 @@ int check_io(const char* who, const pbg_ppo_grad_io_t* uio, pbg_ppo_grad_io_t* i
   constexpr uint32_t v1_size = (uint32_t)(offsetof(pbg_ppo_grad_io_t, v_out) + sizeof(float*));
   // the two versions: the one that ends with v_out and this library's, which appends value_old, gate and vf_clip (NULL,
   // NULL and 0 for the first)
-  if (uio->struct_size != v1_size && uio->struct_size != (uint32_t)sizeof(pbg_ppo_grad_io_t)) {
-    snprintf(msg, sizeof(msg), "%s: io->struct_size %u is not a pbg_ppo_grad_io_t size", who, uio->struct_size);
-    return pbg::capi_fail(PBG_E_ARG, msg);
-  }
-  memset(io, 0, sizeof(*io));
-  memcpy(io, uio, uio->struct_size);
+  if (const int rc = pbg::read_versioned(who, "pbg_ppo_grad_io_t", uio, {v1_size, (uint32_t)sizeof(pbg_ppo_grad_io_t)}, io))
+    return rc;
   if (io->mb_rows < 1 || io->batch_rows < 1 || (!io->idx && io->mb_rows > io->batch_rows)) {
     snprintf(msg, sizeof(msg), "%s: mb_rows %d and batch_rows %d must be >= 1, and mb_rows <= batch_rows without idx", who,
              io->mb_rows, io->batch_rows);

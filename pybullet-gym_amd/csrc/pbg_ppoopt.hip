@@ -263,11 +263,6 @@ __global__ void ppoopt_reset_kernel(OptState* st) {
   }
 }
 
-int launched(const char* what) {
-  const int e = (int)hipGetLastError();
-  return e ? hip_fail(e, what) : PBG_OK;
-}
-
 int adv_norm_args(const char* who, int n_batch, int n_rows, const float* adv, const int64_t* idx, const float* out) {
   if (n_rows < 2 || n_batch < 1 || (!idx && n_rows > n_batch) || !adv || !out) {
     char msg[200];
@@ -289,12 +284,8 @@ int check_io(const char* who, const pbg_ppo_opt_io_t* uio, int n_blocks, pbg_ppo
   constexpr uint32_t v2_size = (uint32_t)(offsetof(pbg_ppo_opt_io_t, lr_ptr) + sizeof(double*));
   // the three versions: the one that ends with bpow, the one that appends lr_ptr and this library's, which appends gate
   // and a reserved word (NULL for what a version lacks); the size between the last two stays refused
-  if (uio->struct_size != v1_size && uio->struct_size != v2_size && uio->struct_size != (uint32_t)sizeof(pbg_ppo_opt_io_t)) {
-    snprintf(msg, sizeof(msg), "%s: io->struct_size %u is not a pbg_ppo_opt_io_t size", who, uio->struct_size);
-    return pbg::capi_fail(PBG_E_ARG, msg);
-  }
-  memset(io, 0, sizeof(*io));
-  memcpy(io, uio, uio->struct_size);
+  if (const int rc = pbg::read_versioned(who, "pbg_ppo_opt_io_t", uio, {v1_size, v2_size, (uint32_t)sizeof(pbg_ppo_opt_io_t)}, io))
+    return rc;
   for (int b = 0; b < n_blocks; b++)
     if (!io->param[b] || !io->grad[b]) {
       snprintf(msg, sizeof(msg), "%s: param[%d] or grad[%d] is NULL", who, b, b);

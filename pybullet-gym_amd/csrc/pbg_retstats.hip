@@ -214,11 +214,6 @@ __global__ __launch_bounds__(256) void ret_reset_kernel(long long words, uint64_
   if (i == 3) *scale = 1.0f;
 }
 
-int launched(const char* what) {
-  const int e = (int)hipGetLastError();
-  return e ? hip_fail(e, what) : PBG_OK;
-}
-
 int tiles(int n) { return (n + TILE - 1) / TILE; }
 
 // bytes from src to dst on the object's side: a launch on `stream`, or memcpy for a host object

@@ -81,11 +81,6 @@ __global__ __launch_bounds__(256) void gae_trunc_kernel(int T, int n, const floa
   if (e < n) gae_env<true>(T, n, e, rew, done, trunc, value, term_value, gamma, gl, adv, ret);
 }
 
-int launched(const char* what) {
-  const int e = (int)hipGetLastError();
-  return e ? hip_fail(e, what) : PBG_OK;
-}
-
 bool gae_trunc_args_ok(int T, int n, const void* rew, const void* done, const void* trunc, const void* value,
                        const void* term_value, const void* adv, const void* ret) {
   return T >= 1 && n >= 1 && rew && done && trunc && value && term_value && adv && ret;

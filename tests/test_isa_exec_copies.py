@@ -5,7 +5,7 @@ into AGPRs inside a divergent region's join block, before the `s_or_b64 exec, ex
 the region's lanes; lanes outside the region then read stale registers (found on the GPU by
 register-file poisoning, tools/vgpr_poison_probe.py).  tools/isa_uninit.py --exec-copies flags that
 pattern; these tests pin the checker on a synthetic reproducer and run it over the product's float64
-quad kernels and over the learner's six translation units compiled from this tree.  CPU only (hipcc
+quad kernels and over every translation unit of the learner compiled from this tree.  CPU only (hipcc
 cross-compiles gfx950).
 """
 import os
@@ -103,8 +103,8 @@ def test_product_float64_quad_kernel_has_no_partial_exec_copies(tmp_path, robot)
         assert isa_uninit.exec_copies(isa_uninit.parse(str(out), k)) == [], k
 
 
-# the learner's translation units (Makefile SHARED_OBJS) and the kernels each must hold, by a substring of the
-# mangled name: 24 in all
+# the learner's translation units (Makefile LEARNER_UNITS) and the kernels each must hold, by a substring of the
+# mangled name: 43 in all.  A unit added to the Makefile must be added here.
 LEARNER_UNITS = {
     "policy": [f"actor_kernelILi{mode}ELb{sample}E" for sample in (0, 1) for mode in (0, 1, 2)] +
               ["book_kernelILb0E", "book_kernelILb1E"],
@@ -113,21 +113,35 @@ LEARNER_UNITS = {
     "actnoise": ["action_noise_fill_kernel", "gae_kernel"],
     "ppograd": ["ppograd_tiles_kernelILb1E", "ppograd_tiles_kernelILb0E", "ppograd_reduce_kernel"],
     "ppoopt": ["adv_norm_kernel", "ppoopt_sumsq_kernel", "ppoopt_step_kernel", "ppoopt_reset_kernel"],
+    "perm": ["perm_fill_kernel", "perm_advance_kernel", "perm_set_kernel", "lr_linear_kernel"],
+    "ppograd_mfma": ["ppograd_mfma_kernelILb1E", "ppograd_mfma_kernelILb0E"],
+    "obsslots": ["obs_stats_slots_kernelILb0E", "obs_stats_slots_kernelILb1E"],
+    "trunc": ["gae_trunc_kernel", "actor_where_kernelILi0E", "actor_where_kernelILi1E"],
+    "retstats": ["ret_walk_kernel", "ret_finalize_kernel", "ret_copy_kernel", "ret_reset_kernel", "ret_apply_kernelILb0E",
+                 "ret_apply_kernelILb1E"],
+    "ppogate": ["ppo_gate_kernel", "ppo_gate_reset_kernel"],
 }
+
+
+def compile_unit(tmp_path, unit):
+    """csrc/pbg_<unit>.hip's device ISA, compiled from this tree with the Makefile's HIPFLAGS: the file's path."""
+    out = tmp_path / f"{unit}.s"
+    subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize",
+                           "--cuda-device-only", "-S", "-o", str(out),
+                           os.path.join(REPO, "pybullet-gym_amd", "csrc", f"pbg_{unit}.hip")],
+                          stderr=subprocess.DEVNULL)
+    return out
 
 
 @pytest.mark.timeout(900)
 @pytest.mark.skipif(shutil.which("/opt/rocm/bin/hipcc") is None, reason="hipcc absent")
 @pytest.mark.parametrize("unit", list(LEARNER_UNITS))
 def test_learner_kernels_have_no_partial_exec_copies(tmp_path, unit):
-    """The actors, the population's and the statistics' kernels, the noise fill, GAE, the PPO gradient (whose
-    register path runs into the AGPR half) and the optimiser step, compiled from this tree with the Makefile's
-    HIPFLAGS: every kernel of the unit is there and none holds such a copy."""
-    out = tmp_path / f"{unit}.s"
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize",
-                           "--cuda-device-only", "-S", "-o", str(out),
-                           os.path.join(REPO, "pybullet-gym_amd", "csrc", f"pbg_{unit}.hip")],
-                          stderr=subprocess.DEVNULL)
+    """Every learner unit -- the actors, the population's and the statistics' kernels, the noise fill, GAE, the PPO
+    gradient on both paths (whose register path runs into the AGPR half), the optimiser step, the permutations,
+    truncation, the return statistics and the KL gate: every kernel of the unit is there and none copies a live
+    register inside a divergent region's join block."""
+    out = compile_unit(tmp_path, unit)
     names = isa_uninit.kernels(str(out))
     for want in LEARNER_UNITS[unit]:
         assert sum(want in k for k in names) == 1, (want, names)
@@ -137,11 +151,21 @@ def test_learner_kernels_have_no_partial_exec_copies(tmp_path, unit):
 
 
 def test_the_learner_units_are_the_makefiles():
-    """The list above is the Makefile's SHARED_OBJS: a unit added there must be added here."""
-    mk = open(os.path.join(REPO, "pybullet-gym_amd", "Makefile")).read()
-    line = next(ln for ln in mk.split("\n") if ln.startswith("SHARED_OBJS ="))
-    assert sorted(w.split("/")[-1][:-2] for w in line.split("=")[1].split()) == sorted(LEARNER_UNITS)
-    assert sum(len(v) for v in LEARNER_UNITS.values()) == 24
+    """The table above is the Makefile's LEARNER_UNITS, and that list is what every library variant links
+    (LIB_RULES, TRACE_REST) and what `make policy-report` covers."""
+    mk = open(os.path.join(REPO, "pybullet-gym_amd", "Makefile")).read().split("\n")
+    units = next(ln for ln in mk if ln.startswith("LEARNER_UNITS :=")).split(":=")[1].split()
+    assert sorted(units) == sorted(LEARNER_UNITS) and len(units) == len(set(units)) == 12
+    assert sum(len(v) for v in LEARNER_UNITS.values()) == 43
+    assert "LEARNER_OBJS := $(LEARNER_UNITS:%=$(OBJ)/%.o)" in mk
+    link = next(ln for ln in mk if ln.startswith("$(3):"))
+    assert link.split()[-2:] == ["$(1)/capi.o", "$$(LEARNER_OBJS)"]
+    rest = next(ln for ln in mk if ln.startswith("TRACE_REST ="))
+    assert rest.split()[-2:] == ["$(OBJ)/capi.o", "$(LEARNER_OBJS)"]
+    report = subprocess.run(["make", "-n", "-C", os.path.join(REPO, "pybullet-gym_amd"), "policy-report"],
+                            capture_output=True, text=True, check=True).stdout
+    for u in units:
+        assert report.count(f"-Rpass-analysis=kernel-resource-usage -c -o /dev/null csrc/pbg_{u}.hip") == 1, u
 
 
 @pytest.mark.timeout(900)

@@ -22,6 +22,26 @@ def test_header_declares_the_abi():
         assert n in names
 
 
+def prototypes():
+    """name -> parameter count of every prototype `name ( ... );` of the header, comments stripped."""
+    src = re.sub(r"/\*.*?\*/|//[^\n]*", " ", open(HEADER).read(), flags=re.S)
+    return {name: 0 if params.strip() == "void" else params.count(",") + 1
+            for name, params in re.findall(r"\b(pbg_[a-z_0-9]+)\s*\(([^();]*)\)\s*;", src)}
+
+
+def test_the_signature_table_names_what_the_header_declares():
+    """_native.SIGNATURES, the one place the binding states the ABI, against the header alone (no library)."""
+    assert sorted(_native.EXPORTED) == declared() == sorted(prototypes())
+    assert len(_native.EXPORTED) == len(set(_native.EXPORTED)) == 103
+
+
+def test_every_signature_has_its_prototypes_parameter_count():
+    counts = prototypes()
+    for sigs in _native.SIGNATURES.values():
+        for name, (_, argtypes) in sigs.items():
+            assert len(argtypes) == counts[name], name
+
+
 @pytest.mark.skipif(not os.path.exists(_native.LIB_PATH), reason="libpbg_amd.so not built")
 def test_library_exports_every_declared_symbol():
     lib = ctypes.CDLL(_native.LIB_PATH)

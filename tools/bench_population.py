@@ -35,30 +35,17 @@ another build of libpbg_amd.so (the parent commit's, alternated with this tree's
 """
 from __future__ import annotations
 
-import argparse
-import json
 import os
 import statistics
 import sys
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
+from benchlib import REPO, capture, device_windows, finish, parser, summary, use_library
+
 sys.path.insert(0, os.path.join(REPO, "tests"))
 
 ENV_ID, N = "AntPyBulletEnv-v0", 16384
 K = 20  # steps per graph
 LEGS = {"A": None, "B": 1024, "C": 4096}  # members (None: the shared-weight policy)
-
-
-def capture(fn, dev):
-    import torch
-    s = torch.cuda.Stream(dev)
-    s.wait_stream(torch.cuda.current_stream(dev))
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g, stream=s):
-        fn()
-    torch.cuda.current_stream(dev).wait_stream(s)
-    return g
 
 
 def actors(dev, members):
@@ -79,28 +66,9 @@ def actors(dev, members):
     return out, dims, theta
 
 
-def timed(windows, replays, legs, run, dev, per):
-    """`windows` rounds over the legs, each window `replays` calls of run(leg) between two device events;
-    returns {leg: [microseconds per `per`]}."""
-    import torch
-    stream = torch.cuda.current_stream(dev)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    res = {leg: [] for leg in legs}
-    for _ in range(windows):
-        for leg in legs:
-            torch.cuda.synchronize(dev)
-            e0.record(stream)
-            for _ in range(replays):
-                run(leg)
-            e1.record(stream)
-            torch.cuda.synchronize(dev)
-            res[leg].append(e0.elapsed_time(e1) * 1e3 / (replays * per))
-    return res
-
-
-def summary(w):
-    return {"windows": w, "median": {k: statistics.median(v) for k, v in w.items()},
-            "min": {k: min(v) for k, v in w.items()}, "max": {k: max(v) for k, v in w.items()}}
+def replay_windows(args, dev, graphs):
+    """us per step of the K-step graphs, after one warm replay of each."""
+    return device_windows(dev, {leg: g.replay for leg, g in graphs.items()}, args.windows, args.replays, warmup=1, per=K)
 
 
 def bench_rollout(args, dev):
@@ -116,9 +84,7 @@ def bench_rollout(args, dev):
             envs[leg].rollout(pis[leg], K)
     torch.cuda.synchronize(dev)
     graphs = {leg: capture(lambda leg=leg: envs[leg].rollout(pis[leg], K), dev) for leg in LEGS}
-    for leg in LEGS:
-        graphs[leg].replay()
-    w = timed(args.windows, args.replays, list(LEGS), lambda leg: graphs[leg].replay(), dev, K)
+    w = replay_windows(args, dev, graphs)
     out = summary(w)
     med = out["median"]
     D = pis["B"].n_params
@@ -164,9 +130,7 @@ def bench_obs_norm(args, dev):
             envs[leg].rollout(pis[leg], K)
     torch.cuda.synchronize(dev)
     graphs = {leg: capture(lambda leg=leg: envs[leg].rollout(pis[leg], K), dev) for leg in NORM_LEGS}
-    for leg in NORM_LEGS:
-        graphs[leg].replay()
-    w = timed(args.windows, args.replays, list(NORM_LEGS), lambda leg: graphs[leg].replay(), dev, K)
+    w = replay_windows(args, dev, graphs)
     out = summary(w)
     med = out["median"]
     counted = {}
@@ -221,9 +185,7 @@ def bench_action_noise(args, dev):
             envs[leg].rollout(pis[leg], K)
     torch.cuda.synchronize(dev)
     graphs = {leg: capture(lambda leg=leg: envs[leg].rollout(pis[leg], K), dev) for leg in legs}
-    for leg in legs:
-        graphs[leg].replay()
-    w = timed(args.windows, args.replays, list(legs), lambda leg: graphs[leg].replay(), dev, K)
+    w = replay_windows(args, dev, graphs)
     out = summary(w)
     med = out["median"]
     out.update({"env_id": ENV_ID, "n_envs": N, "precision": 64, "steps_per_graph": K, "replays_per_window": args.replays,
@@ -278,7 +240,7 @@ def bench_gae(args, dev, T=200):
     ta, tr = runs["torch_loop"]()
     runs["pbg_gae"]()
     err = max(float((ta - adv).abs().max()), float((tr - ret).abs().max()))
-    w = timed(args.windows, 5, list(runs), lambda leg: runs[leg](), dev, 1)
+    w = device_windows(dev, runs, args.windows, 5)
     out = summary(w)
     out.update({"T": T, "n": N, "unit": "us per call", "max_abs_difference_from_the_torch_loop": err,
                 "bytes_touched": T * N * (4 + 1 + 4 + 4 + 4) + N * 4,
@@ -294,7 +256,7 @@ def bench_copy(args, dev):
     b = torch.empty_like(a)
     for _ in range(3):
         b.copy_(a)
-    w = timed(args.windows, 10, ["copy"], lambda leg: b.copy_(a), dev, 1)["copy"]
+    w = device_windows(dev, {"copy": lambda: b.copy_(a)}, args.windows, 10)["copy"]
     gbs = [2 * 4 * n / (us * 1e-6) / 1e9 for us in w]
     return {"bytes_each_way": 4 * n, "us": w, "GB_per_s_read_plus_write": {"median": statistics.median(gbs),
                                                                            "min": min(gbs), "max": max(gbs)}}
@@ -320,8 +282,7 @@ def bench_generation(args, dev):
     generation()
     torch.cuda.synchronize(dev)
     g = capture(generation, dev)
-    g.replay()
-    w = timed(args.windows, 20, ["generation"], lambda leg: g.replay(), dev, 1)["generation"]
+    w = device_windows(dev, {"generation": g.replay}, args.windows, 20, warmup=1)["generation"]
     out = {"n_pairs": pop.n_pairs, "params": pop.n_params, "unit": "us per generation (without the rollout)", "us": w,
            "median": statistics.median(w), "min": min(w), "max": max(w)}
     env.close()
@@ -344,25 +305,18 @@ def actor_only(args, dev):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=None, help="default: profiles/population_rollout.json "
-                    "(--obs-norm: profiles/obs_norm_rollout.json)")
+    ap = parser(None, warmup=20)   # --out: profiles/population_rollout.json, obs_norm_rollout.json, action_noise_rollout.json
     ap.add_argument("--obs-norm", action="store_true", help="the observation-normalisation legs only")
     ap.add_argument("--action-noise", action="store_true", help="the action-noise legs and pbg_gae only")
     ap.add_argument("--lib", default=None, help="another build of libpbg_amd.so (the parent commit's, to alternate with)")
     ap.add_argument("--preroll", type=int, default=200)
-    ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--windows", type=int, default=5)
     ap.add_argument("--replays", type=int, default=10, help="graph replays (of 20 steps) per timed window")
     ap.add_argument("--actor-only", action="store_true")
     ap.add_argument("--members", type=int, default=1024)
     args = ap.parse_args()
     import torch
-    import pybulletgym_amd  # noqa: F401
+    use_library(args.lib)
     dev = torch.device("cuda:0")
-    if args.lib:
-        from pybulletgym_amd import _native
-        _native.LIB_PATH = os.path.abspath(args.lib)
     if args.actor_only:
         return actor_only(args, dev)
     if args.out is None:
@@ -374,9 +328,6 @@ def main():
         res = {"rollout": bench_action_noise(args, dev)}
         if hasattr(_native.lib(), "pbg_gae"):
             res["gae"] = bench_gae(args, dev)
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            json.dump(res, f, indent=1)
         r = res["rollout"]
         print("rollout us/step median [min, max]: " + "  ".join(
             f"{leg} {r['median'][leg]:.1f} [{r['min'][leg]:.1f}, {r['max'][leg]:.1f}]" for leg in r["median"]) +
@@ -385,32 +336,24 @@ def main():
             g = res["gae"]
             print("gae us/call median [min, max]: " + "  ".join(
                 f"{k} {g['median'][k]:.1f} [{g['min'][k]:.1f}, {g['max'][k]:.1f}]" for k in g["median"]))
-        print(json.dumps({"done": bool(r["final_obs_equal"]), "out": args.out}))
-        return
+        return finish(res, args.out, bool(r["final_obs_equal"]))
     if args.obs_norm:
         res = {"rollout": bench_obs_norm(args, dev)}
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            json.dump(res, f, indent=1)
         r = res["rollout"]
         print("rollout us/step median [min, max]: " + "  ".join(
             f"{leg} {r['median'][leg]:.1f} [{r['min'][leg]:.1f}, {r['max'][leg]:.1f}]" for leg in NORM_LEGS) +
             f"  same states: {r['final_obs_equal']}")
-        print(json.dumps({"done": bool(r["final_obs_equal"]), "out": args.out}))
-        return
+        return finish(res, args.out, bool(r["final_obs_equal"]))
     res = {"rollout": bench_rollout(args, dev), "copy": bench_copy(args, dev), "generation": bench_generation(args, dev)}
     bw = res["copy"]["GB_per_s_read_plus_write"]["median"]
     res["actor_weight_stream_at_copy_bandwidth_us"] = {
         leg: b / (bw * 1e9) * 1e6 for leg, b in res["rollout"]["actor_weight_bytes_per_step"].items()}
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(res, f, indent=1)
     r = res["rollout"]
     print("rollout us/step median [min, max]: " + "  ".join(
         f"{leg} {r['median'][leg]:.1f} [{r['min'][leg]:.1f}, {r['max'][leg]:.1f}]" for leg in LEGS) +
         f"  B-A {r['B_minus_A_us']:.1f}  C-A {r['C_minus_A_us']:.1f}  same states: {r['final_obs_equal']}")
     print(f"copy {bw:.0f} GB/s (read + write)  generation {res['generation']['median']:.1f} us")
-    print(json.dumps({"done": bool(r["final_obs_equal"]), "out": args.out}))
+    finish(res, args.out, bool(r["final_obs_equal"]))
 
 
 if __name__ == "__main__":

@@ -1,7 +1,6 @@
 #!/usr/bin/env python3
 """What value clipping and the KL gate cost, and that with both off nothing got slower.
-tools/bench_ppo_trunc.py's protocol: warm-up, windows bracketed by a synchronise, the legs alternated per window, medians
-with [min, max]; a library is loaded once per process, so a round is one child process per library, the parent's first.
+tools/benchlib.py's protocol; a round is one child process per library, the parent's first.
 
   grad      PPOGrad.run (two launches) on both paths at the pendulum trainer's shape, (5, 64, 64, 1) x 2,048 rows of
             8,192, and at Ant's, (28, 128, 64, 8) x 131,072 rows:
@@ -20,45 +19,14 @@ with [min, max]; a library is loaded once per process, so a round is one child p
 """
 from __future__ import annotations
 
-import argparse
 import json
-import os
 import statistics
-import subprocess
-import sys
-import time
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
+from benchlib import ENV_ID, ENVS, HP, device_windows, finish, parser, pendulum_windows, run_child, summary, use_library
 
-HP = dict(hidden=(64, 64), steps=32, lr=3e-3, epochs=4, minibatches=4, log_std=-0.5)
+BASE = dict(backward="hip", optimizer="hip", permutation="device", graph="iteration")
 ITER_LEGS = {"plain": {}, "plain_beside": {}, "both": dict(vf_clip=0.2, target_kl=0.02)}
 SHAPES = {"pendulum": ((5, 64, 64, 1), 8192, 2048), "ant": ((28, 128, 64, 8), 131072, 131072)}
-
-
-def summary(w):
-    return {"windows": w, "median": {k: statistics.median(v) for k, v in w.items()}, "min": {k: min(v) for k, v in w.items()},
-            "max": {k: max(v) for k, v in w.items()}}
-
-
-def timed(torch, dev, legs, args, calls):
-    """us per call of every leg, alternated per window."""
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    stream = torch.cuda.current_stream(dev)
-    for _ in range(args.warmup):
-        for f in legs.values():
-            f()
-    w = {leg: [] for leg in legs}
-    for _ in range(args.windows):
-        for leg, f in legs.items():
-            torch.cuda.synchronize(dev)
-            e0.record(stream)
-            for _ in range(calls):
-                f()
-            e1.record(stream)
-            torch.cuda.synchronize(dev)
-            w[leg].append(e0.elapsed_time(e1) * 1e3 / calls)
-    return w
 
 
 def batch_of(torch, np, dev, dims, B, Bm):
@@ -89,7 +57,8 @@ def bench_grad(args, dev, options):
                 gate = KLGate(dev)
                 legs["value_old"] = lambda: g.run(*params, *data, value_old=value_old, vf_clip=0.2, **kw)
                 legs["gate_open"] = lambda: g.run(*params, *data, gate=gate.gate, **kw)
-            w = timed(torch, dev, legs, args, args.calls if shape == "pendulum" else max(2, args.calls // 10))
+            w = device_windows(dev, legs, args.windows, args.calls if shape == "pendulum" else max(2, args.calls // 10),
+                               warmup=args.warmup)
             assert bool(torch.isfinite(out["grad_actor"]).all())
             res[f"{shape}_{path}"] = w
             g.close()
@@ -122,7 +91,7 @@ def bench_minibatch(args, dev):
         legs = {"six_launches_open": lambda: minibatch(gates["open"], 1e30),
                 "six_launches_stopped": lambda: minibatch(gates["stopped"], 1e30),
                 "gate_launch": lambda: gates["open"].check(stats, 1e30)}
-        res[path] = timed(torch, dev, legs, args, args.calls)
+        res[path] = device_windows(dev, legs, args.windows, args.calls, warmup=args.warmup)
         assert gates["stopped"].state.cpu().tolist()[0] == 1 and gates["open"].state.cpu().tolist()[0] == 0
         g.close()
         opt.close()
@@ -130,41 +99,20 @@ def bench_minibatch(args, dev):
 
 
 def bench_iterate(args, dev, legs):
-    import torch
-    from pybulletgym_amd.ppo import PPO
-    from pybulletgym_amd.vec_env import VecEnv
-    tr = {}
-    for leg in legs:
-        env = VecEnv("InvertedPendulumPyBulletEnv-v0", 256, device=dev, seed=0, autoreset=True, precision=64)
-        tr[leg] = (env, PPO(env, seed=0, backward="hip", optimizer="hip", permutation="device", graph="iteration", **HP,
-                            **ITER_LEGS[leg]))
-        for _ in range(3):
-            tr[leg][1].iterate()
-    w, updates = {leg: [] for leg in tr}, {leg: [] for leg in tr}
-    for _ in range(args.windows):
-        for leg, (_, ppo) in tr.items():
-            torch.cuda.synchronize(dev)
-            t0 = time.perf_counter()
-            for _ in range(args.iterations):
-                st = ppo.iterate()
-            torch.cuda.synchronize(dev)
-            w[leg].append((time.perf_counter() - t0) * 1e3 / args.iterations)
-            if "updates" in st:
-                updates[leg].append(int(st["updates"]))
-    finite = {leg: bool(torch.isfinite(ppo.actor_theta.data).all()) for leg, (_, ppo) in tr.items()}
-    for env, ppo in tr.values():
-        ppo.close()
-        env.close()
+    updates = {leg: [] for leg in legs}
+
+    def after(leg, ppo):   # what the window's last iterate() reported as stats["updates"]
+        if ppo.kl_gate is not None:
+            updates[leg].append(int(ppo.kl_gate.state[1]))
+
+    w, finite = pendulum_windows(dev, {leg: ITER_LEGS[leg] for leg in legs}, args.windows, args.iterations, base=BASE, after=after)
     return w, finite, {k: v for k, v in updates.items() if v}
 
 
 def child(args):
     """One process, one library: its legs' windows as one JSON line."""
     import torch
-    import pybulletgym_amd  # noqa: F401
-    from pybulletgym_amd import _native
-    if args.lib:
-        _native.LIB_PATH = os.path.abspath(args.lib)
+    use_library(args.lib)
     dev = torch.device("cuda:0")
     out = {}
     if args.child == "plain":
@@ -177,17 +125,6 @@ def child(args):
     print(json.dumps(out))
 
 
-def run_child(args, what, lib=None):
-    cmd = [sys.executable, os.path.abspath(__file__), "--child", what, "--warmup", str(args.warmup), "--windows",
-           str(args.windows), "--calls", str(args.calls), "--iterations", str(args.iterations)]
-    if lib:
-        cmd += ["--lib", lib]
-    p = subprocess.run(cmd, capture_output=True, text=True, timeout=400)
-    if p.returncode:
-        raise RuntimeError(f"{' '.join(cmd)} failed ({p.returncode}):\n{p.stderr[-3000:]}")
-    return json.loads(p.stdout.strip().splitlines()[-1])
-
-
 def pool(into, got, rename=lambda k: k):
     for group, legs in got.items():
         for leg, v in legs.items():
@@ -195,34 +132,26 @@ def pool(into, got, rename=lambda k: k):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "ppo_vclip_klstop.json"))
-    ap.add_argument("--lib", default=None, help="another build of libpbg_amd.so (the parent commit's, to alternate with)")
-    ap.add_argument("--rounds", type=int, default=3, help="child processes per library")
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--windows", type=int, default=5)
-    ap.add_argument("--calls", type=int, default=40, help="calls per timed window at the pendulum shape (a tenth at Ant's)")
-    ap.add_argument("--iterations", type=int, default=5, help="PPO.iterate() calls per timed window")
-    ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
-    args = ap.parse_args()
+    args = parser("ppo_vclip_klstop.json", calls=40, calls_help="calls per timed window at the pendulum shape (a tenth at Ant's)",
+                  iterations_help="PPO.iterate() calls per timed window", rounds=3).parse_args()
     if args.child:
         return child(args)
     grad, mb, it, updates, rounds = {}, {}, {}, [], []
     for r in range(args.rounds):
         this = {}
         if args.lib:
-            got = run_child(args, "plain", args.lib)
+            got = run_child(__file__, "plain", args, args.lib, timeout=400)
             pool(grad, got["grad"], lambda k: "parent_" + k)
             pool(it, {"iterate": got["iterate"]}, lambda k: "parent_" + k)
             this["parent"] = {k: statistics.median(v["plain"]) for k, v in got["grad"].items()}
             this["parent"]["iterate"] = statistics.median(got["iterate"]["plain"])
-        got = run_child(args, "plain")
+        got = run_child(__file__, "plain", args, timeout=400)
         assert all(got["finite"].values()), got["finite"]
         pool(grad, got["grad"])
         pool(it, {"iterate": got["iterate"]})
         this["this_tree"] = {k: statistics.median(v["plain"]) for k, v in got["grad"].items()}
         this["this_tree"]["iterate"] = statistics.median(got["iterate"]["plain"])
-        got = run_child(args, "options")
+        got = run_child(__file__, "options", args, timeout=400)
         assert all(got["finite"].values()), got["finite"]
         pool(grad, got["grad"], lambda k: k if k != "plain" else "plain_beside")
         pool(mb, got["minibatch"])
@@ -237,8 +166,7 @@ def main():
                minibatch={k: dict(summary(v), unit="us", shape=SHAPES["pendulum"][0], rows=SHAPES["pendulum"][2])
                           for k, v in mb.items()},
                iterate=dict(summary(it["iterate"]), unit="ms per PPO.iterate()", updates_of_both_per_window_end=updates,
-                            trainer=dict(HP, env_id="InvertedPendulumPyBulletEnv-v0", envs=256, backward="hip", optimizer="hip",
-                                         permutation="device", graph="iteration")))
+                            trainer=dict(HP, env_id=ENV_ID, envs=ENVS, **BASE)))
     if args.lib:
         # each median of this tree against the parent's median and the parent's own round-to-round spread
         verdict = {}
@@ -259,10 +187,7 @@ def main():
         f"{k} {s['median'][k]:.3f} [{s['min'][k]:.3f}, {s['max'][k]:.3f}]" for k in s["median"]) + f"  updates {updates}", flush=True)
     if args.lib:
         print(json.dumps(res["options_off_vs_parent"], indent=1))
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(res, f, indent=1)
-    print(json.dumps({"done": True, "out": args.out}))
+    finish(res, args.out)
 
 
 if __name__ == "__main__":

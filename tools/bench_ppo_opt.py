@@ -11,34 +11,18 @@ Legs of one minibatch step from the same data, eager launches as the trainer iss
   opt_step    pbg_ppo_opt_step alone (bytes/s: 7 floats read or written per element)
 
 Then one whole PPO.iterate() of the pendulum trainer (256 envs x 32 steps, 4 epochs x 4 minibatches), all with
-backward="hip": optimizer="torch", optimizer="hip", and optimizer="hip" with graph=True.  Warm-up, five windows
-bracketed by device events (iterate: a host clock around a synchronise), the legs alternated per window, medians
-with [min, max].
+backward="hip": optimizer="torch", optimizer="hip", and optimizer="hip" with graph=True.  tools/benchlib.py's protocol.
 
   python tools/bench_ppo_opt.py [--out profiles/ppo_opt.json]
 """
 from __future__ import annotations
 
-import argparse
-import json
 import math
-import os
-import statistics
-import sys
-import time
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
-sys.path.insert(0, os.path.join(REPO, "tools"))
-
-import bench_ppo_update as base  # noqa: E402
+import bench_ppo_update as base
+from benchlib import ENV_ID, ENVS, HP, device_windows, finish, parser, pendulum_windows, summary
 
 LR, EPS, MAX_GRAD_NORM = 1e-5, 1e-5, 0.5   # a small lr: hundreds of timed steps on one minibatch stay finite
-
-
-def summary(w):
-    return {"windows": w, "median": {k: statistics.median(v) for k, v in w.items()}, "min": {k: min(v) for k, v in w.items()},
-            "max": {k: max(v) for k, v in w.items()}}
 
 
 def bench_shape(name, dims, B, Bm, args, dev):
@@ -108,22 +92,7 @@ def bench_shape(name, dims, B, Bm, args, dev):
     adam_o = AdamClip([p.numel() for p in p_o], dev)
     legs = {"torch": torch_leg, "hip_grad": hip_grad_leg, "hip": hip_leg, "adv_norm": lambda: adv_norm(adv, idx, out=pair),
             "opt_step": lambda: adam_o.step(p_o, g_o, LR, (0.9, 0.999), EPS, MAX_GRAD_NORM)}
-    for _ in range(args.warmup):
-        for f in legs.values():
-            f()
-    torch.cuda.synchronize(dev)
-    stream = torch.cuda.current_stream(dev)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    w = {leg: [] for leg in legs}
-    for _ in range(args.windows):
-        for leg, f in legs.items():
-            torch.cuda.synchronize(dev)
-            e0.record(stream)
-            for _ in range(args.calls):
-                f()
-            e1.record(stream)
-            torch.cuda.synchronize(dev)
-            w[leg].append(e0.elapsed_time(e1) * 1e3 / args.calls)
+    w = device_windows(dev, legs, args.windows, args.calls, warmup=args.warmup)
     finite = all(bool(torch.isfinite(p).all()) for p in p_h + [q.data for q in p_t + p_g])
     for o in (g, adam, adam_o):
         o.close()
@@ -136,30 +105,9 @@ def bench_shape(name, dims, B, Bm, args, dev):
 
 
 def bench_iterate(args, dev):
-    import torch
-    from pybulletgym_amd.ppo import PPO
-    from pybulletgym_amd.vec_env import VecEnv
-    hp = dict(hidden=(64, 64), steps=32, lr=3e-3, epochs=4, minibatches=4, log_std=-0.5)
     modes = {"torch_opt": dict(optimizer="torch"), "hip_opt": dict(optimizer="hip"), "hip_opt_graph": dict(optimizer="hip", graph=True)}
-    tr = {}
-    for mode, kw in modes.items():
-        env = VecEnv("InvertedPendulumPyBulletEnv-v0", 256, device=dev, seed=0, autoreset=True, precision=64)
-        tr[mode] = (env, PPO(env, seed=0, backward="hip", **hp, **kw))
-        for _ in range(3):
-            tr[mode][1].iterate()
-    w = {mode: [] for mode in tr}
-    for _ in range(args.windows):
-        for mode, (_, ppo) in tr.items():
-            torch.cuda.synchronize(dev)
-            t0 = time.perf_counter()
-            for _ in range(args.iterations):
-                ppo.iterate()
-            torch.cuda.synchronize(dev)
-            w[mode].append((time.perf_counter() - t0) * 1e3 / args.iterations)
-    for env, ppo in tr.values():
-        ppo.close()
-        env.close()
-    r = dict(summary(w), trainer=dict(hp, env_id="InvertedPendulumPyBulletEnv-v0", envs=256, backward="hip"),
+    w, _ = pendulum_windows(dev, modes, args.windows, args.iterations, base=dict(backward="hip"))
+    r = dict(summary(w), trainer=dict(HP, env_id=ENV_ID, envs=ENVS, backward="hip"),
              unit="ms per PPO.iterate()", iterations_per_window=args.iterations)
     r["median_below_the_torch_optimiser_window_minimum"] = {k: r["median"][k] < r["min"]["torch_opt"]
                                                             for k in ("hip_opt", "hip_opt_graph")}
@@ -167,12 +115,8 @@ def bench_iterate(args, dev):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "ppo_opt.json"))
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--windows", type=int, default=5)
-    ap.add_argument("--calls", type=int, default=20, help="minibatch steps per timed window")
-    ap.add_argument("--iterations", type=int, default=5, help="PPO.iterate() calls per timed window")
+    ap = parser("ppo_opt.json", calls=20, calls_help="minibatch steps per timed window",
+                iterations_help="PPO.iterate() calls per timed window")
     ap.add_argument("--shapes", nargs="*", default=list(base.SHAPES))
     args = ap.parse_args()
     import torch
@@ -189,10 +133,7 @@ def main():
     print("PPO.iterate() ms median [min, max]  " + "  ".join(
         f"{k} {r['median'][k]:.2f} [{r['min'][k]:.2f}, {r['max'][k]:.2f}]" for k in r["median"]) +
         f"  below the torch optimiser's minimum: {r['median_below_the_torch_optimiser_window_minimum']}")
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(res, f, indent=1)
-    print(json.dumps({"done": True, "out": args.out}))
+    finish(res, args.out)
 
 
 if __name__ == "__main__":

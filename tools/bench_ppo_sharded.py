@@ -1,7 +1,6 @@
 #!/usr/bin/env python3
 """The PPO gradient as parts and the data-parallel trainer.  tools/bench_ppo_update.py's shapes
-and section 11's protocol: warm-up, five windows bracketed by device events (iterate: a host clock around a
-synchronise), the legs alternated per window, medians with [min, max].
+and tools/benchlib.py's protocol (section 11's).
 
   grad      at the five shapes and on both paths: PPOGrad.run alone in a process ("run"); with --lib PATH (another
             build of libpbg_amd.so, the parent commit's) the parent's PPOGrad.run, likewise alone in a process
@@ -23,29 +22,18 @@ synchronise), the legs alternated per window, medians with [min, max].
 """
 from __future__ import annotations
 
-import argparse
 import json
 import math
 import os
 import socket
 import statistics
 import subprocess
-import sys
-import time
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
-sys.path.insert(0, os.path.join(REPO, "tools"))
+from bench_ppo_update import CLIP, ENT_COEF, SHAPES, VF_COEF
+from benchlib import (ENV_ID, ENVS, HP, child_cmd, device_windows, finish, last_json, parser, pendulum_windows, run_child,
+                      summary, use_library, wall_windows, warm_up)
 
-from bench_ppo_update import CLIP, ENT_COEF, SHAPES, VF_COEF  # noqa: E402
-
-HP = dict(hidden=(64, 64), steps=32, lr=3e-3, epochs=4, minibatches=4, log_std=-0.5)
-ENV_ID, ENVS = "InvertedPendulumPyBulletEnv-v0", 256
-
-
-def summary(w):
-    return {"windows": w, "median": {k: statistics.median(v) for k, v in w.items()}, "min": {k: min(v) for k, v in w.items()},
-            "max": {k: max(v) for k, v in w.items()}}
+BASE = dict(backward="hip", optimizer="hip", permutation="device")
 
 
 def bench_grad(args, dev, parts):
@@ -93,68 +81,30 @@ def bench_grad(args, dev, parts):
 
                 legs["parts"] = by_parts
                 rec.update(G=G, Dtot=dtot, bytes_all_gathered_per_minibatch=G * (4 * dtot + 32), launches={"run": 2, "parts": 2})
-            for _ in range(args.warmup):
-                for f in legs.values():
-                    f()
+            warm_up(legs, args.warmup)
             if parts:   # the last leg was "parts": its bits are run's
                 got = [t.clone() for t in out.values()]
                 legs["run"]()
                 torch.cuda.synchronize(dev)
                 rec["parts_equal_run_bitwise"] = all(torch.equal(a.view(torch.uint8), b.view(torch.uint8))
                                                      for a, b in zip(got, out.values()))
-            stream = torch.cuda.current_stream(dev)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            w = {leg: [] for leg in legs}
-            for _ in range(args.windows):
-                for leg, f in legs.items():
-                    torch.cuda.synchronize(dev)
-                    e0.record(stream)
-                    for _ in range(args.calls):
-                        f()
-                    e1.record(stream)
-                    torch.cuda.synchronize(dev)
-                    w[leg].append(e0.elapsed_time(e1) * 1e3 / args.calls)
+            rec["windows"] = device_windows(dev, legs, args.windows, args.calls)
             g.close()
-            rec["windows"] = w
             res[f"{name}/{path}"] = rec
     return res
-
-
-def time_iterate(args, ppo, dev):
-    import torch
-    for _ in range(3):
-        ppo.iterate()
-    w = []
-    for _ in range(args.windows):
-        torch.cuda.synchronize(dev)
-        t0 = time.perf_counter()
-        for _ in range(args.iterations):
-            ppo.iterate()
-        torch.cuda.synchronize(dev)
-        w.append((time.perf_counter() - t0) * 1e3 / args.iterations)
-    return w
 
 
 def child(args):
     """One process, one library: its legs' windows as one JSON line."""
     import torch
-    import pybulletgym_amd  # noqa: F401
-    from pybulletgym_amd import _native
-    if args.lib:
-        _native.LIB_PATH = os.path.abspath(args.lib)
+    use_library(args.lib)
     dev = torch.device("cuda:0")
     if args.child == "grad_run":   # PPOGrad.run alone: what the parent's library can do, under the same conditions
         out = bench_grad(args, dev, False)
     elif args.child == "grad":
         out = bench_grad(args, dev, True)
     elif args.child == "one":
-        from pybulletgym_amd.ppo import PPO
-        from pybulletgym_amd.vec_env import VecEnv
-        env = VecEnv(ENV_ID, ENVS, device=dev, seed=0, autoreset=True, precision=64)
-        ppo = PPO(env, seed=0, backward="hip", optimizer="hip", permutation="device", **HP)
-        out = {"one_process": time_iterate(args, ppo, dev)}
-        ppo.close()
-        env.close()
+        out = pendulum_windows(dev, {"one_process": BASE}, args.windows, args.iterations)[0]
     else:   # a rank of the two: RANK, WORLD_SIZE, MASTER_ADDR and MASTER_PORT are in the environment
         import torch.distributed as dist
         from pybulletgym_amd.distributed import ShardedVecEnv
@@ -163,7 +113,10 @@ def child(args):
         dist.init_process_group("gloo", init_method="env://", rank=rank, world_size=world)
         shard = ShardedVecEnv(ENV_ID, ENVS, rank, world, dev, seed=0, autoreset=True, precision=64)
         ppo = ShardedPPO(shard, seed=0, **HP)
-        out = {f"two_ranks_gloo_rank{rank}": time_iterate(args, ppo, dev)}
+        for _ in range(3):
+            ppo.iterate()
+        out = wall_windows(lambda: torch.cuda.synchronize(dev), {f"two_ranks_gloo_rank{rank}": ppo.iterate}, args.windows,
+                           args.iterations)
         dist.barrier()
         ppo.close()
         shard.env.close()
@@ -171,60 +124,33 @@ def child(args):
     print(json.dumps(out))
 
 
-def child_cmd(args, what, lib=None):
-    cmd = [sys.executable, os.path.abspath(__file__), "--child", what, "--warmup", str(args.warmup), "--windows", str(args.windows),
-           "--calls", str(args.calls), "--iterations", str(args.iterations), "--shapes"] + list(args.shapes)
-    return cmd + (["--lib", lib] if lib else [])
-
-
-def last_json(p, cmd):
-    if p.returncode:
-        raise RuntimeError(f"{' '.join(cmd)} failed ({p.returncode}):\n{p.stderr[-3000:]}")
-    return json.loads(p.stdout.strip().splitlines()[-1])
-
-
-def run_child(args, what, lib=None):
-    cmd = child_cmd(args, what, lib)
-    return last_json(subprocess.run(cmd, capture_output=True, text=True, timeout=600), cmd)
-
-
 def run_ranks(args, world=2):
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
     port = s.getsockname()[1]
     s.close()
-    cmd = child_cmd(args, "rank")
+    cmd = child_cmd(__file__, "rank", args)
     procs = [subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
                               env=dict(os.environ, RANK=str(r), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port)))
              for r in range(world)]
-    out = {}
+    out, texts = {}, []
     try:
         for p in procs:
-            so, se = p.communicate(timeout=600)
-            p.stdout_text, p.stderr_text = so, se
+            texts.append(p.communicate(timeout=600))
     finally:
         for p in procs:
             if p.poll() is None:
                 p.kill()
-    for p in procs:
-        if p.returncode:
-            raise RuntimeError(f"a rank failed ({p.returncode}):\n{p.stderr_text[-3000:]}")
-        out.update(json.loads(p.stdout_text.strip().splitlines()[-1]))
+    for p, (so, se) in zip(procs, texts):
+        out.update(last_json(cmd, p.returncode, so, se))
     return out
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "ppo_sharded.json"))
-    ap.add_argument("--lib", default=None, help="another build of libpbg_amd.so (the parent commit's, to alternate with)")
-    ap.add_argument("--rounds", type=int, default=2, help="child processes per library")
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--windows", type=int, default=5)
-    ap.add_argument("--calls", type=int, default=20, help="gradient calls per timed window")
-    ap.add_argument("--iterations", type=int, default=5, help="iterate() calls per timed window")
+    ap = parser("ppo_sharded.json", calls=20, calls_help="gradient calls per timed window",
+                iterations_help="iterate() calls per timed window", rounds=2)
     ap.add_argument("--shapes", nargs="*", default=list(SHAPES))
     ap.add_argument("--skip-iterate", action="store_true", help="the gradient legs only")
-    ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.child:
         return child(args)
@@ -234,7 +160,7 @@ def main():
         # a third process alternates run and parts per window on this tree ("run_beside_parts", "parts")
         for what, lib, names in ([("grad_run", args.lib, {"run": "parent_run"})] if args.lib else []) + \
                 [("grad_run", None, {"run": "run"}), ("grad", None, {"run": "run_beside_parts", "parts": "parts"})]:
-            for key, rec in run_child(args, what, lib).items():
+            for key, rec in run_child(__file__, what, args, lib).items():
                 g = grad.setdefault(key, {"windows": {}, "windows_per_round": {}})
                 for leg, v in rec.pop("windows").items():
                     g["windows"].setdefault(names[leg], []).extend(v)
@@ -242,7 +168,7 @@ def main():
                 if what == "grad":
                     g.update(rec)
         if not args.skip_iterate:
-            for k, v in list(run_child(args, "one").items()) + list(run_ranks(args).items()):
+            for k, v in list(run_child(__file__, "one", args).items()) + list(run_ranks(args).items()):
                 it.setdefault(k, []).extend(v)
     res = {"unit": "us per minibatch gradient", "calls_per_window": args.calls, "rounds": args.rounds,
            "parent_library": "another build of libpbg_amd.so, given with --lib" if args.lib else None, "grad": {}}
@@ -264,17 +190,13 @@ def main():
              f"({', '.join(f'{d:+.1f}' for d in r['run_median_minus_parent_maximum_us_per_round'])} us; pooled "
              f"{r['run_median_not_above_parent_window_maximum_pooled']})" if args.lib else ""), flush=True)
     if it:
-        res["iterate"] = r = dict(summary(it), trainer=dict(HP, env_id=ENV_ID, envs=ENVS, backward="hip", optimizer="hip",
-                                                            permutation="device"),
+        res["iterate"] = r = dict(summary(it), trainer=dict(HP, env_id=ENV_ID, envs=ENVS, **BASE),
                                   unit="ms per iterate()", iterations_per_window=args.iterations,
                                   note="two ranks on one device over gloo: host-staged collectives, not representative of xGMI; "
                                        "no multi-GPU time can be measured on one GPU")
         print("iterate() ms median [min, max]  " + "  ".join(
             f"{k} {r['median'][k]:.2f} [{r['min'][k]:.2f}, {r['max'][k]:.2f}]" for k in r["median"]))
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(res, f, indent=1)
-    print(json.dumps({"done": True, "out": args.out}))
+    finish(res, args.out)
 
 
 if __name__ == "__main__":

@@ -11,9 +11,8 @@ at five shapes: the pendulum trainer's (5, 64, 64, 1) with 2,048 rows of 8,192, 
 131,072 rows of 524,288, (44, 256, 256, 17) with 16,384 rows of 65,536, and the two reference networks, Ant's
 (28, 128, 64, 8) with 131,072 rows of 524,288 and Humanoid's (44, 256, 128, 17) with 16,384 rows of 65,536.  Then
 (unless --skip-iterate) one whole PPO.iterate() of the
-pendulum trainer (256 envs x 32 steps, 4 epochs x 4 minibatches) in both modes.  Section 11's protocol: warm-up,
-five windows bracketed by device events (iterate: a host clock around a synchronise), the legs alternated per
-window, medians with [min, max].  The FLOP count is the algorithm's: per row and network 2 K H for each layer's
+pendulum trainer (256 envs x 32 steps, 4 epochs x 4 minibatches) in both modes.  tools/benchlib.py's protocol (section
+11's).  The FLOP count is the algorithm's: per row and network 2 K H for each layer's
 forward, 2 K H for its weight gradient and 2 K H for the input gradient of layers two and three.
 
   python tools/bench_ppo_update.py [--out profiles/ppo_grad_mfma.json] [--shapes wide ant_ref ...] [--skip-iterate]
@@ -22,16 +21,9 @@ profiles/ppo_grad.json is the record of the two-leg version of this tool (sectio
 """
 from __future__ import annotations
 
-import argparse
-import json
 import math
-import os
-import statistics
-import sys
-import time
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
+from benchlib import ENV_ID, ENVS, HP, device_windows, finish, parser, pendulum_windows, summary, warm_up
 
 SHAPES = {"pendulum": ((5, 64, 64, 1), 8192, 2048), "ant": ((28, 64, 64, 8), 524288, 131072),
           "wide": ((44, 256, 256, 17), 65536, 16384), "ant_ref": ((28, 128, 64, 8), 524288, 131072),
@@ -106,33 +98,20 @@ def bench_shape(name, dims, B, Bm, args, dev):
             "hip_mfma": lambda: hip(gm)}
     rel = lambda: max(float((x - p.grad).abs().max() / p.grad.abs().max())  # noqa: E731
                       for x, p in ((ga, theta_a), (gc, theta_c), (gl, log_std)))
-    for _ in range(args.warmup):
-        for f in legs.values():
-            f()
+    warm_up(legs, args.warmup)
     # ga, gc, gl hold the last leg's result: the matrix-core path's; then the FMA path's once more
     torch.cuda.synchronize(dev)
     diff_mfma = rel()
     hip()
     torch.cuda.synchronize(dev)
     diff = rel()
-    stream = torch.cuda.current_stream(dev)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    w = {leg: [] for leg in legs}
-    for _ in range(args.windows):
-        for leg, f in legs.items():
-            torch.cuda.synchronize(dev)
-            e0.record(stream)
-            for _ in range(args.calls):
-                f()
-            e1.record(stream)
-            torch.cuda.synchronize(dev)
-            w[leg].append(e0.elapsed_time(e1) * 1e3 / args.calls)
+    s = summary(device_windows(dev, legs, args.windows, args.calls))
     g.close()
     gm.close()
-    med = {k: statistics.median(v) for k, v in w.items()}
+    w, med = s["windows"], s["median"]
     fl = flops_per_row(dims) * Bm
     return {"dims": dims, "batch_rows": B, "minibatch_rows": Bm, "unit": "us per minibatch gradient", "windows": w, "median": med,
-            "min": {k: min(v) for k, v in w.items()}, "max": {k: max(v) for k, v in w.items()},
+            "min": s["min"], "max": s["max"],
             "torch_over_hip": med["torch"] / med["hip"], "torch_over_hip_mfma": med["torch"] / med["hip_mfma"],
             "hip_over_hip_mfma": med["hip"] / med["hip_mfma"],
             "hip_mfma_median_below_hip_window_minimum": med["hip_mfma"] < min(w["hip"]), "flops_per_minibatch": fl,
@@ -143,42 +122,16 @@ def bench_shape(name, dims, B, Bm, args, dev):
 
 
 def bench_iterate(args, dev):
-    import torch
-    from pybulletgym_amd.ppo import PPO
-    from pybulletgym_amd.vec_env import VecEnv
-    hp = dict(hidden=(64, 64), steps=32, lr=3e-3, epochs=4, minibatches=4, log_std=-0.5)
-    tr = {}
-    for mode in ("torch", "hip", "hip_mfma"):
-        env = VecEnv("InvertedPendulumPyBulletEnv-v0", 256, device=dev, seed=0, autoreset=True, precision=64)
-        kw = dict(backward="hip", grad_path="mfma") if mode == "hip_mfma" else dict(backward=mode)
-        tr[mode] = (env, PPO(env, seed=0, **kw, **hp))
-        for _ in range(3):
-            tr[mode][1].iterate()
-    w = {mode: [] for mode in tr}
-    for _ in range(args.windows):
-        for mode, (_, ppo) in tr.items():
-            torch.cuda.synchronize(dev)
-            t0 = time.perf_counter()
-            for _ in range(args.iterations):
-                ppo.iterate()
-            torch.cuda.synchronize(dev)
-            w[mode].append((time.perf_counter() - t0) * 1e3 / args.iterations)
-    for env, ppo in tr.values():
-        ppo.close()
-        env.close()
-    med = {k: statistics.median(v) for k, v in w.items()}
-    return {"trainer": dict(hp, env_id="InvertedPendulumPyBulletEnv-v0", envs=256), "unit": "ms per PPO.iterate()", "windows": w,
-            "median": med, "min": {k: min(v) for k, v in w.items()}, "max": {k: max(v) for k, v in w.items()},
-            "torch_over_hip": med["torch"] / med["hip"], "iterations_per_window": args.iterations}
+    modes = {"torch": dict(backward="torch"), "hip": dict(backward="hip"), "hip_mfma": dict(backward="hip", grad_path="mfma")}
+    s = summary(pendulum_windows(dev, modes, args.windows, args.iterations)[0])
+    return {"trainer": dict(HP, env_id=ENV_ID, envs=ENVS), "unit": "ms per PPO.iterate()", "windows": s["windows"],
+            "median": s["median"], "min": s["min"], "max": s["max"],
+            "torch_over_hip": s["median"]["torch"] / s["median"]["hip"], "iterations_per_window": args.iterations}
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "ppo_grad_mfma.json"))
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--windows", type=int, default=5)
-    ap.add_argument("--calls", type=int, default=20, help="gradient calls per timed window")
-    ap.add_argument("--iterations", type=int, default=5, help="PPO.iterate() calls per timed window")
+    ap = parser("ppo_grad_mfma.json", calls=20, calls_help="gradient calls per timed window",
+                iterations_help="PPO.iterate() calls per timed window")
     ap.add_argument("--shapes", nargs="*", default=list(SHAPES))
     ap.add_argument("--skip-iterate", action="store_true", help="the gradient legs only")
     args = ap.parse_args()
@@ -198,10 +151,7 @@ def main():
         print("PPO.iterate() ms median [min, max]  " + "  ".join(
             f"{k} {r['median'][k]:.2f} [{r['min'][k]:.2f}, {r['max'][k]:.2f}]" for k in r["median"]) +
             f"  torch / hip {r['torch_over_hip']:.2f}")
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(res, f, indent=1)
-    print(json.dumps({"done": True, "out": args.out}))
+    finish(res, args.out)
 
 
 if __name__ == "__main__":

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""What reward scaling by a running std of the discounted return costs.  tools/bench_ppo_iter.py's
-protocol: warm-up, five windows bracketed by a synchronise, the legs alternated per window, medians with [min, max].
+"""What reward scaling by a running std of the discounted return costs.  tools/benchlib.py's
+protocol.
 
   launches  pbg_ret_stats_walk, _finalize and _apply alone and as one round, at Ant's 32 x 16,384 and at the pendulum
             trainer's 32 x 256, beside a torch restatement of the same round (a Python loop over t with float64
@@ -16,24 +16,11 @@ protocol: warm-up, five windows bracketed by a synchronise, the legs alternated 
 """
 from __future__ import annotations
 
-import argparse
-import json
-import os
-import statistics
-import sys
-import time
+from benchlib import ENV_ID, ENVS, HP, device_windows, finish, parser, pendulum_windows, summary, warm_up
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
-
-HP = dict(hidden=(64, 64), steps=32, lr=3e-3, epochs=4, minibatches=4, log_std=-0.5)
+BASE = dict(backward="hip", optimizer="hip", permutation="device", graph="iteration")
 SHAPES = {"ant_32x16384": (32, 16384), "pendulum_32x256": (32, 256)}
 GAMMA, CLIP, FLOOR = 0.99, 10.0, 1e-2
-
-
-def summary(w):
-    return {"windows": w, "median": {k: statistics.median(v) for k, v in w.items()}, "min": {k: min(v) for k, v in w.items()},
-            "max": {k: max(v) for k, v in w.items()}}
 
 
 def torch_round(rew, done, carry, tot, out):
@@ -66,8 +53,6 @@ def bench_launches(args, dev):
     import torch
     from pybulletgym_amd.ppo import RetStats
     res = {}
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    stream = torch.cuda.current_stream(dev)
     for name, (T, n) in SHAPES.items():
         r = np.random.default_rng(0)
         rew = torch.from_numpy((2.0 * r.standard_normal((T, n))).astype(np.float32)).to(dev)
@@ -84,9 +69,7 @@ def bench_launches(args, dev):
         legs = {"walk": lambda: obj.update(rew, done), "finalize": lambda: obj.finalize(var_floor=FLOOR),
                 "apply": lambda: obj.apply(rew, out=out, clip=CLIP), "round": round_,
                 "torch_round": lambda: torch_round(rew, done, carry, tot, out_t)}
-        for _ in range(args.warmup):
-            for g in legs.values():
-                g()
+        warm_up(legs, args.warmup)
         graphs = {}
         for leg, g in legs.items():   # --calls calls of the leg as one graph: no host work between its kernels
             torch.cuda.synchronize(dev)
@@ -95,23 +78,10 @@ def bench_launches(args, dev):
                 for _ in range(args.calls):
                     g()
             graphs[leg].replay()
-        stream = torch.cuda.current_stream(dev)
-        w = {leg: [] for leg in legs}
-        wg = {leg: [] for leg in legs}
-        for _ in range(args.windows):
-            for leg, g in legs.items():
-                torch.cuda.synchronize(dev)
-                e0.record(stream)
-                for _ in range(args.calls):
-                    g()
-                e1.record(stream)
-                torch.cuda.synchronize(dev)
-                w[leg].append(e0.elapsed_time(e1) * 1e3 / args.calls)
-                e0.record(stream)
-                graphs[leg].replay()
-                e1.record(stream)
-                torch.cuda.synchronize(dev)
-                wg[leg].append(e0.elapsed_time(e1) * 1e3 / args.calls)
+        # each leg's eager window, then its graph's, before the next leg's
+        both = {(leg, how): f for leg, g in legs.items() for how, f in (("eager", g), ("graph", graphs[leg].replay))}
+        both = device_windows(dev, both, args.windows, args.calls, once=[k for k in both if k[1] == "graph"])
+        w, wg = ({leg: both[leg, how] for leg in legs} for how in ("eager", "graph"))
         # the two rounds agree to rounding (the sums' order differs): both scales, for the record
         obj.reset()
         carry.zero_()
@@ -130,32 +100,11 @@ def bench_launches(args, dev):
 
 
 def bench_iterate(args, dev):
-    import torch
-    from pybulletgym_amd.ppo import PPO
-    from pybulletgym_amd.vec_env import VecEnv
-    tr = {}
     # a second trainer without the option: what two trainers of one process differ by
-    for leg, kw in (("reward_norm_off", {}), ("reward_norm_on", dict(reward_norm=True)), ("reward_norm_off_second", {})):
-        env = VecEnv("InvertedPendulumPyBulletEnv-v0", 256, device=dev, seed=0, autoreset=True, precision=64)
-        tr[leg] = (env, PPO(env, seed=0, backward="hip", optimizer="hip", permutation="device", graph="iteration", **HP, **kw))
-        for _ in range(3):
-            tr[leg][1].iterate()
-    w = {leg: [] for leg in tr}
-    for _ in range(args.windows):
-        for leg, (_, ppo) in tr.items():
-            torch.cuda.synchronize(dev)
-            t0 = time.perf_counter()
-            for _ in range(args.iterations):
-                ppo.iterate()
-            torch.cuda.synchronize(dev)
-            w[leg].append((time.perf_counter() - t0) * 1e3 / args.iterations)
-    finite = {leg: bool(torch.isfinite(ppo.actor_theta.data).all()) for leg, (_, ppo) in tr.items()}
-    for env, ppo in tr.values():
-        ppo.close()
-        env.close()
+    legs = {"reward_norm_off": {}, "reward_norm_on": dict(reward_norm=True), "reward_norm_off_second": {}}
+    w, finite = pendulum_windows(dev, legs, args.windows, args.iterations, base=BASE)
     assert all(finite.values()), finite
-    it = dict(summary(w), trainer=dict(HP, env_id="InvertedPendulumPyBulletEnv-v0", envs=256, backward="hip", optimizer="hip",
-                                       permutation="device", graph="iteration"),
+    it = dict(summary(w), trainer=dict(HP, env_id=ENV_ID, envs=ENVS, **BASE),
               unit="ms per PPO.iterate()", iterations_per_window=args.iterations,
               note="reward_norm_on also copies rew_scale out after every iterate(): one launch outside the graph")
     it["on_minus_off_median_ms"] = it["median"]["reward_norm_on"] - it["median"]["reward_norm_off"]
@@ -163,13 +112,8 @@ def bench_iterate(args, dev):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "ret_stats.json"))
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--windows", type=int, default=5)
-    ap.add_argument("--calls", type=int, default=20, help="calls per timed window of a launch leg")
-    ap.add_argument("--iterations", type=int, default=5, help="PPO.iterate() calls per timed window")
-    args = ap.parse_args()
+    args = parser("ret_stats.json", calls=20, calls_help="calls per timed window of a launch leg",
+                  iterations_help="PPO.iterate() calls per timed window").parse_args()
     import torch
     import pybulletgym_amd  # noqa: F401
     dev = torch.device("cuda:0")
@@ -182,10 +126,7 @@ def main():
     it = res["iterate"]
     print("PPO.iterate() ms median [min, max]  " + "  ".join(
         f"{k} {it['median'][k]:.3f} [{it['min'][k]:.3f}, {it['max'][k]:.3f}]" for k in it["median"]), flush=True)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(res, f, indent=1)
-    print(json.dumps({"done": True, "out": args.out}))
+    finish(res, args.out)
 
 
 if __name__ == "__main__":

@@ -26,29 +26,15 @@ tests directory staying where it is.
 """
 from __future__ import annotations
 
-import argparse
-import json
 import os
-import statistics
 import sys
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
+from benchlib import REPO, capture, device_windows, finish, parser, summary
+
 sys.path.insert(0, os.path.join(REPO, "tests"))
 
 WORKLOADS = {"ant": ("AntPyBulletEnv-v0", 16384), "humanoid": ("HumanoidPyBulletEnv-v0", 4096)}
 K = 20  # steps per graph
-
-
-def capture(fn, dev):
-    import torch
-    s = torch.cuda.Stream(dev)
-    s.wait_stream(torch.cuda.current_stream(dev))
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g, stream=s):
-        fn()
-    torch.cuda.current_stream(dev).wait_stream(s)
-    return g
 
 
 def run_workload(name, args):
@@ -116,25 +102,11 @@ def run_workload(name, args):
     torch.cuda.synchronize(dev)
     graphs = {"A": capture(leg_a, dev), "B": capture(leg_b, dev), "C": capture(leg_c, dev),
               "C2": capture(leg_c2, dev)}
-    for leg in LEGS:
-        run_c2(graphs[leg]) if leg == "C2" else graphs[leg].replay()
-    torch.cuda.synchronize(dev)
-    stream = torch.cuda.current_stream(dev)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    windows = {leg: [] for leg in LEGS}
-    for _ in range(args.windows):
-        for leg in LEGS:
-            torch.cuda.synchronize(dev)
-            e0.record(stream)
-            for _ in range(args.replays):
-                run_c2(graphs[leg]) if leg == "C2" else graphs[leg].replay()
-            e1.record(stream)
-            torch.cuda.synchronize(dev)
-            windows[leg].append(e0.elapsed_time(e1) * 1e3 / (args.replays * K))  # us per step
-    med = {leg: statistics.median(w) for leg, w in windows.items()}
+    replay = {leg: (lambda: run_c2(graphs["C2"])) if leg == "C2" else graphs[leg].replay for leg in LEGS}
+    s = summary(device_windows(dev, replay, args.windows, args.replays, warmup=1, per=K))  # us per step
+    windows, med = s["windows"], s["median"]
     out = {"env_id": env_id, "n_envs": n, "precision": 64, "steps_per_graph": K, "replays_per_window": args.replays,
-           "unit": "us per env-batch step", "windows": windows, "median": med,
-           "min": {leg: min(w) for leg, w in windows.items()}, "max": {leg: max(w) for leg, w in windows.items()},
+           "unit": "us per env-batch step", "windows": windows, "median": med, "min": s["min"], "max": s["max"],
            "B_minus_C_us": med["B"] - med["C"], "A_minus_C_us": med["A"] - med["C"],
            "B_minus_C2_us": med["B"] - med["C2"], "A_minus_C2_us": med["A"] - med["C2"],
            "C2_minus_C_us": med["C2"] - med["C"],
@@ -172,12 +144,9 @@ def actor_only(args):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "rollout_closed_loop.json"))
+    ap = parser("rollout_closed_loop.json", warmup=20)
     ap.add_argument("--only", choices=sorted(WORKLOADS), default=None)
     ap.add_argument("--preroll", type=int, default=200)
-    ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--windows", type=int, default=5)
     ap.add_argument("--replays", type=int, default=10, help="graph replays (of 20 steps) per timed window")
     ap.add_argument("--actor-only", action="store_true")
     args = ap.parse_args()
@@ -185,15 +154,12 @@ def main():
         return actor_only(args)
     res = {"workloads": {name: run_workload(name, args) for name in WORKLOADS if args.only in (None, name)}}
     res["done"] = all(w["B_slowest_faster_than_A_fastest"] for w in res["workloads"].values())
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(res, f, indent=1)
     for name, w in res["workloads"].items():
         print(f"{name}: A {w['median']['A']:.1f} us  B {w['median']['B']:.1f} us  C {w['median']['C']:.1f} us  "
               f"C2 {w['median']['C2']:.1f} us  B-C {w['B_minus_C_us']:.1f} us  B-C2 {w['B_minus_C2_us']:.1f} us  "
               f"A-C2 {w['A_minus_C2_us']:.1f} us  C2==B states: {w['C2_final_obs_equals_B']}  "
               f"B max {w['max']['B']:.1f} < A min {w['min']['A']:.1f}: {w['B_slowest_faster_than_A_fastest']}")
-    print(json.dumps({"done": res["done"], "out": args.out}))
+    finish(res, args.out, res["done"])
 
 
 if __name__ == "__main__":
